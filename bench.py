@@ -10,14 +10,19 @@ timed region, over gloo).
 
 Dataset: seed_i = SHA-256("SVSEED"||u64le i), msg_i =
 SHA-256("SVMSG"||u64le i); keypairs and signatures are generated ON THE GPU
-by the engine's RFC 8032 signer, and on rank 0 the SHA-256 of the
-pk||sig||msg stream is compared with the libsodium-generated digest in
+by the engine's RFC 8032 signer, and with --full rank 0 compares the SHA-256
+of the pk||sig||msg stream with the libsodium-generated digest in
 tests/golden/digests.json, so the bench verifies the exact dataset libsodium
 would produce.
+
+A plain run sets up, warms up, times --steps steps, writes the last step's
+outputs when --dump-outputs is given, and prints the result line; every other
+leg below runs only with --full (and its own --no-* switch unset).
 
 Printed by rank 0: one JSON line (contract in the task statement) with
   roofline      VALU-integer roofline of the verify kernel (kernel time from
                 HIP events on the engine's stream over the timed region)
+and with --full also
   cpu_baseline  libsodium crypto_sign_verify_detached (the function
                 PubKeyUtils::verifySig calls), multithreaded on this host's
                 cores over a bounded sample of the same dataset
@@ -597,12 +602,32 @@ def config4_integrated(sv, sodium, n=48000):
     return res
 
 
+def dump_outputs(outdir, d_verdict, d_bitmap, n, rank, world):
+    """What the last timed step's sv_ed25519_verify_device call handed its
+    caller, as float32 .npy files: the n verdict bytes, and the first n bits
+    of the ballot bitmap (bit i of word w = row 64 w + i) unpacked to 0/1.
+    8 bytes per signature in all; one pair of files per rank when N > 1."""
+    os.makedirs(outdir, exist_ok=True)
+    tag = "" if world == 1 else "_rank%d" % rank
+    verdict = d_verdict.cpu().numpy()
+    words = d_bitmap.cpu().numpy().astype("<i8")
+    bits = np.unpackbits(words.view(np.uint8), bitorder="little")[:n]
+    np.save(os.path.join(outdir, "verdict%s.npy" % tag), verdict.astype(np.float32))
+    np.save(os.path.join(outdir, "bitmap_bits%s.npy" % tag), bits.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1 << 20, help="signatures per GPU per step")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the timed steps: dataset digest, host API, in-process "
+                         "multi-GPU, 1k-batch latency, CPU baselines, configs 1, 3, 4, 5 (the --no-* switches "
+                         "below drop single legs of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write the last step's verdicts and bitmap as DIR/<name>.npy (float32)")
     ap.add_argument("--latency-iters", type=int, default=1000)
     ap.add_argument("--cpu-sample", type=int, default=524288)
     ap.add_argument("--no-cpu", action="store_true")
@@ -613,6 +638,8 @@ def main():
     ap.add_argument("--no-config35", action="store_true",
                     help="skip the config-3 (5000-tx set) and config-5 (64M signatures) blocks")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -659,7 +686,7 @@ def main():
 
     digest_ok = None
     pk_h = sig_h = None
-    if rank == 0:
+    if rank == 0 and args.full:
         pk_h = d_pk.cpu().numpy().reshape(n, 32)
         sig_h = d_sig.cpu().numpy().reshape(n, 64)
         with open(os.path.join(REPO, "tests", "golden", "digests.json")) as f:
@@ -695,6 +722,8 @@ def main():
     full = n // 64
     bitmap_ok = bool((d_bitmap[:full] == -1).all().item())
     verdicts_ok = verdict_count == n and bitmap_ok
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_verdict, d_bitmap, n, rank, world)
 
     global_digest = None
     if world > 1:
@@ -716,7 +745,7 @@ def main():
     # H2D, kernels and D2H pipelined in 2^18-signature chunks -- what a host
     # caller gets; reported beside the HBM-resident `value`, never as it
     host_api = None
-    if rank == 0 and not args.no_host_api:
+    if rank == 0 and args.full and not args.no_host_api:
         msg_h = msgs.reshape(n, 32)
         sv.verify_fixed(pk_h[:4096], sig_h[:4096], msg_h[:4096], 32, device=local)  # warm the staging
         best, ok_all = None, True
@@ -737,7 +766,7 @@ def main():
     # sees G > 1 slots (an 8-GPU node, or SV_DEVICE_MAP rehearsing slots on one
     # card) times a G x 2^20 host batch on 1, 2, 4, 8 slots.
     inproc = None
-    if rank == 0 and world == 1 and not args.no_host_api and n == 1 << 20:
+    if rank == 0 and world == 1 and args.full and not args.no_host_api and n == 1 << 20:
         try:
             inproc = in_process_multi_gpu(sv, pk_h, sig_h, msgs.reshape(n, 32))
         except Exception as e:
@@ -851,8 +880,8 @@ def main():
             result["in_process_multi_gpu"] = inproc
 
     # ---- latency @1k batch (config 4), rank 0 only
-    sodium = load_libsodium() if rank == 0 else None
-    if rank == 0 and not args.no_latency:
+    sodium = load_libsodium() if rank == 0 and args.full else None
+    if rank == 0 and args.full and not args.no_latency:
         try:
             if sodium is not None:
                 pks, sigs, lmsgs, expect = scp_latency_set(sodium)
@@ -984,7 +1013,7 @@ def main():
     # ---- CPU baseline (rank 0, every N: after the timed region and its final
     # barrier, on the host cores of this job; the other ranks wait at the next
     # collective)
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         try:
             threads, cpu_info = host_cpus()
             spath = sodium_path() if sodium is not None else None
@@ -1019,13 +1048,13 @@ def main():
                 log("config 1 (both shapes) in %.1fs" % (time.perf_counter() - t_c1))
         except Exception as e:  # (rank 0's optional legs: recorded, never the whole line)
             leg_failed(result, 'cpu_baseline', e)
-    if not args.no_config35 and n == 1 << 20 and 64 % world == 0:
+    if args.full and not args.no_config35 and n == 1 << 20 and 64 % world == 0:
         t_c = time.perf_counter()
         c5 = config5(sv, torch, dev, stream, local, d_pk, d_sig, d_msg, n, world, rank, barrier, dist)
         if rank == 0:
             result["config5"] = c5
             log("config 5 (64M signatures on %d GPU(s)) in %.1fs" % (world, time.perf_counter() - t_c))
-    if rank == 0 and not args.no_config35 and n == 1 << 20:
+    if rank == 0 and args.full and not args.no_config35 and n == 1 << 20:
         t_c = time.perf_counter()
         try:
             result["config3"] = config3()
