@@ -186,6 +186,41 @@ int svh_check_envelopes(const svh_envelope* env, size_t n, const svh_decorated_s
                         uint32_t protocol, int prefetch, int for_apply, svh_tx_result* results,
                         uint64_t* prefetched_pairs);
 
+/* svh_check_envelopes straight from the transaction bodies (catchup replay:
+ * every frame is fresh, nobody has computed its contents hash yet).  The
+ * envelopes' contents_hash / fee_bump_hash fields are ignored on input; the
+ * hashes are those of the bodies, sha256(networkID || envelope type || body)
+ * (TransactionFrame::getContentsHash, FeeBumpTransactionFrame::getContentsHash):
+ * envelope t's (inner) transaction is bodies[off .. off + len) of kind 0 (V1)
+ * or 1 (V0, hashed with its extra zero word), and with env[t].fee_bump set its
+ * fee-bump transaction is bodies[outer_off .. outer_off + outer_len).
+ * contents_hash_out / fee_bump_hash_out (n x 32 each) receive the hashes (zeros
+ * for the fee-bump hash of a plain envelope).
+ *   prefetch 0  the hashes are computed on the host (the reference's flow),
+ *               then exactly svh_check_envelopes' per-envelope checks
+ *   prefetch 1  the catchup form (side table, verify cache bypassed): the pairs
+ *               are enumerated without the hashes, ONE
+ *               sv_ed25519_verify_txbodies call hashes every body and verifies
+ *               every ed25519 pair, the digests become the hashes; signed-
+ *               payload pairs (their own message) are a second batch.  An
+ *               engine error re-runs on sv_ed25519_verify_txbodies_cpu
+ *               (counted in svh_engine_stats.fallbacks).
+ *   prefetch 2  SVH_ERR_INVALID_ARG (no keyed, cache-seeding body form) */
+typedef struct svh_envelope_body {
+  uint64_t off;
+  uint32_t len;
+  uint32_t kind; /* 0 V1, 1 V0 */
+  uint64_t outer_off;
+  uint32_t outer_len;
+  uint32_t reserved;
+} svh_envelope_body;
+int svh_check_envelopes_bodies(const svh_envelope* env, size_t n, const svh_decorated_sig* sigs, const svh_op* ops,
+                               const svh_signer* signers, const svh_account* accounts, size_t naccounts,
+                               uint32_t protocol, int prefetch, int for_apply, svh_tx_result* results,
+                               uint64_t* prefetched_pairs, const uint8_t* network_id, const uint8_t* bodies,
+                               const svh_envelope_body* body, uint8_t* contents_hash_out,
+                               uint8_t* fee_bump_hash_out);
+
 typedef struct svh_mb_stats {
   uint64_t items, batches, flushed_by_size, flushed_by_deadline, max_batch;
   double lat_p50_us, lat_p99_us; /* submit -> verdict ready (submit mode) */

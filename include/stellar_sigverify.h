@@ -233,6 +233,62 @@ int sv_verify_cache_keys_device(int device, const void* d_pk, const void* d_sig,
 int sv_sha256_device(int device, const void* d_data, const uint64_t* d_off, const uint32_t* d_len,
                      uint32_t fixed_len, size_t n, void* d_digests, void* stream);
 
+/* ---- Signatures straight from transaction bodies ------------------------
+ * One device pass from transaction bytes to verdicts: the engine computes each
+ * body's contents hash itself -- sha256(xdr_to_opaque(networkID, ENVELOPE_TYPE_TX,
+ * tx)), TransactionFrame::getContentsHash /
+ * FeeBumpTransactionFrame::getContentsHash -- and verifies the body's
+ * signatures over it (csrc/sv_txhash.hip, then the verify kernels' 32-byte
+ * mode on the same stream).  No caller-computed contents hash.
+ *
+ *   n_bodies bodies  body t = bodies[body_off[t] .. body_off[t] + body_len[t])
+ *                    body_kind[t]: the hashed bytes are prefix || body, with
+ *                      SV_TXBODY_V1       networkID || 00 00 00 02
+ *                      SV_TXBODY_V0       networkID || 00 00 00 02 || 00 00 00 00
+ *                      SV_TXBODY_FEE_BUMP networkID || 00 00 00 05
+ *   n signatures     pk (n x 32), sig (n x 64), grouped by body in CSR form:
+ *                    body t owns signatures sig_begin[t] .. sig_begin[t+1]-1;
+ *                    sig_begin has n_bodies + 1 entries, is non-decreasing,
+ *                    sig_begin[0] == 0, sig_begin[n_bodies] == n.  A body may
+ *                    own no signature; it still gets a digest.
+ *   verdict          n bytes out (may be NULL when n == 0)
+ *   digests          optional, n_bodies x 32 bytes out
+ * n == 0 with n_bodies > 0 is legal: only digests are produced.  A null
+ * required pointer, a kind > 2 or a malformed sig_begin is SV_ERR_INVALID_ARG.
+ *
+ * Host buffers: the bodies go up in chunks of whole bodies, each of at most
+ * the staging chunk of signatures (SV_STAGE_CHUNK) and SV_TXBODY_CHUNK_BYTES
+ * (default 64 MiB) of body bytes (a larger single body is a chunk of its own),
+ * double-buffered: chunk c+1 is packed and copied up while chunk c hashes and
+ * verifies.  With opts->device == -1 the signatures are sliced over the slots
+ * as for sv_ed25519_verify_batch; each slot hashes the bodies its slice
+ * references (a body whose signatures straddle a boundary on both slots). */
+#define SV_TXBODY_V1 0
+#define SV_TXBODY_V0 1
+#define SV_TXBODY_FEE_BUMP 2
+int sv_ed25519_verify_txbodies(const uint8_t* network_id /* 32 B */, const uint8_t* bodies, const uint64_t* body_off,
+                               const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                               const uint64_t* sig_begin, const uint8_t* pk, const uint8_t* sig, size_t n,
+                               uint8_t* verdict, uint8_t* digests /* optional, n_bodies x 32 */,
+                               const sv_opts* opts);
+/* Device-resident form (stream semantics, d_bitmap and the 16-byte alignment
+ * of d_pk / d_sig as sv_ed25519_verify_device; d_digests, optional, 16-byte
+ * aligned).  network_id is host memory.  Bodies may start at any alignment
+ * (16-byte aligned starts take the kernel's fast loads).  The device arrays
+ * are not validated: kinds > 2 hash as fee bumps and signature ranges are
+ * clamped to n.  The message array lives in the slot's workspace. */
+int sv_ed25519_verify_txbodies_device(int device, const uint8_t* network_id /* host, 32 B */, const void* d_bodies,
+                                      const uint64_t* d_body_off, const uint32_t* d_body_len,
+                                      const uint8_t* d_body_kind, size_t n_bodies, const uint64_t* d_sig_begin,
+                                      const void* d_pk, const void* d_sig, size_t n, void* d_verdict, void* d_bitmap,
+                                      void* d_digests, void* stream);
+/* The same computation on the engine's CPU path (what a caller runs when one
+ * of the two above returns an error; threads as sv_ed25519_verify_batch_cpu). */
+int sv_ed25519_verify_txbodies_cpu(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                   const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                   const uint64_t* sig_begin, const uint8_t* pk, const uint8_t* sig, size_t n,
+                                   uint8_t* verdict, uint8_t* digests /* optional */, int threads);
+
 /* ---- Warm-key latency path (csrc/comb.h, csrc/sv_comb.hip) ---------------
  * Each device slot keeps a bounded cache of per-public-key tables
  * ({0..8} * 16^j * (-A), 108 KiB per key) in HBM.  A latency-path host batch

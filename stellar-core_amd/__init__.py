@@ -67,7 +67,11 @@ EXPORTED_SYMBOLS = (
     "sv_set_device_map", "sv_set_min_shard", "sv_set_debug_flags", "sv_workspace_bytes", "sv_pinned_bytes",
     "sv_set_key_cache", "sv_key_cache_wait", "sv_key_cache_get_stats", "sv_set_key_tables",
     "sv_ed25519_verify_batch_gather_progress", "sv_host_feed_probe",
+    "sv_ed25519_verify_txbodies", "sv_ed25519_verify_txbodies_device", "sv_ed25519_verify_txbodies_cpu",
 )
+
+# body kinds of the tx-body entry points (include/stellar_sigverify.h)
+TXBODY_V1, TXBODY_V0, TXBODY_FEE_BUMP = 0, 1, 2
 
 # test knobs (include/stellar_sigverify.h sv_set_debug_flags)
 DBG_TRIVIAL_PAIR, DBG_MAX_WINDOWS, DBG_FAIL, DBG_PREP_ONLY, DBG_KEY_COLLIDE = 0x1, 0x2, 0x4, 0x8, 0x10
@@ -156,6 +160,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.sv_lat_last_trace.argtypes = [ctypes.POINTER(ctypes.c_double)]
     lib.sv_host_feed_probe.argtypes = [vp, vp, vp, ctypes.c_uint32, sz, ctypes.c_uint32, ctypes.c_int,
                                        ctypes.POINTER(FeedStats)]
+    lib.sv_ed25519_verify_txbodies.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp]
+    lib.sv_ed25519_verify_txbodies_device.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp, vp,
+                                                      vp, vp]
+    lib.sv_ed25519_verify_txbodies_cpu.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp, vp, ctypes.c_int]
     _lib = lib
     return lib
 
@@ -327,6 +335,69 @@ def verify_batch_cpu(pk, sig, msg, msg_off, msg_len, threads: int = 0) -> np.nda
     _check(lib.sv_ed25519_verify_batch_cpu(_ptr(pk), _ptr(sig), _ptr(msg), _ptr(off), _ptr(ln), n, _ptr(out),
                                            int(threads)))
     return out
+
+
+def _txbodies_args(network_id, bodies, body_off, body_len, body_kind, sig_begin, pk, sig):
+    nid = np.ascontiguousarray(np.frombuffer(bytes(network_id), np.uint8))
+    if nid.size != 32:
+        raise ValueError("network_id must be 32 bytes")
+    pk, sig = _u8(pk, 32), _u8(sig, 64)
+    n = pk.shape[0]
+    if sig.shape[0] != n:
+        raise ValueError("pk/sig row mismatch")
+    kind = np.ascontiguousarray(np.asarray(body_kind, dtype=np.uint8).reshape(-1))
+    nb = kind.shape[0]
+    bodies, off, ln = _var_msgs(bodies, body_off, body_len, nb)
+    sb = np.ascontiguousarray(np.asarray(sig_begin, dtype=np.uint64).reshape(-1))
+    if sb.shape[0] != nb + 1:
+        raise ValueError("sig_begin must hold n_bodies + 1 entries")
+    return nid, bodies, off, ln, kind, nb, sb, pk, sig, n
+
+
+def verify_txbodies(network_id, bodies, body_off, body_len, body_kind, sig_begin, pk, sig, device: int = -1,
+                    max_devices: int = 0, path=None):
+    """Signatures straight from transaction bodies (sv_ed25519_verify_txbodies):
+    body t = bodies[body_off[t]:body_off[t]+body_len[t]] of kind body_kind[t]
+    (TXBODY_V1 / TXBODY_V0 / TXBODY_FEE_BUMP) owns signatures
+    sig_begin[t]..sig_begin[t+1]-1.  The GPU hashes the bodies and verifies the
+    signatures over the digests in one pass.  Returns (verdict, digests)."""
+    lib = load_library()
+    nid, bodies, off, ln, kind, nb, sb, pk, sig, n = _txbodies_args(network_id, bodies, body_off, body_len, body_kind,
+                                                                   sig_begin, pk, sig)
+    out = np.zeros(n, np.uint8)
+    dig = np.zeros((nb, 32), np.uint8)
+    _check(lib.sv_ed25519_verify_txbodies(_ptr(nid), _ptr(bodies), _ptr(off), _ptr(ln), _ptr(kind), nb, _ptr(sb),
+                                          _ptr(pk), _ptr(sig), n, _ptr(out), _ptr(dig),
+                                          _opts(device, max_devices, path)))
+    return out, dig
+
+
+def verify_txbodies_cpu(network_id, bodies, body_off, body_len, body_kind, sig_begin, pk, sig, threads: int = 0):
+    """The same on the engine's CPU path (what a caller runs on an engine error)."""
+    lib = load_library()
+    nid, bodies, off, ln, kind, nb, sb, pk, sig, n = _txbodies_args(network_id, bodies, body_off, body_len, body_kind,
+                                                                   sig_begin, pk, sig)
+    out = np.zeros(n, np.uint8)
+    dig = np.zeros((nb, 32), np.uint8)
+    _check(lib.sv_ed25519_verify_txbodies_cpu(_ptr(nid), _ptr(bodies), _ptr(off), _ptr(ln), _ptr(kind), nb, _ptr(sb),
+                                              _ptr(pk), _ptr(sig), n, _ptr(out), _ptr(dig), int(threads)))
+    return out, dig
+
+
+def verify_txbodies_device(device: int, network_id, d_bodies: int, d_body_off: int, d_body_len: int, d_body_kind: int,
+                           n_bodies: int, d_sig_begin: int, d_pk: int, d_sig: int, n: int, d_verdict: int,
+                           d_bitmap: int = 0, d_digests: int = 0, stream: int = 0) -> None:
+    """Device-resident form (raw device pointers; network_id is 32 host bytes).
+    The verdicts and digests land in d_verdict (n) / d_digests (n_bodies x 32)."""
+    lib = load_library()
+    nid = np.ascontiguousarray(np.frombuffer(bytes(network_id), np.uint8))
+    if nid.size != 32:
+        raise ValueError("network_id must be 32 bytes")
+    _check(lib.sv_ed25519_verify_txbodies_device(device, _ptr(nid), d_bodies or None, d_body_off or None,
+                                                 d_body_len or None, d_body_kind or None, n_bodies,
+                                                 d_sig_begin or None, d_pk or None, d_sig or None, n,
+                                                 d_verdict or None, d_bitmap or None, d_digests or None,
+                                                 stream or None))
 
 
 def verify_gather(items, keys: bool = False, device: int = -1, max_devices: int = 0):

@@ -16,6 +16,7 @@
 #include <exception>
 #include <mutex>
 #include <random>
+#include <stdexcept>
 #include <string>
 #include <thread>
 
@@ -1008,6 +1009,30 @@ void verifyBatchUncached(const uint8_t* pk, const uint8_t* sig, const uint8_t* m
   }
   ++gFallbacks;
   timedBatch(false, n, [&] { return sv_ed25519_verify_batch_cpu(pk, sig, msg, off, len, n, verdict, 0); });
+  gCpuSigs += n;
+}
+
+void verifyTxBodiesUncached(const uint8_t* networkID, const uint8_t* bodies, const uint64_t* bodyOff,
+                            const uint32_t* bodyLen, const uint8_t* bodyKind, size_t nBodies,
+                            const uint64_t* sigBegin, const uint8_t* pk, const uint8_t* sig, size_t n,
+                            uint8_t* verdict, uint8_t* digests) {
+  if (nBodies == 0) return;
+  const size_t work = std::max<size_t>(n, 1);  // (a digests-only call still counts as a batch)
+  int rc = timedBatch(true, work, [&] {
+    return sv_ed25519_verify_txbodies(networkID, bodies, bodyOff, bodyLen, bodyKind, nBodies, sigBegin, pk, sig, n,
+                                      verdict, digests, nullptr);
+  });
+  if (rc == SV_OK) {
+    gGpuSigs += n;
+    gGpuBatches += 1;
+    return;
+  }
+  ++gFallbacks;
+  rc = timedBatch(false, work, [&] {
+    return sv_ed25519_verify_txbodies_cpu(networkID, bodies, bodyOff, bodyLen, bodyKind, nBodies, sigBegin, pk, sig, n,
+                                          verdict, digests, 0);
+  });
+  if (rc != SV_OK) throw std::invalid_argument("verifyTxBodiesUncached: malformed batch");
   gCpuSigs += n;
 }
 

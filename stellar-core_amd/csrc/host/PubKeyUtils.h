@@ -148,6 +148,17 @@ std::vector<bool> verifySigBatch(std::vector<VerifyItem> const& items, std::vect
 void verifyBatchUncached(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, const uint64_t* off,
                          const uint32_t* len, size_t n, uint8_t* verdict);
 
+// Engine-only batch straight from transaction bodies (sv_ed25519_verify_txbodies,
+// include/stellar_sigverify.h: same arguments): the engine hashes body t with
+// its kind's prefix, returns the digests and verifies signatures sigBegin[t] ..
+// sigBegin[t+1]-1 over digest t.  Always one engine call; an engine error
+// re-runs it on sv_ed25519_verify_txbodies_cpu and counts a fallback.  Throws
+// std::invalid_argument if both refuse the arguments.
+void verifyTxBodiesUncached(const uint8_t* networkID, const uint8_t* bodies, const uint64_t* bodyOff,
+                            const uint32_t* bodyLen, const uint8_t* bodyKind, size_t nBodies,
+                            const uint64_t* sigBegin, const uint8_t* pk, const uint8_t* sig, size_t n,
+                            uint8_t* verdict, uint8_t* digests);
+
 void clearVerifySigCache();
 void maybeSeedVerifySigCache(unsigned int seed);
 void flushVerifySigCacheCounts(uint64_t& hits, uint64_t& misses);

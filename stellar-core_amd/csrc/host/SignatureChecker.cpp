@@ -195,11 +195,11 @@ void forEachPair(TxSigners& ts, std::vector<DecoratedSignature> const& signature
 }
 }  // namespace
 
-void SignatureBatchPrefetch::enumerate(Storage& st, Hash const& contentsHash,
-                                       std::vector<DecoratedSignature> const& signatures,
-                                       std::vector<Signer> const& signers) {
+uint64_t SignatureBatchPrefetch::enumerate(Storage& st, Hash const& contentsHash,
+                                           std::vector<DecoratedSignature> const& signatures,
+                                           std::vector<Signer> const& signers) {
   TxSigners ts(signers);
-  if (ts.eds.empty()) return;
+  if (ts.eds.empty()) return ~0ull;
   auto pushMsg = [&](const uint8_t* msg, size_t msgLen) {
     const uint64_t off = st.msg.size();
     st.msg.resize(off + msgLen);
@@ -231,11 +231,79 @@ void SignatureBatchPrefetch::enumerate(Storage& st, Hash const& contentsHash,
     st.off.push_back(mo);
     st.len.push_back((uint32_t)ml);
   });
+  return hashOff;
 }
 
 void SignatureBatchPrefetch::add(Hash const& contentsHash, std::vector<DecoratedSignature> const& signatures,
                                  std::vector<Signer> const& signers) {
   enumerate(st_, contentsHash, signatures, signers);
+}
+
+void SignatureBatchPrefetch::add(TxBody const& body, std::vector<DecoratedSignature> const& signatures,
+                                 std::vector<Signer> const& signers) {
+  static const Hash kUnknown{};  // (the bytes are patched in runBodies)
+  BodyEntry e;
+  e.body = body;
+  e.pair0 = len_.size();
+  e.hashOff = enumerate(st_, kUnknown, signatures, signers);
+  e.pair1 = len_.size();
+  bodies_.push_back(e);
+}
+
+void SignatureBatchPrefetch::runBodies(const uint8_t* networkID, const uint8_t* blob) {
+  const size_t n = len_.size(), nb = bodies_.size();
+  verdict_.assign(n, 0);
+  if (nb == 0) return;
+  // the engine's batch: bodies in add() order, their ed25519 pairs (the ones
+  // whose message is the body's hash) gathered next to each other; every
+  // other pair is a signed-payload pair
+  std::vector<uint64_t> off(nb), sigBegin(nb + 1, 0);
+  std::vector<uint32_t> len(nb);
+  std::vector<uint8_t> kind(nb), digests(32 * nb);
+  std::vector<uint32_t> edPair, payPair;
+  for (size_t b = 0; b < nb; ++b) {
+    BodyEntry const& e = bodies_[b];
+    off[b] = e.body.off;
+    len[b] = e.body.len;
+    kind[b] = e.body.kind;
+    for (size_t i = e.pair0; i < e.pair1; ++i) {
+      // (an empty payload stored just before the hash shares its offset: the length tells them apart)
+      if (e.hashOff != ~0ull && off_[i] == e.hashOff && len_[i] == 32) edPair.push_back((uint32_t)i);
+      else payPair.push_back((uint32_t)i);
+    }
+    sigBegin[b + 1] = edPair.size();
+  }
+  const size_t ne = edPair.size();
+  std::vector<uint8_t> pk(32 * std::max<size_t>(ne, 1)), sig(64 * std::max<size_t>(ne, 1)), v(std::max<size_t>(ne, 1));
+  for (size_t k = 0; k < ne; ++k) {
+    std::memcpy(&pk[32 * k], &pk_[32 * (size_t)edPair[k]], 32);
+    std::memcpy(&sig[64 * k], &sig_[64 * (size_t)edPair[k]], 64);
+  }
+  PubKeyUtils::verifyTxBodiesUncached(networkID, blob, off.data(), len.data(), kind.data(), nb, sigBegin.data(),
+                                      pk.data(), sig.data(), ne, v.data(), digests.data());
+  for (size_t b = 0; b < nb; ++b) {
+    BodyEntry const& e = bodies_[b];
+    if (e.body.hashOut) std::memcpy(e.body.hashOut->data(), &digests[32 * b], 32);
+    if (e.hashOff != ~0ull) std::memcpy(&msg_[e.hashOff], &digests[32 * b], 32);
+  }
+  for (size_t k = 0; k < ne; ++k) verdict_[edPair[k]] = v[k];
+  if (const size_t np = payPair.size()) {
+    std::vector<uint8_t> ppk(32 * np), psig(64 * np), pv(np);
+    std::vector<uint64_t> poff(np);
+    std::vector<uint32_t> plen(np);
+    for (size_t k = 0; k < np; ++k) {
+      const size_t i = payPair[k];
+      std::memcpy(&ppk[32 * k], &pk_[32 * i], 32);
+      std::memcpy(&psig[64 * k], &sig_[64 * i], 64);
+      poff[k] = off_[i];
+      plen[k] = len_[i];
+    }
+    static const uint8_t dummy = 0;
+    PubKeyUtils::verifyBatchUncached(ppk.data(), psig.data(), msg_.empty() ? &dummy : msg_.data(), poff.data(),
+                                     plen.data(), np, pv.data());
+    for (size_t k = 0; k < np; ++k) verdict_[payPair[k]] = pv[k];
+  }
+  buildTable();  // (after the hashes are in place: the table hashes the message bytes)
 }
 
 void SignatureBatchPrefetch::addBatch(std::vector<TxRef> const& txs, std::function<void(size_t)> const& prepare) {

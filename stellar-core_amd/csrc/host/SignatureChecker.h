@@ -104,6 +104,25 @@ class SignatureBatchPrefetch {
   // the global verify cache (a later verifySig then hits).  An engine error
   // re-runs the batch on the CPU path.
   void run(bool seedCache = false);
+  // Body form (catchup replay: every frame is fresh, so nobody has hashed it
+  // yet).  add(TxBody, ...) enumerates a transaction's pairs without knowing
+  // its contents hash: the hash is that of the body, prefix || bytes with the
+  // kind's prefix (include/stellar_sigverify.h SV_TXBODY_*), off / len a range
+  // of the blob given to runBodies.  runBodies sends every ed25519 pair and
+  // every body to the engine in one sv_ed25519_verify_txbodies call, stores the
+  // digests that come back through hashOut and into the pairs' message bytes,
+  // verifies the signed-payload pairs (which carry their own message) as a
+  // second, normally empty, batch, and builds the side table: lookups then work
+  // as after run(false).  A prefetch takes either form, not both.
+  struct TxBody {
+    uint64_t off;
+    uint32_t len;
+    uint8_t kind;
+    Hash* hashOut;
+  };
+  void add(TxBody const& body, std::vector<DecoratedSignature> const& signatures,
+           std::vector<Signer> const& signers);
+  void runBodies(const uint8_t* networkID, const uint8_t* blob);
   // verdict for (pk, sig, msg) if prefetched (tx: see addBatch)
   static constexpr size_t kNoTx = ~size_t(0);
   bool lookup(uint256 const& pk, Signature const& sig, ByteSlice const& msg, bool& verdict,
@@ -145,8 +164,15 @@ class SignatureBatchPrefetch {
     std::vector<uint32_t> txBegin;  // addBatch: first pair of batch tx k (k + 1 entries)
     void clear();
   };
-  static void enumerate(Storage& st, Hash const& contentsHash, std::vector<DecoratedSignature> const& signatures,
-                        std::vector<Signer> const& signers);
+  // returns where the contents hash was stored in st.msg (~0: no ed25519 pair)
+  static uint64_t enumerate(Storage& st, Hash const& contentsHash, std::vector<DecoratedSignature> const& signatures,
+                            std::vector<Signer> const& signers);
+  struct BodyEntry {
+    TxBody body;
+    size_t pair0, pair1;  // the pairs enumerated for it
+    uint64_t hashOff;     // its contents hash in msg_ (~0: none)
+  };
+  std::vector<BodyEntry> bodies_;
   static std::vector<Storage>& spares();
   static constexpr size_t kSpares = 4;
   Storage st_;

@@ -129,7 +129,8 @@ TxSigResult checkFeeBumpSignatures(FeeBumpSigInfo const& tx, AccountSnapshot con
   return r;
 }
 
-void prefetchTransaction(SignatureBatchPrefetch& pre, TransactionSigInfo const& tx, AccountSnapshot const& accounts) {
+void prefetchTransaction(SignatureBatchPrefetch& pre, TransactionSigInfo const& tx, AccountSnapshot const& accounts,
+                         SignatureBatchPrefetch::TxBody const* body) {
   std::vector<Signer> all;
   auto addAccount = [&](uint256 const& id, bool noAccountKey) {
     if (AccountSigState const* a = find(accounts, id)) {
@@ -155,12 +156,17 @@ void prefetchTransaction(SignatureBatchPrefetch& pre, TransactionSigInfo const& 
       }
     if (!dup) uniq.push_back(s);
   }
-  pre.add(tx.contentsHash, tx.signatures, uniq);
+  if (body) pre.add(*body, tx.signatures, uniq);
+  else pre.add(tx.contentsHash, tx.signatures, uniq);
 }
 
-void prefetchFeeBump(SignatureBatchPrefetch& pre, FeeBumpSigInfo const& tx, AccountSnapshot const& accounts) {
-  if (AccountSigState const* a = find(accounts, tx.feeSource)) pre.add(tx.contentsHash, tx.signatures, accountSigners(*a));
-  prefetchTransaction(pre, tx.inner, accounts);
+void prefetchFeeBump(SignatureBatchPrefetch& pre, FeeBumpSigInfo const& tx, AccountSnapshot const& accounts,
+                     SignatureBatchPrefetch::TxBody const* outerBody, SignatureBatchPrefetch::TxBody const* innerBody) {
+  // (body form: the outer body is added even without a fee-source account, so its hash is still computed)
+  AccountSigState const* a = find(accounts, tx.feeSource);
+  if (outerBody) pre.add(*outerBody, tx.signatures, a ? accountSigners(*a) : std::vector<Signer>());
+  else if (a) pre.add(tx.contentsHash, tx.signatures, accountSigners(*a));
+  prefetchTransaction(pre, tx.inner, accounts, innerBody);
 }
 
 }  // namespace stellar

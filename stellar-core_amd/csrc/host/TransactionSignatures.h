@@ -111,9 +111,13 @@ TxSigResult checkTransactionSignatures(TransactionSigInfo const& tx, AccountSnap
 TxSigResult checkFeeBumpSignatures(FeeBumpSigInfo const& tx, AccountSnapshot const& accounts, uint32_t protocol,
                                    SignatureBatchPrefetch const* prefetched = nullptr, bool forApply = false);
 
-// Adds every (signature, signer) pair the checks of `tx` can reach.
-void prefetchTransaction(SignatureBatchPrefetch& pre, TransactionSigInfo const& tx,
-                         AccountSnapshot const& accounts);
-void prefetchFeeBump(SignatureBatchPrefetch& pre, FeeBumpSigInfo const& tx, AccountSnapshot const& accounts);
+// Adds every (signature, signer) pair the checks of `tx` can reach.  With a
+// body (SignatureBatchPrefetch's body form) the contents hash is not read: it
+// is the hash of that body, delivered by runBodies.
+void prefetchTransaction(SignatureBatchPrefetch& pre, TransactionSigInfo const& tx, AccountSnapshot const& accounts,
+                         SignatureBatchPrefetch::TxBody const* body = nullptr);
+void prefetchFeeBump(SignatureBatchPrefetch& pre, FeeBumpSigInfo const& tx, AccountSnapshot const& accounts,
+                     SignatureBatchPrefetch::TxBody const* outerBody = nullptr,
+                     SignatureBatchPrefetch::TxBody const* innerBody = nullptr);
 
 }  // namespace stellar

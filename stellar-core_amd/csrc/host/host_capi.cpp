@@ -445,11 +445,49 @@ int svh_check_txset(const svh_tx* txs, size_t ntx, const svh_decorated_sig* sigs
 
 void svh_txset_last_phases(double out[4]) { std::memcpy(out, t_txset_phases, sizeof t_txset_phases); }
 
-int svh_check_envelopes(const svh_envelope* env, size_t n, const svh_decorated_sig* sigs, const svh_op* ops,
-                        const svh_signer* signers, const svh_account* accounts, size_t naccounts,
-                        uint32_t protocol, int prefetch, int for_apply, svh_tx_result* results,
-                        uint64_t* prefetched_pairs) {
+}  // extern "C"
+
+namespace {
+// The body form's extra arguments (svh_check_envelopes_bodies); null for
+// svh_check_envelopes, which reads the hashes from the envelopes.
+struct EnvelopeBodies {
+  const uint8_t* networkID;
+  const uint8_t* blob;
+  const svh_envelope_body* body;
+  uint8_t* contentsHashOut;
+  uint8_t* feeBumpHashOut;
+};
+
+// sha256(prefix(kind) || body) with the mirror's own SHA-256 (the reference's
+// per-frame getContentsHash)
+Hash hostContentsHash(const uint8_t* networkID, uint32_t kind, const uint8_t* body, size_t len) {
+  std::vector<uint8_t> m(networkID, networkID + 32);
+  const uint8_t type[4] = {0, 0, 0, (uint8_t)(kind == 2 ? 5 : 2)};
+  m.insert(m.end(), type, type + 4);
+  if (kind == 1) m.insert(m.end(), 4, (uint8_t)0);
+  if (len) m.insert(m.end(), body, body + len);
+  const auto h = hostcrypto::sha256(m.data(), m.size());
+  Hash out;
+  std::memcpy(out.data(), h.data(), 32);
+  return out;
+}
+
+int checkEnvelopes(const svh_envelope* env, size_t n, const svh_decorated_sig* sigs, const svh_op* ops,
+                   const svh_signer* signers, const svh_account* accounts, size_t naccounts, uint32_t protocol,
+                   int prefetch, int for_apply, svh_tx_result* results, uint64_t* prefetched_pairs,
+                   const EnvelopeBodies* eb) {
   try {
+    if (eb) {
+      if (prefetch != 0 && prefetch != 1)
+        throw std::invalid_argument("svh_check_envelopes_bodies: prefetch must be 0 or 1 (no keyed, cache-seeding form)");
+      if (!eb->networkID || !eb->contentsHashOut || !eb->feeBumpHashOut || (n && !eb->body))
+        throw std::invalid_argument("svh_check_envelopes_bodies: null argument");
+      for (size_t t = 0; t < n; ++t) {
+        if (eb->body[t].kind > 1) throw std::invalid_argument("inner body kind must be 0 (V1) or 1 (V0)");
+        if (!eb->blob && (eb->body[t].len || (env[t].fee_bump && eb->body[t].outer_len)))
+          throw std::invalid_argument("svh_check_envelopes_bodies: null body blob");
+      }
+    }
     AccountSnapshot snap;
     snap.reserve(naccounts);
     for (size_t a = 0; a < naccounts; ++a) {
@@ -464,7 +502,11 @@ int svh_check_envelopes(const svh_envelope* env, size_t n, const svh_decorated_s
     for (size_t t = 0; t < n; ++t) {
       svh_envelope const& e = env[t];
       TransactionSigInfo& in = txs[t].inner;
-      std::memcpy(in.contentsHash.data(), e.contents_hash, 32);
+      // (body form: the bytes of a null blob are never read, every length is 0 then)
+      auto at = [&](uint64_t off) { return eb->blob ? eb->blob + off : nullptr; };
+      if (!eb) std::memcpy(in.contentsHash.data(), e.contents_hash, 32);
+      else if (!prefetch)
+        in.contentsHash = hostContentsHash(eb->networkID, eb->body[t].kind, at(eb->body[t].off), eb->body[t].len);
       in.sourceAccount = u256(e.source);
       in.signatures = sigRange(sigs, e.sig_off, e.nsigs);
       for (uint32_t k = 0; k < e.nops; ++k) {
@@ -477,19 +519,37 @@ int svh_check_envelopes(const svh_envelope* env, size_t n, const svh_decorated_s
       }
       for (uint32_t k = 0; k < e.nextra; ++k) in.extraSigners.push_back(signer(signers[e.extra_off + k]).key);
       if (e.fee_bump) {
-        std::memcpy(txs[t].contentsHash.data(), e.fee_bump_hash, 32);
+        if (!eb) std::memcpy(txs[t].contentsHash.data(), e.fee_bump_hash, 32);
+        else if (!prefetch)
+          txs[t].contentsHash = hostContentsHash(eb->networkID, 2, at(eb->body[t].outer_off), eb->body[t].outer_len);
         txs[t].feeSource = u256(e.fee_source);
         txs[t].signatures = sigRange(sigs, e.outer_off, e.nouter);
       }
     }
     SignatureBatchPrefetch pre;
-    if (prefetch) {
+    if (prefetch && eb) {
+      // the catchup form: pairs enumerated without the hashes, one engine call
+      // from the bodies to the verdicts, the digests taken as the hashes
+      for (size_t t = 0; t < n; ++t) {
+        svh_envelope_body const& b = eb->body[t];
+        const SignatureBatchPrefetch::TxBody inner{b.off, b.len, (uint8_t)b.kind, &txs[t].inner.contentsHash};
+        const SignatureBatchPrefetch::TxBody outer{b.outer_off, b.outer_len, 2, &txs[t].contentsHash};
+        if (env[t].fee_bump) prefetchFeeBump(pre, txs[t], snap, &outer, &inner);
+        else prefetchTransaction(pre, txs[t].inner, snap, &inner);
+      }
+      pre.runBodies(eb->networkID, eb->blob);
+    } else if (prefetch) {
       for (size_t t = 0; t < n; ++t) {
         if (env[t].fee_bump) prefetchFeeBump(pre, txs[t], snap);
         else prefetchTransaction(pre, txs[t].inner, snap);
       }
       pre.run(prefetch == 2);
     }
+    if (eb)
+      for (size_t t = 0; t < n; ++t) {
+        std::memcpy(eb->contentsHashOut + 32 * t, txs[t].inner.contentsHash.data(), 32);
+        std::memcpy(eb->feeBumpHashOut + 32 * t, txs[t].contentsHash.data(), 32);  // (zeros without a fee bump)
+      }
     if (prefetched_pairs) *prefetched_pairs = pre.pairs();
     SignatureBatchPrefetch const* p = prefetch ? &pre : nullptr;
     auto check = [&](size_t a, size_t b) {
@@ -510,6 +570,28 @@ int svh_check_envelopes(const svh_envelope* env, size_t n, const svh_decorated_s
   } catch (std::exception const& e) {
     return guard_exc(e);
   }
+}
+}  // namespace
+
+extern "C" {
+
+int svh_check_envelopes(const svh_envelope* env, size_t n, const svh_decorated_sig* sigs, const svh_op* ops,
+                        const svh_signer* signers, const svh_account* accounts, size_t naccounts,
+                        uint32_t protocol, int prefetch, int for_apply, svh_tx_result* results,
+                        uint64_t* prefetched_pairs) {
+  return checkEnvelopes(env, n, sigs, ops, signers, accounts, naccounts, protocol, prefetch, for_apply, results,
+                        prefetched_pairs, nullptr);
+}
+
+int svh_check_envelopes_bodies(const svh_envelope* env, size_t n, const svh_decorated_sig* sigs, const svh_op* ops,
+                               const svh_signer* signers, const svh_account* accounts, size_t naccounts,
+                               uint32_t protocol, int prefetch, int for_apply, svh_tx_result* results,
+                               uint64_t* prefetched_pairs, const uint8_t* network_id, const uint8_t* bodies,
+                               const svh_envelope_body* body, uint8_t* contents_hash_out,
+                               uint8_t* fee_bump_hash_out) {
+  const EnvelopeBodies eb{network_id, bodies, body, contents_hash_out, fee_bump_hash_out};
+  return checkEnvelopes(env, n, sigs, ops, signers, accounts, naccounts, protocol, prefetch, for_apply, results,
+                        prefetched_pairs, &eb);
 }
 
 int svh_mb_run_ex(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off,

@@ -80,6 +80,12 @@ hipError_t sv_launch_hash(int kind, unsigned max_blocks, const void* pk, const v
                           const uint64_t* off, const uint32_t* len, uint32_t fixed_len, uint64_t n, void* out,
                           hipStream_t s);
 // warm-key latency path (sv_comb.hip)
+hipError_t sv_launch_txhash(unsigned max_blocks, const uint8_t* nid, const void* bodies, const uint64_t* off,
+                            const uint32_t* len, const uint8_t* kind, uint64_t n_bodies, const uint64_t* sig_begin,
+                            uint64_t n, void* msg, void* digests, hipStream_t s);
+int sv_txbodies_check(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                      const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies, const uint64_t* sig_begin,
+                      const uint8_t* pk, const uint8_t* sig, size_t n, const uint8_t* verdict);
 size_t sv_comb_btab_bytes(void);
 size_t sv_key_slot_bytes(void);
 hipError_t sv_launch_comb_btab(uint32_t* d_ctab, hipStream_t s);
@@ -353,6 +359,7 @@ struct Device {
   HostBuf z_out;  // mapped: its verdicts, written in place (bulk_zc_out)
   DevBuf msg, off, len, keys;  // sha256 batches
   HostBuf h_sha;
+  DevBuf txmsg;  // tx-body batches: the n x 32 message array the hash kernel fills (grown after draining `stream`)
   // timing
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
   std::vector<uint64_t> pending_n;
@@ -501,6 +508,7 @@ void release_device(Device& D) {
     s.up = s.done = s.down = s.keys_down = nullptr;
   }
   D.msg.release(); D.off.release(); D.len.release(); D.keys.release(); D.h_sha.release();
+  D.txmsg.release();
   D.ws.release();
   D.kt.index.release(); D.kt.store.release(); D.kt.kslot.release(); D.kt.builders.release();
   D.kt.count.release(); D.kt.h_count.release();
@@ -2129,6 +2137,223 @@ int verify_host(const HostIn& in, size_t n, uint8_t* verdict, uint8_t* keys, con
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
+// ------------------------------------------------------------ tx bodies
+// sv_ed25519_verify_txbodies: a batch of bodies and their signatures (CSR).
+struct TxIn {
+  const uint8_t* nid;
+  const uint8_t* bodies;
+  const uint64_t* off;
+  const uint32_t* len;
+  const uint8_t* kind;
+  size_t nb;
+  const uint64_t* sb;
+  const uint8_t* pk;
+  const uint8_t* sig;
+};
+
+// Body bytes per staging chunk (SV_TXBODY_CHUNK_BYTES, default 64 MiB).
+size_t txbody_chunk_bytes() {
+  static const size_t b = std::max<size_t>(4096, env_size("SV_TXBODY_CHUNK_BYTES", (size_t)64 << 20));
+  return b;
+}
+inline size_t al16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// One staging chunk: bodies [b0, b1) and the signatures [s0, s1) of the slice
+// they own.  Pinned / device image:
+//   pk (32 m) | sig (64 m) | body_off (8 k) | sig_begin (8 (k + 1)) | body_len (4 k) | kind (k) | bodies
+// with every body 16-byte aligned (offsets relative to the body section) and
+// sig_begin relative to s0.
+struct TxChunk {
+  size_t b0, b1, s0, s1;
+  size_t body_bytes;  // the aligned body section
+  size_t o_sig, o_off, o_sb, o_len, o_kind, o_body, bytes;
+};
+
+// The chunks of a slice: bodies [B0, B1), signatures [lo, hi) (a body's range
+// clipped to the slice).  A chunk is a run of whole bodies of at most max_s
+// signatures and max_b body bytes; a body over either bound is a chunk alone.
+std::vector<TxChunk> tx_plan(const TxIn& in, size_t B0, size_t B1, size_t lo, size_t hi, size_t max_s, size_t max_b) {
+  auto cb = [&](size_t t) { return (size_t)std::min<uint64_t>(std::max<uint64_t>(in.sb[t], lo), hi); };
+  std::vector<TxChunk> out;
+  size_t t = B0;
+  while (t < B1) {
+    TxChunk c{};
+    c.b0 = t;
+    c.s0 = cb(t);
+    size_t bytes = 0;
+    do {
+      bytes += al16(in.len[t]);
+      ++t;
+    } while (t < B1 && cb(t + 1) - c.s0 <= max_s && bytes + al16(in.len[t]) <= max_b);
+    c.b1 = t;
+    c.s1 = cb(t);
+    c.body_bytes = bytes;
+    const size_t m = c.s1 - c.s0, k = c.b1 - c.b0;
+    c.o_sig = 32 * m;
+    c.o_off = 96 * m;
+    c.o_sb = c.o_off + 8 * k;
+    c.o_len = c.o_sb + 8 * (k + 1);
+    c.o_kind = c.o_len + 4 * k;
+    c.o_body = al16(c.o_kind + k);
+    c.bytes = c.o_body + std::max<size_t>(bytes, 16);
+    out.push_back(c);
+  }
+  return out;
+}
+
+void tx_pack(const TxIn& in, const TxChunk& c, size_t lo, size_t hi, uint8_t* h) {
+  const size_t m = c.s1 - c.s0, k = c.b1 - c.b0;
+  uint64_t* offs = (uint64_t*)(h + c.o_off);
+  uint64_t* sb = (uint64_t*)(h + c.o_sb);
+  size_t pos = 0;
+  for (size_t i = 0; i < k; ++i) {
+    offs[i] = pos;
+    pos += al16(in.len[c.b0 + i]);
+  }
+  for (size_t i = 0; i <= k; ++i)
+    sb[i] = std::min<uint64_t>(std::max<uint64_t>(in.sb[c.b0 + i], lo), hi) - c.s0;
+  std::memcpy(h + c.o_len, in.len + c.b0, 4 * k);
+  std::memcpy(h + c.o_kind, in.kind + c.b0, k);
+  sv::Pool& pp = pack_pool();
+  const size_t cap = t_pack_parts ? t_pack_parts : pp.size() + 1;
+  const size_t work = 96 * m + c.body_bytes;
+  const size_t parts = std::max<size_t>(1, std::min<size_t>(std::min(pp.size() + 1, cap), work / pack_part()));
+  const bool nt = pack_nt();
+  pp.run(parts, [&](size_t p) {
+    struct Fence {
+      bool nt;
+      ~Fence() {
+        if (nt) _mm_sfence();
+      }
+    } fence{nt};
+    auto cp = [nt](uint8_t* d, const uint8_t* s, size_t len) {
+      if (nt) nt_copy(d, s, len);
+      else std::memcpy(d, s, len);
+    };
+    const size_t a = m * p / parts, b = m * (p + 1) / parts;
+    if (b > a) {
+      cp(h + 32 * a, in.pk + 32 * (c.s0 + a), 32 * (b - a));
+      cp(h + c.o_sig + 64 * a, in.sig + 64 * (c.s0 + a), 64 * (b - a));
+    }
+    for (size_t i = k * p / parts; i < k * (p + 1) / parts; ++i) {
+      const uint32_t l = in.len[c.b0 + i];
+      if (l) cp(h + c.o_body + offs[i], in.bodies + in.off[c.b0 + i], l);
+    }
+  });
+}
+
+// A chunk's results in its pinned slot: verdicts (m), then digests (32 k).
+struct TxPending {
+  bool busy = false;
+  TxChunk c;
+};
+int tx_drain(Stage& s, TxPending& pd, size_t dig_from, uint8_t* verdict, uint8_t* digests) {
+  if (!pd.busy) return SV_OK;
+  SV_HIP(hipEventSynchronize(s.down));
+  pd.busy = false;
+  const TxChunk& c = pd.c;
+  const size_t m = c.s1 - c.s0;
+  const uint8_t* h = (const uint8_t*)s.h_out.p;
+  if (m) std::memcpy(verdict + c.s0, h, m);
+  if (digests) {
+    // (a body whose signatures straddle the slice's lower boundary was also
+    // hashed by the slot before: that slot delivers its digest)
+    const size_t from = std::max(c.b0, dig_from);
+    if (from < c.b1) std::memcpy(digests + 32 * from, h + m + 32 * (from - c.b0), 32 * (c.b1 - from));
+  }
+  if (stage_trace()) fprintf(stderr, "SV_STAGE_TRACE tx chunk [%zu, %zu) drained @%.1f\n", c.b0, c.b1, trace_abs_us());
+  return SV_OK;
+}
+
+// Bodies [B0, B1) and signatures [lo, hi) on one slot (caller holds D.mu,
+// device set): per chunk pack -> H2D -> hash kernel -> verify launch (mode 0
+// over the message array, same stream) -> D2H, over the slot's two staging
+// slots as host_slice_locked does, so chunk c + 1 is packed and copied up
+// while chunk c hashes and verifies.
+int tx_slice_locked(Device& D, const TxIn& in, size_t B0, size_t B1, size_t lo, size_t hi, size_t dig_from,
+                    uint8_t* verdict, uint8_t* digests, int path) {
+  int rc;
+  if (stage_trace()) fprintf(stderr, "SV_STAGE_TRACE tx slice @%.1f\n", trace_abs_us());
+  const std::vector<TxChunk> plan = tx_plan(in, B0, B1, lo, hi, stage_chunk(), txbody_chunk_bytes());
+  if (plan.empty()) return SV_OK;
+  if (stage_trace()) fprintf(stderr, "SV_STAGE_TRACE tx plan: %zu chunks @%.1f\n", plan.size(), trace_abs_us());
+  size_t max_m = 0;
+  for (const TxChunk& c : plan) max_m = std::max(max_m, c.s1 - c.s0);
+  // the message array and the largest launch's workspace first, so neither
+  // grows under a running kernel
+  if (32 * max_m > D.txmsg.cap) {
+    SV_HIP(hipStreamSynchronize(D.stream));
+    if ((rc = D.txmsg.ensure(32 * max_m))) return rc;
+  }
+  if (max_m) {
+    const int rp = resolve_path(path, max_m);
+    const size_t wb = std::max(sv_verify_ws_bytes(rp, grid_for(D, max_m), max_m),
+                               sv_verify_ws_bytes(launch_geometry(rp, max_m), grid_for(D, max_m), max_m));
+    if ((rc = ensure_ws(D, wb))) return rc;
+  }
+  const bool single = plan.size() == 1;
+  hipStream_t up_s = single ? D.stream : D.h2d, down_s = single ? D.stream : D.d2h;
+  TxPending pend[2];
+  for (size_t ci = 0; ci < plan.size(); ++ci) {
+    const TxChunk& c = plan[ci];
+    Stage& s = D.st[ci & 1];
+    if ((rc = tx_drain(s, pend[ci & 1], dig_from, verdict, digests))) return rc;
+    const size_t m = c.s1 - c.s0, k = c.b1 - c.b0;
+    if ((rc = s.h_in.ensure(c.bytes)) || (rc = s.d_in.ensure(c.bytes)) || (rc = s.h_out.ensure(m + 32 * k)) ||
+        (rc = s.d_verdict.ensure(std::max<size_t>(m, 1))) || (rc = s.d_keys.ensure(32 * k)))
+      return rc;
+    uint8_t* hp = (uint8_t*)s.h_in.p;
+    uint8_t* d = (uint8_t*)s.d_in.p;
+    if (stage_trace()) fprintf(stderr, "SV_STAGE_TRACE tx chunk %zu staging @%.1f\n", ci, trace_abs_us());
+    tx_pack(in, c, lo, hi, hp);
+    if (stage_trace())
+      fprintf(stderr, "SV_STAGE_TRACE tx chunk %zu packed (%zu B, %zu sigs) @%.1f\n", ci, c.bytes, m, trace_abs_us());
+    const size_t piece = share_now(D) ? share_upload_bytes() : c.bytes;
+    for (size_t o = 0; o < c.bytes; o += piece)
+      SV_HIP(hipMemcpyAsync(d + o, hp + o, std::min(piece, c.bytes - o), hipMemcpyHostToDevice, up_s));
+    if (!single) {
+      SV_HIP(hipEventRecord(s.up, D.h2d));
+      SV_HIP(hipStreamWaitEvent(D.stream, s.up, 0));
+    }
+    SV_HIP(sv_launch_txhash(D.grid * 8, in.nid, d + c.o_body, (const uint64_t*)(d + c.o_off),
+                            (const uint32_t*)(d + c.o_len), d + c.o_kind, k, (const uint64_t*)(d + c.o_sb), m,
+                            D.txmsg.p, s.d_keys.p, D.stream));
+    if (m && (rc = launch_locked(D, 0, path, d, d + c.o_sig, D.txmsg.p, nullptr, nullptr, 32, m, s.d_verdict.p,
+                                 nullptr, kt_mode() == 1)))
+      return rc;
+    if (!single) {
+      SV_HIP(hipEventRecord(s.done, D.stream));
+      SV_HIP(hipStreamWaitEvent(D.d2h, s.done, 0));
+    }
+    uint8_t* ho = (uint8_t*)s.h_out.p;
+    if (m) SV_HIP(hipMemcpyAsync(ho, s.d_verdict.p, m, hipMemcpyDeviceToHost, down_s));
+    if (digests) SV_HIP(hipMemcpyAsync(ho + m, s.d_keys.p, 32 * k, hipMemcpyDeviceToHost, down_s));
+    SV_HIP(hipEventRecord(s.down, down_s));
+    pend[ci & 1].busy = true;
+    pend[ci & 1].c = c;
+    if (stage_trace()) fprintf(stderr, "SV_STAGE_TRACE tx chunk %zu enqueued @%.1f\n", ci, trace_abs_us());
+  }
+  for (int i = 0; i < 2; ++i)
+    if ((rc = tx_drain(D.st[i], pend[i], dig_from, verdict, digests))) return rc;
+  return SV_OK;
+}
+
+int tx_slice(Device& D, const TxIn& in, size_t B0, size_t B1, size_t lo, size_t hi, size_t dig_from,
+             uint8_t* verdict, uint8_t* digests, int path) {
+  std::lock_guard<std::mutex> g(D.mu);
+  SV_HIP(hipSetDevice(D.phys));
+  int rc;
+  if ((rc = ready_locked(D))) return rc;
+  rc = tx_slice_locked(D, in, B0, B1, lo, hi, dig_from, verdict, digests, path);
+  if (rc != SV_OK) {
+    // leave the slot reusable: nothing of this call may still be in flight
+    (void)hipStreamSynchronize(D.h2d);
+    (void)hipStreamSynchronize(D.stream);
+    (void)hipStreamSynchronize(D.d2h);
+  }
+  return rc;
+}
+
 // Releases every slot (caller holds g_mu).  Lock order: lat.mu, then mu.
 void shutdown_locked() {
   for (Device* D : g_devs) {
@@ -2463,6 +2688,78 @@ int sv_sha256_device(int device, const void* d_data, const uint64_t* d_off, cons
   return hash_device(1, device, nullptr, nullptr, d_data, d_off, d_len, fixed_len, n, d_digests, stream);
 }
 
+int sv_ed25519_verify_txbodies(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                               const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                               const uint64_t* sig_begin, const uint8_t* pk, const uint8_t* sig, size_t n,
+                               uint8_t* verdict, uint8_t* digests, const sv_opts* opts) {
+  LifeGuard life_;
+  int rc = check_opts(opts);
+  if (rc) return rc;
+  if (sv_txbodies_check(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, pk, sig, n, verdict))
+    return fail(SV_ERR_INVALID_ARG, "tx bodies: null pointer, body kind > 2 or malformed sig_begin");
+  if (n_bodies == 0) return SV_OK;
+  if ((rc = debug_fail())) return rc;
+  if ((rc = ensure_init())) return rc;
+  std::vector<Device*> devs;
+  if ((rc = select_devices(opts, n, devs))) return rc;
+  const int path = path_from_flags(opts ? opts->flags : 0u);
+  const TxIn in{network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, pk, sig};
+  // bodies that end at or before signature x
+  auto ended = [&](size_t x) {
+    return (size_t)(std::upper_bound(sig_begin + 1, sig_begin + n_bodies + 1, (uint64_t)x) - (sig_begin + 1));
+  };
+  // The slice [lo, hi) of the signatures takes the bodies it references; a
+  // body that straddles hi is hashed here and by the next slot, which leaves
+  // its digest to this one.  Bodies without signatures go with the slice they
+  // end in (the first slice starts at body 0, the last ends at n_bodies).
+  return shard(devs, n, [&](Device& D, size_t lo, size_t hi) {
+    const bool first = lo == 0, last = hi == n;
+    const size_t B0 = first ? 0 : ended(lo);
+    size_t B1 = last ? n_bodies : ended(hi);
+    if (!last && B1 < n_bodies && sig_begin[B1] < hi) ++B1;
+    const size_t dig_from = B0 + (!first && B0 < n_bodies && sig_begin[B0] < lo ? 1 : 0);
+    return tx_slice(D, in, B0, B1, lo, hi, dig_from, verdict, digests, path);
+  });
+}
+
+int sv_ed25519_verify_txbodies_device(int device, const uint8_t* network_id, const void* d_bodies,
+                                      const uint64_t* d_body_off, const uint32_t* d_body_len,
+                                      const uint8_t* d_body_kind, size_t n_bodies, const uint64_t* d_sig_begin,
+                                      const void* d_pk, const void* d_sig, size_t n, void* d_verdict, void* d_bitmap,
+                                      void* d_digests, void* stream) {
+  LifeGuard life_;
+  if (!network_id || (n_bodies && (!d_bodies || !d_body_off || !d_body_len || !d_body_kind)) ||
+      (n && (n_bodies == 0 || !d_sig_begin || !d_pk || !d_sig || !d_verdict)))
+    return fail(SV_ERR_INVALID_ARG, "tx bodies: null pointer");
+  if (!aligned16(d_pk) || !aligned16(d_sig) || !aligned16(d_digests))
+    return fail(SV_ERR_ALIGN, "pk/sig/digests must be 16-byte aligned");
+  int rc;
+  if ((rc = debug_fail())) return rc;
+  if ((rc = ensure_init())) return rc;
+  Device* Dp = device_arg(device);
+  if (!Dp) return fail(SV_ERR_INVALID_ARG, "device index out of range");
+  if (n_bodies == 0) return SV_OK;
+  Device& D = *Dp;
+  hipStream_t user = (hipStream_t)stream;
+  std::lock_guard<std::mutex> g(D.mu);
+  SV_HIP(hipSetDevice(D.phys));
+  if ((rc = ready_locked(D))) return rc;
+  if (32 * n > D.txmsg.cap) {  // (growing frees the old array: earlier launches may still read it)
+    SV_HIP(hipStreamSynchronize(D.stream));
+    if ((rc = D.txmsg.ensure(32 * n))) return rc;
+  }
+  SV_HIP(hipEventRecord(D.dep_in, user));
+  SV_HIP(hipStreamWaitEvent(D.stream, D.dep_in, 0));
+  SV_HIP(sv_launch_txhash(D.grid * 8, network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies,
+                          d_sig_begin, n, D.txmsg.p, d_digests, D.stream));
+  if (n && (rc = launch_locked(D, 0, SV_PATH_AUTO, d_pk, d_sig, D.txmsg.p, nullptr, nullptr, 32, n, d_verdict,
+                               d_bitmap, kt_mode() == 1)))
+    return rc;
+  SV_HIP(hipEventRecord(D.dep_out, D.stream));
+  SV_HIP(hipStreamWaitEvent(user, D.dep_out, 0));
+  return SV_OK;
+}
+
 int sv_ed25519_verify_device(int device, const void* d_pk, const void* d_sig, const void* d_msg,
                              const uint64_t* d_msg_off, const uint32_t* d_msg_len, uint32_t fixed_msg_len,
                              size_t n, void* d_verdict, void* d_bitmap, void* stream) {
@@ -2731,7 +3028,7 @@ int sv_workspace_bytes(int device, size_t* bytes) {
   // (lock order: the lane's mutex before the slot's)
   std::lock_guard<std::mutex> gl(Dp->lat.mu);
   std::lock_guard<std::mutex> g(Dp->mu);
-  size_t b = Dp->ws.cap;
+  size_t b = Dp->ws.cap + Dp->txmsg.cap;
   for (const LatCtx& c : Dp->lat.ctx) b += c.ws.cap + c.d_in.cap + c.d_out.cap + c.d_keys.cap;
   *bytes = b;
   return SV_OK;

@@ -22,6 +22,11 @@
 // the multiplications here
 #define SV_HOST_FE51 1
 #include "verify_core.h"
+// (hash_dev.h's whole-message hashes are device-side helpers, unused here)
+#pragma GCC diagnostic push
+#pragma GCC diagnostic ignored "-Wunused-function"
+#include "txhash.h"
+#pragma GCC diagnostic pop
 
 #include <algorithm>
 #include <cstring>
@@ -103,6 +108,66 @@ int sv_ed25519_verify_batch_cpu(const uint8_t* pk, const uint8_t* sig, const uin
   work(0);
   for (auto& x : th) x.join();
   return SV_OK;
+}
+
+// Argument check shared by the three sv_ed25519_verify_txbodies* host-array
+// entry points (sv_api.cpp calls it too): SV_OK or SV_ERR_INVALID_ARG.
+int sv_txbodies_check(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                      const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies, const uint64_t* sig_begin,
+                      const uint8_t* pk, const uint8_t* sig, size_t n, const uint8_t* verdict) {
+  if (!network_id || !sig_begin) return SV_ERR_INVALID_ARG;
+  if (n_bodies && (!body_off || !body_len || !body_kind)) return SV_ERR_INVALID_ARG;
+  if (n && (!pk || !sig || !verdict)) return SV_ERR_INVALID_ARG;
+  if (sig_begin[0] != 0 || sig_begin[n_bodies] != n) return SV_ERR_INVALID_ARG;
+  for (size_t t = 0; t < n_bodies; ++t) {
+    if (sig_begin[t + 1] < sig_begin[t] || body_kind[t] > 2) return SV_ERR_INVALID_ARG;
+    if (body_len[t] && !bodies) return SV_ERR_INVALID_ARG;
+  }
+  return SV_OK;
+}
+
+int sv_ed25519_verify_txbodies_cpu(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                   const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                   const uint64_t* sig_begin, const uint8_t* pk, const uint8_t* sig, size_t n,
+                                   uint8_t* verdict, uint8_t* digests, int threads) {
+  int rc = sv_txbodies_check(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, pk, sig, n,
+                             verdict);
+  if (rc) return rc;
+  if (n_bodies == 0) return SV_OK;
+  uint32_t nid[8];
+  std::memcpy(nid, network_id, 32);
+  // the digests (threaded like the verification), then the signatures over them
+  std::vector<uint8_t> own;
+  if (!digests) {
+    own.resize(32 * n_bodies);
+    digests = own.data();
+  }
+  size_t T = threads > 0 ? (size_t)threads : std::min<size_t>(16, std::max(1u, std::thread::hardware_concurrency()));
+  T = std::max<size_t>(1, std::min(T, n_bodies / 64));
+  auto work = [&](size_t t) {
+    const size_t a = n_bodies * t / T, b = n_bodies * (t + 1) / T;
+    for (size_t i = a; i < b; ++i) {
+      uint32_t d[8];
+      sv_txhash<SV_TX_BYTES>(d, nid, bodies ? bodies + body_off[i] : nullptr, body_len[i], body_kind[i]);
+      std::memcpy(digests + 32 * i, d, 32);
+    }
+  };
+  {
+    std::vector<std::thread> th;
+    for (size_t t = 1; t < T; ++t) th.emplace_back(work, t);
+    work(0);
+    for (auto& x : th) x.join();
+  }
+  if (n == 0) return SV_OK;
+  std::vector<uint8_t> msg(32 * n);
+  std::vector<uint64_t> off(n);
+  const std::vector<uint32_t> len(n, 32u);
+  for (size_t t = 0; t < n_bodies; ++t)
+    for (uint64_t s = sig_begin[t]; s < sig_begin[t + 1]; ++s) {
+      std::memcpy(&msg[32 * s], digests + 32 * t, 32);
+      off[s] = 32 * s;
+    }
+  return sv_ed25519_verify_batch_cpu(pk, sig, msg.data(), off.data(), len.data(), n, verdict, threads);
 }
 
 int sv_ed25519_verify_cpu(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, size_t msg_len) {
