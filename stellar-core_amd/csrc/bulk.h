@@ -1,0 +1,644 @@
+// Bulk work of a device slot, on its three streams under Device::mu: the
+// throughput-path launch with its per-key tables, the staged host-buffer
+// pipeline (host_slice), its kernel-less probe (feed_slice), SHA-256 batches
+// (sha_slice) and tx-body batches (tx_slice).  Included by sv_api.cpp.
+#pragma once
+
+#include <chrono>
+#include <cstdio>
+#include <functional>
+#include <random>
+#include <thread>
+
+#include "engine_state.h"
+#include "host_image.h"
+
+namespace sv {
+namespace {
+
+// Shared mode of the throughput kernels (sv_kernels.hip sv_launch_verify):
+// taken by every bulk launch within SV_LAT_SHARE_MS (default 1000) ms of a
+// latency-lane batch on the same slot, so SCP-class batches find free
+// workgroup slots while a tx set or catchup batch runs.  0 disables it.
+inline int64_t share_window_ns() {
+  static const int64_t w = (int64_t)env_size("SV_LAT_SHARE_MS", 1000) * 1000000;
+  return w;
+}
+inline size_t share_upload_bytes() {
+  static const size_t b = std::max<size_t>(64, env_size("SV_SHARE_UPLOAD_KB", 2048)) * 1024;
+  return b;
+}
+// One-chunk host batches (n <= SV_STAGE_CHUNK) read in place
+// (SV_BULK_ZC_IN, default on; 0: one staged H2D copy): the kernels read the
+// packed image from mapped pinned memory, so the copy no longer runs before
+// the first kernel (a multi-chunk batch overlaps its copies with the previous
+// chunk's kernels and stays staged).
+inline bool bulk_in_place() {
+  static const bool b = env_size("SV_BULK_ZC_IN", 1) != 0;
+  return b;
+}
+// ... and their verdicts are written in place too (SV_BULK_ZC_OUT, default on):
+// the kernels store them to mapped memory, so no copy is queued behind them.
+inline bool bulk_zc_out() {
+  static const bool b = env_size("SV_BULK_ZC_OUT", 1) != 0;
+  return b;
+}
+// One-chunk throughput launches read in place run the prep kernel in its
+// decode-first order (sv_kernels.hip sv_prep_kernel DF; SV_DECODE_FIRST=0: the
+// device path's order)
+inline bool decode_first() {
+  static const bool b = env_size("SV_DECODE_FIRST", 1) != 0;
+  return b;
+}
+inline bool share_now(const Device& D) {
+  const int64_t w = share_window_ns();
+  return w > 0 && now_ns() - D.lat_last_ns.load(std::memory_order_relaxed) < w;
+}
+
+// Runs fn() on the slot: D.mu held, the device set, the slot's resources
+// created.  A failing call leaves the slot reusable: nothing of it may still
+// be in flight.
+template <class F>
+int with_slot(Device& D, F fn) {
+  std::lock_guard<std::mutex> g(D.mu);
+  SV_HIP(hipSetDevice(D.phys));
+  int rc;
+  if ((rc = ready_locked(D))) return rc;
+  if ((rc = fn()) != SV_OK) {
+    (void)hipStreamSynchronize(D.h2d);
+    (void)hipStreamSynchronize(D.stream);
+    (void)hipStreamSynchronize(D.d2h);
+    D.st[0].busy = D.st[1].busy = false;
+  }
+  return rc;
+}
+
+inline unsigned grid_for(const Device& D, uint64_t n, bool share = false) {
+  const uint64_t need = (n + sv_block_threads() - 1) / sv_block_threads();
+  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(share ? D.grid_share : D.grid, need));
+}
+
+// ---------------------------------------------------- per-key tables
+// sv_set_key_tables: 0 off, 1 on for every throughput-path launch, 2 (auto,
+// the default) on for host-buffer batches whose keys repeat (repeated_keys);
+// -1: SV_KEY_TABLES.  Slots: SV_KEY_TABLE_SLOTS (default 2^19; claims stop at
+// half of them, when the claim words are cleared).
+inline std::atomic<int> g_kt_mode{-1};
+inline std::atomic<size_t> g_kt_slots{0};
+inline int kt_mode() {
+  const int v = g_kt_mode.load();
+  if (v >= 0) return v;
+  return (int)std::min<size_t>(2, env_size("SV_KEY_TABLES", 2));
+}
+inline size_t kt_slots() {
+  size_t v = g_kt_slots.load();
+  if (v == 0) v = env_size("SV_KEY_TABLE_SLOTS", (size_t)1 << 19);
+  size_t p = 1024;
+  while (p < v && p < ((size_t)1 << 26)) p <<= 1;
+  return p;
+}
+
+// Readies the slot's key tables for a launch of n (caller holds D.mu, device
+// set) and fills *kt; false: tables unavailable (allocation failed), the
+// launch runs without them.
+inline bool kt_prepare(Device& D, uint64_t n, sv_ktparams* kt) {
+  KeyTabs& T = D.kt;
+  const size_t want = kt_slots();
+  if (T.slots != want) {
+    (void)hipStreamSynchronize(D.stream);
+    T.index.release();
+    T.store.release();
+    T.slots = 0;
+    if (T.index.ensure(want * 8) || T.store.ensure(want * sv_key_table_entry_bytes()) || T.count.ensure(16) ||
+        T.h_count.ensure(16))
+      return false;
+    if (!T.copied && hipEventCreateWithFlags(&T.copied, hipEventDisableTiming) != hipSuccess) return false;
+    if (hipMemsetAsync(T.index.p, 0, want * 8, D.stream) != hipSuccess ||
+        hipMemsetAsync(T.count.p, 0, 16, D.stream) != hipSuccess)
+      return false;
+    std::memset(T.h_count.p, 0, 16);
+    T.salt = ((uint64_t)std::random_device{}() << 32) ^ std::random_device{}() ^ (uint64_t)now_ns();
+    T.slots = want;
+  }
+  const uint64_t cap = sv_plan_chunk_max(n);
+  if (cap * 4 > T.kslot.cap || cap * 4 > T.builders.cap) {
+    (void)hipStreamSynchronize(D.stream);  // (the lists of a running launch)
+    if (T.kslot.ensure(cap * 4) || T.builders.ensure(cap * 4)) return false;
+  }
+  // the claims as of the last launch whose counters have come back
+  const uint32_t limit = (uint32_t)(want / 2);
+  if (hipEventQuery(T.copied) == hipSuccess) {
+    T.claims = ((const uint32_t*)T.h_count.p)[1];
+    if (T.claims >= limit) {
+      if (hipMemsetAsync(T.index.p, 0, want * 8, D.stream) != hipSuccess ||
+          hipMemsetAsync(T.count.p, 0, 16, D.stream) != hipSuccess)
+        return false;
+      std::memset(T.h_count.p, 0, 16);
+      T.claims = 0;
+      ++T.clears;
+    }
+  }
+  kt->index = (unsigned long long*)T.index.p;
+  kt->store = (sv_u4*)T.store.p;
+  kt->kslot = (uint32_t*)T.kslot.p;
+  kt->builders = (uint32_t*)T.builders.p;
+  kt->count = (uint32_t*)T.count.p;
+  kt->mask = want - 1;
+  kt->limit = limit;
+  kt->salt = T.salt;
+  return true;
+}
+
+// Launch on D.stream (caller holds D.mu and has set the device).  tables:
+// the launch may use the per-key tables (kt_mode / repeated_keys).
+// kp: SV_KP_* launch hints (SV_KP_IN_PLACE: the inputs are mapped host memory)
+inline int launch_locked(Device& D, int mode, int path, const void* pk, const void* sig, const void* msg,
+                         const uint64_t* off, const uint32_t* len, uint32_t fixed_len, uint64_t n, void* verdict,
+                         void* bitmap, bool tables = false, uint32_t kp = 0) {
+  const int rp = resolve_path(path, n);
+  const bool share = rp != SV_PATH_LATENCY && share_now(D);
+  const unsigned grid = grid_for(D, n, share);
+  int rc;
+  sv_ktparams ktp{};
+  const int geom = launch_geometry(rp, n);
+  const bool kt_on = tables && geom == SV_PATH_THROUGHPUT && kt_prepare(D, n, &ktp);
+  if ((rc = ensure_ws(D, sv_verify_ws_bytes(geom, grid, n)))) return rc;
+  if ((rc = D.timer.begin(D.stream))) return rc;
+  SV_HIP(sv_launch_verify(mode, geom, grid, pk, sig, msg, off, len, fixed_len, n, verdict, bitmap, D.ws.p, D.btab,
+                          (g_dbg.load() & kKernelDbgMask) | (kt_on ? 0u : kp), share ? 1 : 0, kt_on ? &ktp : nullptr,
+                          nullptr, D.stream));
+  if (share) D.shared_launches.fetch_add(1, std::memory_order_relaxed);
+  if (kt_on) {
+    ++D.kt.launches;
+    SV_HIP(hipMemcpyAsync(D.kt.h_count.p, D.kt.count.p, 8, hipMemcpyDeviceToHost, D.stream));
+    SV_HIP(hipEventRecord(D.kt.copied, D.stream));
+  }
+  return D.timer.end(D.stream, n);
+}
+
+// The workspace of the largest launch of a call (m signatures on `path`)
+// before its first launch, so it never grows under a running kernel.
+inline int presize_ws(Device& D, int path, size_t m) {
+  const int rp = resolve_path(path, m);
+  return ensure_ws(D, std::max(sv_verify_ws_bytes(rp, grid_for(D, m), m),
+                               sv_verify_ws_bytes(launch_geometry(rp, m), grid_for(D, m), m)));
+}
+
+// H2D of a whole packed image.  While latency-lane batches are live (shared
+// mode) it goes up in pieces of SV_SHARE_UPLOAD_KB (default 2048): a 1k
+// batch's 370 KB copy otherwise queues behind the whole 32 MB chunk copy
+// (~0.65 ms, once per chunk: profiles/r04/isolation/).
+inline int upload_image(const Device& D, void* d, const void* h, size_t bytes, hipStream_t st) {
+  const size_t piece = share_now(D) ? share_upload_bytes() : bytes;
+  for (size_t o = 0; o < bytes; o += piece)
+    SV_HIP(hipMemcpyAsync((uint8_t*)d + o, (const uint8_t*)h + o, std::min(piece, bytes - o), hipMemcpyHostToDevice,
+                          st));
+  return SV_OK;
+}
+// H2D of rows [a, b) of a packed image (each section's slice); msg_total: the
+// image's message bytes.
+inline int upload_rows(const Image& im, size_t m, size_t a, size_t b, uint32_t fixed, size_t msg_total,
+                       const uint8_t* h, uint8_t* d, hipStream_t st) {
+  SV_HIP(hipMemcpyAsync(d + 32 * a, h + 32 * a, 32 * (b - a), hipMemcpyHostToDevice, st));
+  SV_HIP(hipMemcpyAsync(d + im.o_sig + 64 * a, h + im.o_sig + 64 * a, 64 * (b - a), hipMemcpyHostToDevice, st));
+  size_t m0, m1;
+  if (im.var) {
+    SV_HIP(hipMemcpyAsync(d + im.o_off + 8 * a, h + im.o_off + 8 * a, 8 * (b - a), hipMemcpyHostToDevice, st));
+    SV_HIP(hipMemcpyAsync(d + im.o_len + 4 * a, h + im.o_len + 4 * a, 4 * (b - a), hipMemcpyHostToDevice, st));
+    const uint64_t* offs = (const uint64_t*)(h + im.o_off);
+    m0 = offs[a];
+    m1 = b < m ? offs[b] : msg_total;
+  } else {
+    m0 = a * (size_t)fixed;
+    m1 = b * (size_t)fixed;
+  }
+  if (m1 > m0) SV_HIP(hipMemcpyAsync(d + im.o_msg + m0, h + im.o_msg + m0, m1 - m0, hipMemcpyHostToDevice, st));
+  return SV_OK;
+}
+
+// Collects a finished chunk's results from its pinned slot.
+inline int drain_stage(Stage& s, uint8_t* verdict, uint8_t* keys) {
+  if (!s.busy) return SV_OK;
+  SV_HIP(hipEventSynchronize(s.down));
+  if (stage_trace()) fprintf(stderr, "SV_STAGE_TRACE down synced @%.1f\n", trace_abs_us());
+  s.busy = false;
+  const uint8_t* h = (const uint8_t*)s.h_out.p;
+  if (verdict) std::memcpy(verdict + s.lo, s.zv ? s.zv : h, s.m);
+  if (keys) std::memcpy(keys + 32 * s.lo, h + (verdict ? s.m : 0), 32 * s.m);
+  return SV_OK;
+}
+
+inline thread_local std::chrono::steady_clock::time_point g_trace_t0;  // (SV_STAGE_TRACE: host_slice entry)
+
+// Runs fn(0), fn(1), ... fn(P - 1) on a thread of its own, fn(k) once piece
+// k's events have been recorded (recorded(k + 1)); join() returns the first
+// error.  The destructor stops and joins it (an early error return of the
+// caller).
+class KeyNotifier {
+ public:
+  ~KeyNotifier() {
+    stop_.store(true);
+    if (th_.joinable()) th_.join();
+  }
+  void start(int dev, size_t P, std::function<int(size_t)> fn) {
+    fn_ = std::move(fn);
+    th_ = std::thread([this, dev, P] {
+      // (the caller holds the lifetime lock until this thread is joined)
+      t_life_depth = 1;
+      (void)hipSetDevice(dev);
+      for (size_t k = 0; k < P; ++k) {
+        while (rec_.load(std::memory_order_acquire) <= k) {
+          if (stop_.load()) return;
+          std::this_thread::yield();
+        }
+        const int rc = fn_(k);
+        if (rc != SV_OK) {
+          rc_ = rc;
+          return;
+        }
+      }
+    });
+  }
+  void recorded(size_t k) { rec_.store(k, std::memory_order_release); }
+  int join() {
+    if (th_.joinable()) th_.join();
+    return rc_;
+  }
+
+ private:
+  std::thread th_;
+  std::function<int(size_t)> fn_;
+  std::atomic<size_t> rec_{0};
+  std::atomic<bool> stop_{false};
+  int rc_ = SV_OK;
+};
+
+// Host-buffer slice on one slot, pipelined over staging chunks: verdicts
+// (verdict != null) and/or BLAKE2b cache keys (keys != null) into the
+// caller's arrays.  keys_cb (optional, with keys and verdict): called once
+// every key is in `keys` -- for a one-chunk batch while the verify kernels
+// are still running, so the caller's cache walk overlaps them; *cb_done
+// records that it ran.
+inline int host_slice_locked(Device& D, const HostIn& in, size_t n, uint8_t* verdict, uint8_t* keys, int path,
+                             const KeysCb& kcb, bool* cb_done) {
+  KeyNotifier notifier;  // (joined on every return path)
+  const size_t chunk = std::min(n, stage_chunk());
+  int rc;
+  const int ktm = kt_mode();
+  // (decided at the first launch: a keyed batch's first pieces go up before it)
+  int tables = -1;
+  auto trace_at = [](const char* what) {
+    if (stage_trace())
+      fprintf(stderr, "SV_STAGE_TRACE %s at %.1f us @%.1f\n", what,
+              std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - g_trace_t0).count(),
+              trace_abs_us());
+  };
+  if (verdict && (rc = presize_ws(D, path, chunk))) return rc;
+  trace_at("workspace");
+  const size_t out_per = (verdict ? 1 : 0) + (keys ? 32 : 0);
+  // one chunk (latency-bound batches): everything on the kernel stream, no
+  // cross-stream event waits
+  const bool single = n <= chunk;
+  hipStream_t up_s = single ? D.stream : D.h2d, down_s = single ? D.stream : D.d2h;
+  if (!single && stage_ramp()) {
+    // size both slots for a full chunk up front (the ramped first chunks
+    // would otherwise grow the pinned buffers twice)
+    size_t mt;
+    const Image im = image_of(in, 0, chunk, &mt);
+    for (Stage& s : D.st)
+      if ((rc = s.h_in.ensure(im.bytes)) || (rc = s.d_in.ensure(im.bytes)) || (rc = s.h_out.ensure(out_per * chunk)))
+        return rc;
+  }
+  size_t c = 0;
+  size_t m = 0;
+  for (size_t lo = 0; lo < n; lo += m, ++c) {
+    Stage& s = D.st[c & 1];
+    // slot c & 1 was last used by chunk c - 2: its results are collected
+    // (which also means its H2D, kernels and D2H are complete)
+    if ((rc = drain_stage(s, verdict, keys))) return rc;
+    trace_at("slot drained");
+    m = single ? n : chunk_len(c, chunk, n - lo);
+    size_t msg_total;
+    const Image im = image_of(in, lo, m, &msg_total);
+    const bool early = single && kcb && keys && verdict;
+    // a one-chunk keyed batch with a keys-ready callback: pack, copy up, hash
+    // and copy the keys down in pieces, so the caller's walk starts early
+    const std::vector<size_t> pb = early ? key_pieces(m) : std::vector<size_t>{0, m};
+    const size_t P = pb.size() - 1;
+    const bool in_place = single && P == 1 && bulk_in_place();
+    const bool zc_out = in_place && verdict && bulk_zc_out();
+    HostBuf& hin = in_place ? D.z_in : s.h_in;
+    if ((rc = hin.ensure(im.bytes)) || (!in_place && (rc = s.d_in.ensure(im.bytes))) ||
+        (rc = s.h_out.ensure(out_per * m)))
+      return rc;
+    if (verdict && !zc_out && (rc = s.d_verdict.ensure(m))) return rc;
+    if (zc_out && (rc = D.z_out.ensure(m))) return rc;
+    if (keys && (rc = s.d_keys.ensure(32 * m))) return rc;
+    uint8_t* d = (uint8_t*)(in_place ? D.z_in.dp : s.d_in.p);
+    uint8_t* hp = (uint8_t*)hin.p;
+    const uint64_t* d_off = im.var ? (const uint64_t*)(d + im.o_off) : nullptr;
+    const uint32_t* d_len = im.var ? (const uint32_t*)(d + im.o_len) : nullptr;
+    while (s.pev.size() < P) {
+      hipEvent_t e;
+      SV_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      s.pev.push_back(e);
+    }
+    const auto t_pack = stage_trace() ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
+    trace_at("staging");
+    if (P == 1) {
+      pack(in, lo, m, im, hp);
+      if (!in_place && (rc = upload_image(D, s.d_in.p, s.h_in.p, im.bytes, up_s))) return rc;
+      trace_at("uploads enqueued");
+      if (!single) {
+        SV_HIP(hipEventRecord(s.up, D.h2d));
+        SV_HIP(hipStreamWaitEvent(D.stream, s.up, 0));
+      }
+      if (keys)
+        SV_HIP(sv_launch_hash(0, D.grid * 2, d, d + im.o_sig, d + im.o_msg, d_off, d_len, in.fixed, m, s.d_keys.p,
+                              D.stream));
+      if (early) {
+        // keys down on the D2H stream while the verify kernels run
+        SV_HIP(hipEventRecord(s.done, D.stream));
+        SV_HIP(hipStreamWaitEvent(D.d2h, s.done, 0));
+        SV_HIP(hipMemcpyAsync((uint8_t*)s.h_out.p + m, s.d_keys.p, 32 * m, hipMemcpyDeviceToHost, D.d2h));
+        SV_HIP(hipEventRecord(s.pev[0], D.d2h));
+      }
+    } else {
+      // The pieces' keys go to the caller from a notifier thread while this
+      // thread packs and uploads the next pieces (every callback runs on that
+      // one thread, in order).
+      const auto t0 = g_trace_t0;
+      auto us = [t0] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); };
+      // (pb and us by value: an error return leaves this scope before the
+      // notifier is joined)
+      notifier.start(D.phys, P, [&, m, lo, pb, us](size_t k) -> int {
+        const size_t a = pb[k], b = pb[k + 1];
+        SV_HIP(hipEventSynchronize(s.pev[k]));
+        if (stage_trace()) fprintf(stderr, "SV_STAGE_TRACE keys piece %zu down at %.1f us\n", k, us());
+        std::memcpy(keys + 32 * (lo + a), (uint8_t*)s.h_out.p + m + 32 * a, 32 * (b - a));
+        kcb(lo + b);
+        if (stage_trace()) fprintf(stderr, "SV_STAGE_TRACE keys piece %zu walked at %.1f us\n", k, us());
+        return SV_OK;
+      });
+      uint64_t pos = 0;  // (each piece writes its own message offsets first)
+      for (size_t k = 0; k < P; ++k) {
+        const size_t a = pb[k], b = pb[k + 1];
+        pos = pack_offsets(in, lo, a, b, pos, im, hp);
+        if (im.var && b < m) ((uint64_t*)(hp + im.o_off))[b] = pos;  // (upload_rows reads the piece's end there)
+        pack_rows(in, lo, a, b, im, hp, 1u << 16);
+        if (k == 0) trace_at("piece 0 packed");
+        // uploads on the copy stream: piece k + 1 goes up while piece k hashes
+        // (the slot's earlier work is complete: drained above)
+        if ((rc = upload_rows(im, m, a, b, in.fixed, msg_total, hp, d, D.h2d))) return rc;
+        SV_HIP(hipEventRecord(s.up, D.h2d));
+        SV_HIP(hipStreamWaitEvent(D.stream, s.up, 0));
+        if (k == 0) trace_at("piece 0 uploading");
+        SV_HIP(sv_launch_hash(0, D.grid * 2, d + 32 * a, d + im.o_sig + 64 * a,
+                              d + im.o_msg + (im.var ? 0 : a * (size_t)in.fixed), d_off ? d_off + a : nullptr,
+                              d_len ? d_len + a : nullptr, in.fixed, b - a, (uint8_t*)s.d_keys.p + 32 * a, D.stream));
+        SV_HIP(hipEventRecord(s.done, D.stream));
+        SV_HIP(hipStreamWaitEvent(D.d2h, s.done, 0));
+        SV_HIP(hipMemcpyAsync((uint8_t*)s.h_out.p + m + 32 * a, (uint8_t*)s.d_keys.p + 32 * a, 32 * (b - a),
+                              hipMemcpyDeviceToHost, D.d2h));
+        SV_HIP(hipEventRecord(s.pev[k], D.d2h));
+        notifier.recorded(k + 1);
+        if (stage_trace()) fprintf(stderr, "SV_STAGE_TRACE piece %zu enqueued at %.1f us\n", k, us());
+      }
+    }
+    if (stage_trace()) g_trace_pack_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_pack).count();
+    if (verdict) {
+      const int mode = verify_mode(im.var, in.fixed);
+      // (only the one-lane geometry uses the tables: a quad-geometry batch
+      // skips the key sample, ~4k scattered reads of the caller's keys)
+      if (tables < 0)
+        tables = launch_geometry(resolve_path(path, chunk), chunk) == SV_PATH_THROUGHPUT &&
+                 (ktm == 1 || (ktm == 2 && repeated_keys(in, n)));
+      if ((rc = launch_locked(D, mode, path, d, d + im.o_sig, d + im.o_msg, d_off, d_len, in.fixed, m,
+                              zc_out ? D.z_out.dp : s.d_verdict.p, nullptr, tables != 0,
+                              in_place && decode_first() ? SV_KP_IN_PLACE : 0u)))
+        return rc;
+      trace_at("launched");
+    }
+    if (!single) {
+      SV_HIP(hipEventRecord(s.done, D.stream));
+      SV_HIP(hipStreamWaitEvent(D.d2h, s.done, 0));
+    }
+    uint8_t* ho = (uint8_t*)s.h_out.p;
+    if (verdict && !zc_out) SV_HIP(hipMemcpyAsync(ho, s.d_verdict.p, m, hipMemcpyDeviceToHost, down_s));
+    if (keys && !early)
+      SV_HIP(hipMemcpyAsync(ho + (verdict ? m : 0), s.d_keys.p, 32 * m, hipMemcpyDeviceToHost, down_s));
+    SV_HIP(hipEventRecord(s.down, down_s));
+    s.busy = true;
+    s.lo = lo;
+    s.m = m;
+    s.zv = zc_out ? (const uint8_t*)D.z_out.p : nullptr;
+    if (early) {
+      if (P == 1) {
+        SV_HIP(hipEventSynchronize(s.pev[0]));
+        std::memcpy(keys + 32 * lo, ho + m, 32 * m);
+        kcb(lo + m);
+      } else if ((rc = notifier.join())) {
+        return rc;
+      }
+      *cb_done = true;
+    }
+  }
+  for (Stage& s : D.st)
+    if ((rc = drain_stage(s, verdict, keys))) return rc;
+  return SV_OK;
+}
+
+inline int host_slice(Device& D, const HostIn& in, size_t n, uint8_t* verdict, uint8_t* keys, int path,
+                      const KeysCb& kcb = KeysCb(), bool* cb_done = nullptr) {
+  return with_slot(D, [&] {
+    const auto t0 = std::chrono::steady_clock::now();
+    g_trace_t0 = t0;
+    g_trace_pack_us = 0;
+    const int rc = host_slice_locked(D, in, n, verdict, keys, path, kcb, cb_done);
+    if (stage_trace())
+      fprintf(stderr, "SV_STAGE_TRACE n=%zu pack %.1f us total %.1f us\n", n, g_trace_pack_us,
+              std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
+    return rc;
+  });
+}
+
+// Host feed of a slice without kernels (sv_host_feed_probe): host_slice's
+// staging loop -- chunks of stage_chunk() with the ramp, packed into the
+// slot's two pinned slots by the pack pool, and with `upload` copied up on
+// the H2D stream, a slot reused once its copy is done -- and nothing else.
+// staging_node: NUMA node of the first pinned slot's pages.
+inline int feed_slice(Device& D, const HostIn& in, size_t n, int upload, int* staging_node) {
+  std::lock_guard<std::mutex> g(D.mu);
+  SV_HIP(hipSetDevice(D.phys));
+  int rc;
+  if ((rc = ready_locked(D))) return rc;
+  const size_t chunk = std::min(n, stage_chunk());
+  // (the slots' `busy` flags belong to host_slice's pending verdict copies:
+  // the probe tracks its own uploads, and leaves nothing in flight on any
+  // return -- the copy stream is drained before an error is reported)
+  bool pending[2] = {false, false};
+  auto drain = [&] { (void)hipStreamSynchronize(D.h2d); };
+  size_t m = 0;
+  for (size_t lo = 0, c = 0; lo < n; lo += m, ++c) {
+    Stage& s = D.st[c & 1];
+    if (pending[c & 1]) {
+      const hipError_t e = hipEventSynchronize(s.up);
+      pending[c & 1] = false;
+      if (e != hipSuccess) {
+        drain();
+        return hip_fail(e, "feed probe: upload");
+      }
+    }
+    m = n <= chunk ? n : chunk_len(c, chunk, n - lo);
+    size_t msg_total;
+    const Image im = image_of(in, lo, m, &msg_total);
+    if ((rc = s.h_in.ensure(im.bytes)) || (upload && (rc = s.d_in.ensure(im.bytes)))) {
+      drain();
+      return rc;
+    }
+    pack(in, lo, m, im, (uint8_t*)s.h_in.p);
+    if (upload) {
+      hipError_t e = hipMemcpyAsync(s.d_in.p, s.h_in.p, im.bytes, hipMemcpyHostToDevice, D.h2d);
+      if (e == hipSuccess) e = hipEventRecord(s.up, D.h2d);
+      if (e != hipSuccess) {
+        drain();
+        return hip_fail(e, "feed probe: upload");
+      }
+      pending[c & 1] = true;
+    }
+  }
+  SV_HIP(hipStreamSynchronize(D.h2d));
+  if (staging_node) *staging_node = page_numa_node(D.st[0].h_in.p);
+  return SV_OK;
+}
+
+// SHA-256 of a host slice of byte strings on one slot.
+inline int sha_slice(Device& D, const uint8_t* data, const uint64_t* off, const uint32_t* len, size_t n, uint8_t* out) {
+  std::lock_guard<std::mutex> g(D.mu);
+  SV_HIP(hipSetDevice(D.phys));
+  int rc;
+  if ((rc = ready_locked(D))) return rc;
+  size_t total = 0;
+  for (size_t i = 0; i < n; ++i) total += len[i];
+  const size_t o_len = 8 * n, o_msg = 12 * n, bytes = o_msg + std::max<size_t>(total, 1);
+  if ((rc = D.h_sha.ensure(bytes)) || (rc = D.msg.ensure(bytes)) || (rc = D.keys.ensure(n * 32))) return rc;
+  uint8_t* h = (uint8_t*)D.h_sha.p;
+  uint64_t* offs = (uint64_t*)h;
+  size_t pos = 0;
+  for (size_t i = 0; i < n; ++i) {
+    offs[i] = pos;
+    if (len[i]) std::memcpy(h + o_msg + pos, data + off[i], len[i]);
+    pos += len[i];
+  }
+  std::memcpy(h + o_len, len, 4 * n);
+  SV_HIP(hipMemcpyAsync(D.msg.p, h, bytes, hipMemcpyHostToDevice, D.stream));
+  uint8_t* d = (uint8_t*)D.msg.p;
+  SV_HIP(sv_launch_hash(1, D.grid * 2, nullptr, nullptr, d + o_msg, (const uint64_t*)d, (const uint32_t*)(d + o_len),
+                        0, n, D.keys.p, D.stream));
+  SV_HIP(hipMemcpyAsync(out, D.keys.p, n * 32, hipMemcpyDeviceToHost, D.stream));
+  SV_HIP(hipStreamSynchronize(D.stream));
+  return SV_OK;
+}
+
+// The n x 32 message array a tx-body launch's hash kernel fills (caller
+// holds D.mu, device set).  Growing it frees the old array, which earlier
+// launches may still read, so the kernel stream is drained first.
+inline int ensure_txmsg(Device& D, size_t n) {
+  if (32 * n <= D.txmsg.cap) return SV_OK;
+  SV_HIP(hipStreamSynchronize(D.stream));
+  return D.txmsg.ensure(32 * n);
+}
+
+// A chunk's results in its pinned slot: verdicts (m), then digests (32 k).
+struct TxPending {
+  bool busy = false;
+  TxChunk c;
+};
+inline int tx_drain(Stage& s, TxPending& pd, size_t dig_from, uint8_t* verdict, uint8_t* digests) {
+  if (!pd.busy) return SV_OK;
+  SV_HIP(hipEventSynchronize(s.down));
+  pd.busy = false;
+  const TxChunk& c = pd.c;
+  const size_t m = c.s1 - c.s0;
+  const uint8_t* h = (const uint8_t*)s.h_out.p;
+  if (m) std::memcpy(verdict + c.s0, h, m);
+  if (digests) {
+    // (a body whose signatures straddle the slice's lower boundary was also
+    // hashed by the slot before: that slot delivers its digest)
+    const size_t from = std::max(c.b0, dig_from);
+    if (from < c.b1) std::memcpy(digests + 32 * from, h + m + 32 * (from - c.b0), 32 * (c.b1 - from));
+  }
+  if (stage_trace()) fprintf(stderr, "SV_STAGE_TRACE tx chunk [%zu, %zu) drained @%.1f\n", c.b0, c.b1, trace_abs_us());
+  return SV_OK;
+}
+
+// Bodies [B0, B1) and signatures [lo, hi) on one slot (caller holds D.mu,
+// device set): per chunk pack -> H2D -> hash kernel -> verify launch (mode 0
+// over the message array, same stream) -> D2H, over the slot's two staging
+// slots as host_slice_locked does, so chunk c + 1 is packed and copied up
+// while chunk c hashes and verifies.
+inline int tx_slice_locked(Device& D, const TxIn& in, size_t B0, size_t B1, size_t lo, size_t hi, size_t dig_from,
+                           uint8_t* verdict, uint8_t* digests, int path) {
+  int rc;
+  if (stage_trace()) fprintf(stderr, "SV_STAGE_TRACE tx slice @%.1f\n", trace_abs_us());
+  const std::vector<TxChunk> plan = tx_plan(in, B0, B1, lo, hi, stage_chunk(), txbody_chunk_bytes());
+  if (plan.empty()) return SV_OK;
+  if (stage_trace()) fprintf(stderr, "SV_STAGE_TRACE tx plan: %zu chunks @%.1f\n", plan.size(), trace_abs_us());
+  size_t max_m = 0;
+  for (const TxChunk& c : plan) max_m = std::max(max_m, c.s1 - c.s0);
+  // the message array and the largest launch's workspace first, so neither
+  // grows under a running kernel
+  if ((rc = ensure_txmsg(D, max_m))) return rc;
+  if (max_m && (rc = presize_ws(D, path, max_m))) return rc;
+  const bool single = plan.size() == 1;
+  hipStream_t up_s = single ? D.stream : D.h2d, down_s = single ? D.stream : D.d2h;
+  TxPending pend[2];
+  for (size_t ci = 0; ci < plan.size(); ++ci) {
+    const TxChunk& c = plan[ci];
+    Stage& s = D.st[ci & 1];
+    if ((rc = tx_drain(s, pend[ci & 1], dig_from, verdict, digests))) return rc;
+    const size_t m = c.s1 - c.s0, k = c.b1 - c.b0;
+    if ((rc = s.h_in.ensure(c.bytes)) || (rc = s.d_in.ensure(c.bytes)) || (rc = s.h_out.ensure(m + 32 * k)) ||
+        (rc = s.d_verdict.ensure(std::max<size_t>(m, 1))) || (rc = s.d_keys.ensure(32 * k)))
+      return rc;
+    uint8_t* hp = (uint8_t*)s.h_in.p;
+    uint8_t* d = (uint8_t*)s.d_in.p;
+    if (stage_trace()) fprintf(stderr, "SV_STAGE_TRACE tx chunk %zu staging @%.1f\n", ci, trace_abs_us());
+    tx_pack(in, c, lo, hi, hp);
+    if (stage_trace())
+      fprintf(stderr, "SV_STAGE_TRACE tx chunk %zu packed (%zu B, %zu sigs) @%.1f\n", ci, c.bytes, m, trace_abs_us());
+    if ((rc = upload_image(D, d, hp, c.bytes, up_s))) return rc;
+    if (!single) {
+      SV_HIP(hipEventRecord(s.up, D.h2d));
+      SV_HIP(hipStreamWaitEvent(D.stream, s.up, 0));
+    }
+    SV_HIP(sv_launch_txhash(D.grid * 8, in.nid, d + c.o_body, (const uint64_t*)(d + c.o_off),
+                            (const uint32_t*)(d + c.o_len), d + c.o_kind, k, (const uint64_t*)(d + c.o_sb), m,
+                            D.txmsg.p, s.d_keys.p, D.stream));
+    if (m && (rc = launch_locked(D, 0, path, d, d + c.o_sig, D.txmsg.p, nullptr, nullptr, 32, m, s.d_verdict.p,
+                                 nullptr, kt_mode() == 1)))
+      return rc;
+    if (!single) {
+      SV_HIP(hipEventRecord(s.done, D.stream));
+      SV_HIP(hipStreamWaitEvent(D.d2h, s.done, 0));
+    }
+    uint8_t* ho = (uint8_t*)s.h_out.p;
+    if (m) SV_HIP(hipMemcpyAsync(ho, s.d_verdict.p, m, hipMemcpyDeviceToHost, down_s));
+    if (digests) SV_HIP(hipMemcpyAsync(ho + m, s.d_keys.p, 32 * k, hipMemcpyDeviceToHost, down_s));
+    SV_HIP(hipEventRecord(s.down, down_s));
+    pend[ci & 1].busy = true;
+    pend[ci & 1].c = c;
+    if (stage_trace()) fprintf(stderr, "SV_STAGE_TRACE tx chunk %zu enqueued @%.1f\n", ci, trace_abs_us());
+  }
+  for (int i = 0; i < 2; ++i)
+    if ((rc = tx_drain(D.st[i], pend[i], dig_from, verdict, digests))) return rc;
+  return SV_OK;
+}
+
+inline int tx_slice(Device& D, const TxIn& in, size_t B0, size_t B1, size_t lo, size_t hi, size_t dig_from,
+                    uint8_t* verdict, uint8_t* digests, int path) {
+  return with_slot(D, [&] { return tx_slice_locked(D, in, B0, B1, lo, hi, dig_from, verdict, digests, path); });
+}
+
+}  // namespace
+}  // namespace sv

@@ -1,5 +1,5 @@
 // Layout of the comb tables of the warm-key latency path (sv_comb.hip),
-// shared by the device code and the host engine (sv_api.cpp).
+// shared by the device code and the host engine (latlane.h).
 //
 // The latency path evaluates libsodium's own equation
 //

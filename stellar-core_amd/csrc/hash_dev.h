@@ -2,10 +2,10 @@
 //
 // What they replace in the reference:
 //   * verify-cache key  BLAKE2b-256(pk || sig || msg)  per signature,
-//     /root/reference/src/crypto/SecretKey.cpp:50-61 (verifySigCacheKey), hashed
+//     src/crypto/SecretKey.cpp:50-61 (verifySigCacheKey), hashed
 //     on the host before every cache lookup;
 //   * transaction contents hash  SHA-256(networkID || envelope type || tx XDR),
-//     /root/reference/src/transactions/TransactionFrame.cpp:90-117, the 32-byte
+//     src/transactions/TransactionFrame.cpp:90-117, the 32-byte
 //     message every transaction signature is verified over.
 // Computing them in the same device pass removes the remaining per-signature
 // host cost (~1 us of BLAKE2b against ~14 ns of GPU verification).

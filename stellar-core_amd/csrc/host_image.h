@@ -1,0 +1,367 @@
+// What the kernels read from a host batch, and how it gets there: the batch
+// forms (HostIn, TxIn), the layout of their pinned images (Image, TxChunk),
+// the packers that fill an image on the pack pool, and the planners that cut
+// a batch into staging chunks and key pieces.  Pure host code, no HIP:
+// included by the engine (sv_api.cpp, through bulk.h and latlane.h) and by the
+// CPU tests (tests/native/host_core.cpp, tests/test_host_staging.py).
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "host_env.h"
+#include "pool.h"
+
+namespace sv {
+namespace {
+
+inline Pool& pool() {
+  // The GPU box's share is 16 CPUs; the staging copies saturate well below.
+  static Pool p((unsigned)std::min<size_t>(
+      env_size("SV_HOST_THREADS", std::min(8u, std::max(2u, std::thread::hardware_concurrency()))), 64));
+  return p;
+}
+// The pool a pack runs on: a device slot's own workers inside a multi-slot
+// call (shard), else the shared pool.
+inline thread_local Pool* t_pack_pool = nullptr;
+inline thread_local size_t t_pack_parts = 0;  // (multi-slot calls: this slot's share of the CPUs; 0: no cap)
+inline Pool& pack_pool() { return t_pack_pool ? *t_pack_pool : pool(); }
+
+inline size_t stage_chunk() {
+  static const size_t c = std::max<size_t>(1024, env_size("SV_STAGE_CHUNK", (size_t)1 << 18));
+  return c;
+}
+// Pipeline fill: the first R chunks of a multi-chunk batch grow geometrically
+// (chunk / 2^R, ..., chunk / 2), so the first kernel starts after packing and
+// copying a small chunk instead of a whole one.  SV_STAGE_RAMP = R (default
+// 2: chunk/4 then chunk/2; 0: equal chunks).
+inline size_t stage_ramp_steps() {
+  static const size_t r = std::min<size_t>(env_size("SV_STAGE_RAMP", 2), 8);
+  return r;
+}
+inline bool stage_ramp() { return stage_ramp_steps() != 0; }
+inline size_t chunk_len(size_t c, size_t chunk, size_t left) {
+  size_t m = chunk;
+  const size_t r = stage_ramp_steps();
+  if (c < r) m = std::max<size_t>(1024, chunk >> (r - c));
+  return std::min(m, left);
+}
+
+// A batch in host memory: contiguous SoA arrays (pk n x 32, sig n x 64,
+// messages by offset/length or fixed stride), or pointer arrays (gather).
+struct HostIn {
+  const uint8_t* pk = nullptr;
+  const uint8_t* sig = nullptr;
+  const uint8_t* msg = nullptr;
+  const uint64_t* off = nullptr;
+  const uint32_t* len = nullptr;
+  uint32_t fixed = 0;  // != 0: message i = msg + i * fixed, or msg + off[i] when off is set (uniform lengths)
+  const uint8_t* const* ppk = nullptr;  // gather form (ppk != nullptr)
+  const uint8_t* const* psig = nullptr;
+  const uint8_t* const* pmsg = nullptr;
+
+  static HostIn soa(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, const uint64_t* off,
+                    const uint32_t* len) {
+    HostIn in;
+    in.pk = pk;
+    in.sig = sig;
+    in.msg = msg;
+    in.off = off;
+    in.len = len;
+    return in;
+  }
+  static HostIn fixed_len(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, uint32_t len) {
+    HostIn in = soa(pk, sig, msg, nullptr, nullptr);
+    in.fixed = len;
+    return in;
+  }
+  static HostIn gathered(const uint8_t* const* pk, const uint8_t* const* sig, const uint8_t* const* msg,
+                         const uint32_t* len) {
+    HostIn in;
+    in.ppk = pk;
+    in.psig = sig;
+    in.pmsg = msg;
+    in.len = len;
+    return in;
+  }
+
+  bool gather() const { return ppk != nullptr; }
+  uint32_t mlen(size_t i) const { return fixed ? fixed : len[i]; }
+  const uint8_t* pkp(size_t i) const { return gather() ? ppk[i] : pk + 32 * i; }
+  const uint8_t* sigp(size_t i) const { return gather() ? psig[i] : sig + 64 * i; }
+  const uint8_t* msgp(size_t i) const {
+    if (gather()) return pmsg[i];
+    return off ? msg + off[i] : msg + i * (size_t)fixed;
+  }
+  // the slice [lo, ...) as a batch of its own
+  HostIn sub(size_t lo) const {
+    HostIn s = *this;
+    if (gather()) {
+      s.ppk += lo;
+      s.psig += lo;
+      s.pmsg += lo;
+      s.len += lo;
+    } else {
+      s.pk += 32 * lo;
+      s.sig += 64 * lo;
+      if (off) {
+        s.off += lo;
+        if (len) s.len += lo;
+      } else {
+        s.msg += lo * (size_t)fixed;
+      }
+    }
+    return s;
+  }
+};
+
+// Pinned image of m signatures starting at `lo`:
+//   pk (32 m) | sig (64 m) | fixed: msgs (m L)   or   var: off (8 m) | len (4 m) | packed msgs
+// (pk, sig and a fixed-length message block stay 16-byte aligned).
+struct Image {
+  size_t o_sig, o_off, o_len, o_msg, bytes;
+  bool var;
+};
+
+inline Image image_of(const HostIn& in, size_t lo, size_t m, size_t* msg_total) {
+  Image im;
+  im.var = in.fixed == 0;
+  size_t total = 0;
+  if (!im.var) total = m * (size_t)in.fixed;
+  else
+    for (size_t i = 0; i < m; ++i) total += in.len[lo + i];
+  im.o_sig = 32 * m;
+  im.o_off = 96 * m;
+  im.o_len = im.o_off + 8 * m;
+  im.o_msg = im.var ? im.o_len + 4 * m : im.o_off;
+  im.bytes = im.o_msg + std::max<size_t>(total, 1);
+  *msg_total = total;
+  return im;
+}
+
+// sv_launch_verify's message mode of an image: 0 32-byte messages at stride 32
+// (read with 16-byte loads: `aligned`), 1 by offset and length, 2 fixed stride.
+inline int verify_mode(bool var, uint32_t fixed, bool aligned = true) {
+  return var ? 1 : (fixed == 32 && aligned ? 0 : 2);
+}
+
+// Packing [lo, lo + m) into h (layout `im`): the message offsets first, then
+// rows [r0, r1) of the chunk, in parallel for large ranges.
+// (rows [r0, r1), the first at message offset pos; returns the offset past r1)
+inline uint64_t pack_offsets(const HostIn& in, size_t lo, size_t r0, size_t r1, uint64_t pos, const Image& im,
+                             uint8_t* h) {
+  uint64_t* offs = (uint64_t*)(h + im.o_off);
+  if (im.var) {
+    for (size_t i = r0; i < r1; ++i) {
+      offs[i] = pos;
+      pos += in.len[lo + i];
+    }
+  }
+  return pos;
+}
+// kPart: bytes per helper task, pack_part() or 1 MB when 0 (a keyed batch's pieces take
+// smaller ones: the first verify launch waits for the last piece)
+inline void pack_rows(const HostIn& in, size_t lo, size_t r0, size_t r1, const Image& im, uint8_t* h,
+                      size_t kPart = 0) {
+  const uint64_t* offs = (const uint64_t*)(h + im.o_off);
+  const size_t m = r1 - r0;
+  const size_t est = im.bytes / std::max<size_t>(1, (im.o_sig / 32)) * m;  // (bytes of these rows, roughly)
+  if (kPart == 0) kPart = est >= (2u << 20) ? pack_part() : (1u << 20);
+  Pool& pp = pack_pool();
+  const size_t parts = pack_parts(pp.size(), t_pack_parts, est, kPart);
+  pp.run(parts, [&](size_t t) {
+    const size_t a = r0 + m * t / parts, b = r0 + m * (t + 1) / parts;
+    if (a == b) return;
+    const PackCopy cp;
+    if (!in.gather()) {
+      cp(h + 32 * a, in.pk + 32 * (lo + a), 32 * (b - a));
+      cp(h + im.o_sig + 64 * a, in.sig + 64 * (lo + a), 64 * (b - a));
+      if (!im.var && !in.off) {
+        cp(h + im.o_msg + a * (size_t)in.fixed, in.msg + (lo + a) * (size_t)in.fixed, (b - a) * (size_t)in.fixed);
+        return;
+      }
+      if (!im.var) {  // (uniform lengths, found by offset: packed at the fixed stride)
+        for (size_t i = a; i < b; ++i) cp(h + im.o_msg + i * (size_t)in.fixed, in.msg + in.off[lo + i], in.fixed);
+        return;
+      }
+    } else {
+      for (size_t i = a; i < b; ++i) {
+        cp(h + 32 * i, in.ppk[lo + i], 32);
+        cp(h + im.o_sig + 64 * i, in.psig[lo + i], 64);
+      }
+      if (!im.var) {
+        for (size_t i = a; i < b; ++i) cp(h + im.o_msg + i * (size_t)in.fixed, in.pmsg[lo + i], in.fixed);
+        return;
+      }
+    }
+    std::memcpy(h + im.o_len + 4 * a, in.len + lo + a, 4 * (b - a));
+    for (size_t i = a; i < b; ++i) {
+      const uint32_t l = in.len[lo + i];
+      if (l) std::memcpy(h + im.o_msg + offs[i], in.msgp(lo + i), l);
+    }
+  });
+}
+inline void pack(const HostIn& in, size_t lo, size_t m, const Image& im, uint8_t* h) {
+  pack_offsets(in, lo, 0, m, 0, im, h);
+  pack_rows(in, lo, 0, m, im, h);
+}
+// A one-chunk keyed batch of at least kKeyPieceMin rows sends its keys up in
+// pieces (key_pieces): the caller's cache walk starts on the first piece while
+// later ones are packed, copied and hashed.  The first piece is kKeyPieceFirst
+// rows, so the walk starts as early as it can; each later piece is twice the
+// one before, at most kKeyPieceMax rows (a piece costs ~10 HIP calls on this
+// thread: fewer pieces bring the last one, and the verify launch behind it,
+// forward).
+constexpr size_t kKeyPieceMin = 8192, kKeyPieceFirst = 2048, kKeyPieceMax = 1 << 15;
+// Row bounds of the pieces of an m-row batch: b[0] = 0 < b[1] < ... < b[P] = m.
+inline std::vector<size_t> key_pieces(size_t m) {
+  if (m < kKeyPieceMin) return {0, m};
+  std::vector<size_t> b{0};
+  for (size_t len = kKeyPieceFirst; b.back() < m; len = std::min(2 * len, kKeyPieceMax))
+    b.push_back(m - b.back() < len + len / 2 ? m : b.back() + len);  // (no runt last piece)
+  return b;
+}
+
+// Do the keys of a host batch repeat?  A sample of up to 4096 evenly spaced
+// rows: with s sampled of n and d repeats among them, K distinct keys give
+// d ~ s^2 / 2K, so K <= n / 2 (each key signs twice on average) reads as
+// d * n >= s^2 (exact when s = n: n - d <= n / 2).
+inline bool repeated_keys(const HostIn& in, size_t n) {
+  const size_t s = std::min<size_t>(n, 4096);
+  if (s < 2) return false;
+  constexpr size_t kSet = 8192;
+  std::vector<const uint8_t*> set(kSet, nullptr);
+  size_t d = 0;
+  for (size_t k = 0; k < s; ++k) {
+    const uint8_t* pk = in.pkp(k * n / s);
+    uint64_t h;
+    std::memcpy(&h, pk, 8);
+    h *= 0x9E3779B97F4A7C15ull;
+    for (size_t j = (size_t)(h >> 51) & (kSet - 1);; j = (j + 1) & (kSet - 1)) {
+      if (!set[j]) {
+        set[j] = pk;
+        break;
+      }
+      if (std::memcmp(set[j], pk, 32) == 0) {
+        ++d;
+        break;
+      }
+    }
+  }
+  return s == n ? 2 * (n - d) <= n : (uint64_t)d * n >= (uint64_t)s * s;
+}
+
+// A variable-length batch whose messages all have one length L > 0 (tx
+// contents hashes: every pair of a tx-set pre-pass) goes to the device as a
+// fixed-length batch: messages packed at stride L (found by their offsets
+// or pointers), no offset / length arrays in the image, and the kernels' fixed
+// modes instead of an offset read before each message (measured: 50-110 us per
+// call at 29k-50k signatures, tools/varlen_probe.py).  The scan stops at the
+// first other length.
+inline HostIn uniform_form(const HostIn& in, size_t n) {
+  HostIn u = in;
+  if (in.fixed || n == 0 || !in.len) return u;
+  const uint32_t L = in.len[0];
+  if (L == 0) return u;
+  for (size_t i = 1; i < n; ++i)
+    if (in.len[i] != L) return u;
+  u.fixed = L;
+  return u;
+}
+
+// sv_ed25519_verify_txbodies: a batch of bodies and their signatures (CSR).
+struct TxIn {
+  const uint8_t* nid;
+  const uint8_t* bodies;
+  const uint64_t* off;
+  const uint32_t* len;
+  const uint8_t* kind;
+  size_t nb;
+  const uint64_t* sb;
+  const uint8_t* pk;
+  const uint8_t* sig;
+};
+
+// Body bytes per staging chunk (SV_TXBODY_CHUNK_BYTES, default 64 MiB).
+inline size_t txbody_chunk_bytes() {
+  static const size_t b = std::max<size_t>(4096, env_size("SV_TXBODY_CHUNK_BYTES", (size_t)64 << 20));
+  return b;
+}
+inline size_t al16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// One staging chunk: bodies [b0, b1) and the signatures [s0, s1) of the slice
+// they own.  Pinned / device image:
+//   pk (32 m) | sig (64 m) | body_off (8 k) | sig_begin (8 (k + 1)) | body_len (4 k) | kind (k) | bodies
+// with every body 16-byte aligned (offsets relative to the body section) and
+// sig_begin relative to s0.
+struct TxChunk {
+  size_t b0, b1, s0, s1;
+  size_t body_bytes;  // the aligned body section
+  size_t o_sig, o_off, o_sb, o_len, o_kind, o_body, bytes;
+};
+
+// The chunks of a slice: bodies [B0, B1), signatures [lo, hi) (a body's range
+// clipped to the slice).  A chunk is a run of whole bodies of at most max_s
+// signatures and max_b body bytes; a body over either bound is a chunk alone.
+inline std::vector<TxChunk> tx_plan(const TxIn& in, size_t B0, size_t B1, size_t lo, size_t hi, size_t max_s,
+                                    size_t max_b) {
+  auto cb = [&](size_t t) { return (size_t)std::min<uint64_t>(std::max<uint64_t>(in.sb[t], lo), hi); };
+  std::vector<TxChunk> out;
+  size_t t = B0;
+  while (t < B1) {
+    TxChunk c{};
+    c.b0 = t;
+    c.s0 = cb(t);
+    size_t bytes = 0;
+    do {
+      bytes += al16(in.len[t]);
+      ++t;
+    } while (t < B1 && cb(t + 1) - c.s0 <= max_s && bytes + al16(in.len[t]) <= max_b);
+    c.b1 = t;
+    c.s1 = cb(t);
+    c.body_bytes = bytes;
+    const size_t m = c.s1 - c.s0, k = c.b1 - c.b0;
+    c.o_sig = 32 * m;
+    c.o_off = 96 * m;
+    c.o_sb = c.o_off + 8 * k;
+    c.o_len = c.o_sb + 8 * (k + 1);
+    c.o_kind = c.o_len + 4 * k;
+    c.o_body = al16(c.o_kind + k);
+    c.bytes = c.o_body + std::max<size_t>(bytes, 16);
+    out.push_back(c);
+  }
+  return out;
+}
+
+inline void tx_pack(const TxIn& in, const TxChunk& c, size_t lo, size_t hi, uint8_t* h) {
+  const size_t m = c.s1 - c.s0, k = c.b1 - c.b0;
+  uint64_t* offs = (uint64_t*)(h + c.o_off);
+  uint64_t* sb = (uint64_t*)(h + c.o_sb);
+  size_t pos = 0;
+  for (size_t i = 0; i < k; ++i) {
+    offs[i] = pos;
+    pos += al16(in.len[c.b0 + i]);
+  }
+  for (size_t i = 0; i <= k; ++i)
+    sb[i] = std::min<uint64_t>(std::max<uint64_t>(in.sb[c.b0 + i], lo), hi) - c.s0;
+  std::memcpy(h + c.o_len, in.len + c.b0, 4 * k);
+  std::memcpy(h + c.o_kind, in.kind + c.b0, k);
+  Pool& pp = pack_pool();
+  const size_t parts = pack_parts(pp.size(), t_pack_parts, 96 * m + c.body_bytes, pack_part());
+  pp.run(parts, [&](size_t p) {
+    const PackCopy cp;
+    const size_t a = m * p / parts, b = m * (p + 1) / parts;
+    if (b > a) {
+      cp(h + 32 * a, in.pk + 32 * (c.s0 + a), 32 * (b - a));
+      cp(h + c.o_sig + 64 * a, in.sig + 64 * (c.s0 + a), 64 * (b - a));
+    }
+    for (size_t i = k * p / parts; i < k * (p + 1) / parts; ++i) {
+      const uint32_t l = in.len[c.b0 + i];
+      if (l) cp(h + c.o_body + offs[i], in.bodies + in.off[c.b0 + i], l);
+    }
+  });
+}
+}  // namespace
+}  // namespace sv

@@ -1,5 +1,5 @@
 // Per-key tables of the throughput path: layout and launch parameters shared
-// by the kernels (sv_kernels.hip) and the host side (sv_api.cpp).  The design
+// by the kernels (sv_kernels.hip) and the host side (bulk.h kt_prepare).  The design
 // is described in sv_kernels.hip above sv_keyslot_kernel.
 #pragma once
 

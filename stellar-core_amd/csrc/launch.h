@@ -1,0 +1,64 @@
+// The one declaration of every extern "C" launcher and size query that
+// crosses between the kernel files (sv_kernels.hip, sv_comb.hip, sv_hash.hip,
+// sv_txhash.hip), sv_cpu.cpp and the engine (sv_api.cpp and its modules).
+// Included by the callers and by every definer, so a changed parameter list
+// is a compile error instead of arguments corrupted at run time.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+#include "keytab.h"
+
+extern "C" {
+
+// Argument check of the host-array tx-body entry points (sv_cpu.cpp).
+int sv_txbodies_check(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                      const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies, const uint64_t* sig_begin,
+                      const uint8_t* pk, const uint8_t* sig, size_t n, const uint8_t* verdict);
+
+}  // extern "C"
+
+// The launchers take HIP types: compiled only where the HIP runtime headers
+// are on the include path (sv_cpu.cpp is built without them).
+#if defined(__HIP_PLATFORM_AMD__) || defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+
+extern "C" {
+
+// throughput and cold-key latency paths, signing (sv_kernels.hip)
+size_t sv_ws_bytes(unsigned grid, uint64_t cap);
+size_t sv_verify_ws_bytes(int path, unsigned grid, uint64_t n);
+size_t sv_btab_bytes(void);
+int sv_block_threads(void);
+hipError_t sv_launch_btab_init(uint32_t* d_btab, hipStream_t s);
+int sv_occupancy_blocks_per_cu(void);
+hipError_t sv_launch_verify(int mode, int path, unsigned grid, const void* pk, const void* sig, const void* msg,
+                            const uint64_t* off, const uint32_t* len, uint32_t fixed_len, uint64_t n,
+                            void* verdict, void* bitmap, void* ws, const void* btab, uint32_t dbg, int share,
+                            const sv_ktparams* kt, uint32_t* status, hipStream_t s);
+int sv_share_blocks_per_cu(void);
+size_t sv_key_table_entry_bytes(void);
+uint64_t sv_plan_chunk_max(uint64_t n);
+hipError_t sv_launch_sign(unsigned grid, const void* seed, const void* msg, uint64_t n, void* pk, void* sig,
+                          void* ws, const void* btab, hipStream_t s);
+// cache keys and SHA-256 (sv_hash.hip), tx contents hashes (sv_txhash.hip)
+hipError_t sv_launch_hash(int kind, unsigned max_blocks, const void* pk, const void* sig, const void* msg,
+                          const uint64_t* off, const uint32_t* len, uint32_t fixed_len, uint64_t n, void* out,
+                          hipStream_t s);
+hipError_t sv_launch_txhash(unsigned max_blocks, const uint8_t* nid, const void* bodies, const uint64_t* off,
+                            const uint32_t* len, const uint8_t* kind, uint64_t n_bodies, const uint64_t* sig_begin,
+                            uint64_t n, void* msg, void* digests, hipStream_t s);
+// warm-key latency path (sv_comb.hip)
+size_t sv_comb_btab_bytes(void);
+size_t sv_key_slot_bytes(void);
+hipError_t sv_launch_comb_btab(uint32_t* d_ctab, hipStream_t s);
+hipError_t sv_launch_keytab(const void* d_pks, const uint32_t* d_slots, uint32_t nkeys, uint32_t* d_ktab,
+                            uint32_t* d_kstat, hipStream_t s);
+int sv_comb_spw(uint64_t n, int cus);
+hipError_t sv_launch_comb(int mode, int spw, const void* pk, const void* sig, const void* msg, const uint64_t* off,
+                          const uint32_t* len, uint32_t fixed_len, uint64_t n, void* verdict, const uint32_t* kslot,
+                          const uint32_t* ktab, const uint32_t* kstat, const uint32_t* ctab, hipStream_t s);
+
+}  // extern "C"
+#endif

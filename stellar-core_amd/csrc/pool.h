@@ -1,5 +1,5 @@
-// Persistent helper-thread pool shared by the engine's host side (staging,
-// multi-slot fan-out: sv_api.cpp) and the C++ mirror (parallel hashing and
+// Persistent helper-thread pool shared by the engine's host side (staging:
+// host_image.h; multi-slot fan-out: sv_api.cpp) and the C++ mirror (parallel hashing and
 // CPU-path batches: host/).
 #pragma once
 
@@ -23,7 +23,7 @@ namespace sv {
 class Pool {
  public:
   // init (optional) runs first on every helper thread (a device slot's
-  // workers pin themselves to the GPU's NUMA node there: sv_api.cpp)
+  // workers pin themselves to the GPU's NUMA node there: sv_api.cpp slot_pool)
   explicit Pool(unsigned threads, const std::function<void()>& init = {}) {
     for (unsigned i = 0; i < threads; ++i)
       th_.emplace_back([this, init] {

@@ -1,7 +1,7 @@
 // gfx950 kernels of the warm-key latency path (layout: comb.h).
 //
 // Per signature, libsodium 1.0.18 crypto_sign_verify_detached (the call
-// stellar-core makes at /root/reference/src/crypto/SecretKey.cpp:461-463)
+// stellar-core makes at src/crypto/SecretKey.cpp:461-463)
 // accepts iff
 //   (1) S < L, (2) R not small-order, (3)-(5) A canonical, not small-order and
 //   decodable, and (8) encode([S]B - [h]A) == R, h = SHA-512(R||A||M) mod L.
@@ -35,6 +35,7 @@
 #include <hip/hip_runtime.h>
 
 #include "comb_core.h"
+#include "launch.h"
 #include "quad.h"
 #include "sv_kparams.h"
 

@@ -14,7 +14,7 @@
 // caller re-runs the batch here -- and a single verifySig is cheaper here than
 // a GPU round trip.  Reference semantics: libsodium 1.0.18
 // crypto_sign_verify_detached as called by PubKeyUtils::verifySig
-// (/root/reference/src/crypto/SecretKey.cpp:461-463).  Not the oracle: nothing
+// (src/crypto/SecretKey.cpp:461-463).  Not the oracle: nothing
 // under oracle/ is compiled or linked here.
 #define SV_LB_BITS 8
 // field arithmetic in radix 2^51 with 128-bit products (fe51_host.h): what
@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../../include/stellar_sigverify.h"
+#include "launch.h"
 
 namespace {
 
@@ -111,7 +112,7 @@ int sv_ed25519_verify_batch_cpu(const uint8_t* pk, const uint8_t* sig, const uin
 }
 
 // Argument check shared by the three sv_ed25519_verify_txbodies* host-array
-// entry points (sv_api.cpp calls it too): SV_OK or SV_ERR_INVALID_ARG.
+// entry points (declared in launch.h: sv_api.cpp calls it too): SV_OK or SV_ERR_INVALID_ARG.
 int sv_txbodies_check(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
                       const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies, const uint64_t* sig_begin,
                       const uint8_t* pk, const uint8_t* sig, size_t n, const uint8_t* verdict) {

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "hash_dev.h"
+#include "launch.h"
 
 #define SV_HBLOCK 256
 

@@ -22,6 +22,7 @@
 #include "quad.h"
 #include "sv_kparams.h"
 #include "keytab.h"
+#include "launch.h"
 
 #define SV_BLOCK 256
 #define SV_WAVES_PER_SIMD 2
@@ -112,7 +113,7 @@ static_assert(16 + 2 * SV_LB_DIGITS + 2 <= 4 * SV_REC_QUADS, "digit record size"
 // the wave decodes inline as without tables), and the main kernel reads
 // table_A from the entry.  Decoding is deterministic, so verdicts do not
 // depend on the tables.  Entries are never modified after their build; the
-// host clears the claim words when the claims reach `limit` (sv_api.cpp).
+// host clears the claim words when the claims reach `limit` (bulk.h kt_prepare).
 static_assert(SV_KT_TQUADS == SV_ATAB_ENTRIES * SV_LTAB_QUADS, "key-table entry layout");
 
 struct sv_cparams {

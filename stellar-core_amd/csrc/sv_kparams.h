@@ -23,7 +23,7 @@ struct sv_kparams {
   // wait ran out) writes a nonzero SV_KFAIL_* code here; the host, which zeroed
   // it before the launch, then returns an error for the whole batch instead of
   // the (fail-closed) rejects: an error is never a reject
-  // (include/stellar_sigverify.h; /root/reference/src/crypto/SecretKey.cpp:461-466
+  // (include/stellar_sigverify.h; src/crypto/SecretKey.cpp:461-466
   // caches every verdict it is given).
   uint32_t* status;
 };

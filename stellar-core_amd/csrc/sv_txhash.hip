@@ -13,6 +13,7 @@
 // ("Transaction bodies").
 #include <hip/hip_runtime.h>
 
+#include "launch.h"
 #include "txhash.h"
 
 #define SV_TXBLOCK 256

@@ -2,7 +2,7 @@
 //
 // Accept/reject is bit-exact with libsodium 1.0.18 crypto_sign_verify_detached,
 // the function stellar-core's PubKeyUtils::verifySig calls on a cache miss
-// (/root/reference/src/crypto/SecretKey.cpp:461-463).  Steps, in libsodium's
+// (src/crypto/SecretKey.cpp:461-463).  Steps, in libsodium's
 // order (all evaluated branch-free per lane; the verdict is their AND):
 //   (1) S < L                              sc_is_canonical
 //   (2) R not one of 7 small-order encodings (bit 255 masked)

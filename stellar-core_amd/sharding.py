@@ -15,7 +15,7 @@ import numpy as np
 
 
 def shard_bounds(n: int, world: int, rank: int):
-    """Contiguous slice of rank `rank` (same formula as sv_api.cpp verify_host)."""
+    """Contiguous slice of rank `rank` (same formula as sv_api.cpp shard)."""
     if world < 1 or not (0 <= rank < world):
         raise ValueError("bad world/rank")
     return rank * n // world, (rank + 1) * n // world

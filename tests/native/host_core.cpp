@@ -514,3 +514,108 @@ extern "C" int hc_keyindex_fuzz(uint64_t seed, int cap, int ops, int universe) {
   return (int)ix.size() == (int)model.size() ? 0 : 9;
 }
 
+// ---------------------------------------------------------------------------
+// Host staging (stellar-core_amd/csrc/host_image.h): the engine's packers and
+// planners behind flat entry points, for tests/test_host_staging.py to check
+// against the documented layouts.
+#include "../../stellar-core_amd/csrc/host_image.h"
+
+// A batch as the tests hold it: SoA arrays; fixed != 0: messages at that
+// stride; gather: handed to the engine as pointer arrays built here; uniform:
+// through uniform_form first; sub: the engine sees sub(sub) of it.
+struct hs_batch {
+  const uint8_t* pk;
+  const uint8_t* sig;
+  const uint8_t* msg;
+  const uint64_t* off;
+  const uint32_t* len;
+  uint64_t n;
+  uint32_t fixed, gather, uniform;
+  uint64_t sub;
+};
+namespace {
+struct HsIn {
+  std::vector<const uint8_t*> ppk, psig, pmsg;
+  sv::HostIn in;
+  explicit HsIn(const hs_batch& b) {
+    if (b.gather) {
+      for (uint64_t i = 0; i < b.n; ++i) {
+        ppk.push_back(b.pk + 32 * i);
+        psig.push_back(b.sig + 64 * i);
+        pmsg.push_back(b.msg ? b.msg + b.off[i] : nullptr);
+      }
+      in = sv::HostIn::gathered(ppk.data(), psig.data(), pmsg.data(), b.len);
+    } else if (b.fixed) {
+      in = sv::HostIn::fixed_len(b.pk, b.sig, b.msg, b.fixed);
+    } else {
+      in = sv::HostIn::soa(b.pk, b.sig, b.msg, b.off, b.len);
+    }
+    if (b.uniform) in = sv::uniform_form(in, b.n);
+    if (b.sub) in = in.sub(b.sub);
+  }
+};
+sv::TxIn hs_txin(const uint8_t* bodies, const uint64_t* off, const uint32_t* len, const uint8_t* kind, size_t nb,
+                 const uint64_t* sb, const uint8_t* pk, const uint8_t* sig) {
+  return sv::TxIn{nullptr, bodies, off, len, kind, nb, sb, pk, sig};
+}
+static_assert(sizeof(sv::TxChunk) == 12 * sizeof(uint64_t), "hs_tx_plan hands TxChunk out as 12 words");
+}  // namespace
+
+extern "C" {
+
+// out: o_sig, o_off, o_len, o_msg, bytes, var, msg_total, the form's fixed length
+void hs_image(const hs_batch* b, uint64_t lo, uint64_t m, uint64_t out[8]) {
+  HsIn h(*b);
+  size_t total = 0;
+  const sv::Image im = sv::image_of(h.in, lo, m, &total);
+  const uint64_t v[8] = {im.o_sig, im.o_off, im.o_len, im.o_msg, im.bytes, im.var ? 1u : 0u, total, h.in.fixed};
+  memcpy(out, v, sizeof(v));
+}
+void hs_pack(const hs_batch* b, uint64_t lo, uint64_t m, uint8_t* dst) {
+  HsIn h(*b);
+  size_t total = 0;
+  sv::pack(h.in, lo, m, sv::image_of(h.in, lo, m, &total), dst);
+}
+// The early-keys path's packing (bulk.h host_slice_locked): per key_pieces
+// piece its offsets, the end offset at the piece's upper bound, its rows.
+void hs_pack_pieces(const hs_batch* b, uint64_t m, uint64_t part, uint8_t* dst) {
+  HsIn h(*b);
+  size_t total = 0;
+  const sv::Image im = sv::image_of(h.in, 0, m, &total);
+  const std::vector<size_t> pb = sv::key_pieces(m);
+  uint64_t pos = 0;
+  for (size_t k = 0; k + 1 < pb.size(); ++k) {
+    pos = sv::pack_offsets(h.in, 0, pb[k], pb[k + 1], pos, im, dst);
+    if (im.var && pb[k + 1] < m) ((uint64_t*)(dst + im.o_off))[pb[k + 1]] = pos;
+    sv::pack_rows(h.in, 0, pb[k], pb[k + 1], im, dst, part);
+  }
+}
+int hs_key_pieces(uint64_t m, uint64_t* out, int cap) {
+  const std::vector<size_t> pb = sv::key_pieces(m);
+  for (size_t i = 0; i < pb.size() && (int)i < cap; ++i) out[i] = pb[i];
+  return (int)pb.size();
+}
+uint64_t hs_chunk_len(uint64_t c, uint64_t chunk, uint64_t left) { return sv::chunk_len(c, chunk, left); }
+uint32_t hs_uniform_fixed(const uint32_t* len, uint64_t n) {
+  return sv::uniform_form(sv::HostIn::soa(nullptr, nullptr, nullptr, nullptr, len), n).fixed;
+}
+int hs_repeated_keys(const uint8_t* pk, uint64_t n) {
+  return sv::repeated_keys(sv::HostIn::soa(pk, nullptr, nullptr, nullptr, nullptr), n) ? 1 : 0;
+}
+// out: per chunk b0, b1, s0, s1, body_bytes, o_sig, o_off, o_sb, o_len, o_kind, o_body, bytes
+int hs_tx_plan(const uint32_t* len, const uint64_t* sb, uint64_t B0, uint64_t B1, uint64_t lo, uint64_t hi,
+               uint64_t max_s, uint64_t max_b, uint64_t* out, int cap) {
+  const sv::TxIn in = hs_txin(nullptr, nullptr, len, nullptr, 0, sb, nullptr, nullptr);
+  const std::vector<sv::TxChunk> plan = sv::tx_plan(in, B0, B1, lo, hi, max_s, max_b);
+  for (size_t i = 0; i < plan.size() && (int)i < cap; ++i) memcpy(out + 12 * i, &plan[i], sizeof(sv::TxChunk));
+  return (int)plan.size();
+}
+void hs_tx_pack(const uint8_t* bodies, const uint64_t* off, const uint32_t* len, const uint8_t* kind, uint64_t nb,
+                const uint64_t* sb, const uint8_t* pk, const uint8_t* sig, const uint64_t chunk[12], uint64_t lo,
+                uint64_t hi, uint8_t* dst) {
+  sv::TxChunk c;
+  memcpy(&c, chunk, sizeof(c));
+  sv::tx_pack(hs_txin(bodies, off, len, kind, nb, sb, pk, sig), c, lo, hi, dst);
+}
+
+}  // extern "C"

@@ -171,7 +171,7 @@ def test_small_cache_evicts_exactly(sv, gpu, oracle):
 @pytest.mark.parametrize("cap", [64, 8192])
 def test_concurrent_lane_batches(sv, gpu, oracle, cap):
     """Batches from several host threads at once: the lane plans and launches
-    them one at a time but runs up to two side by side (sv_api.cpp LatCtx).
+    them one at a time but runs up to two side by side (engine_state.h LatCtx, latlane.h lat_slice).
     With a 64-key cache under a 600-key workload every batch evicts and queues
     table builds while the other context's comb kernel reads the tables; with a
     large one the same sets run warm side by side.  Every verdict exact."""

@@ -4,7 +4,7 @@ batch run on the same GPU (tests/isolation_load.py).  Every verdict exact;
 bulk launches made while latency batches are live run in shared mode (a
 workgroup slot per CU left free, csrc/sv_kernels.hip sv_launch_verify) and the
 latency lane has its own high-priority stream, staging and mutex
-(csrc/sv_api.cpp LatLane).  The 1k batches' p99 under load is recorded
+(csrc/engine_state.h LatLane, csrc/latlane.h).  The 1k batches' p99 under load is recorded
 (SV_ISOLATION_OUT, profiles/) and held to a loose bound, 1 ms by default
 (SV_ISOLATION_P99_MS=x overrides): the round-4 runs measured 0.21-0.23 ms; a
 lane copy queued behind bulk uploads again (0.6-0.86 ms before round 4) comes

@@ -1,4 +1,4 @@
-"""GPU parity of medium one-chunk host batches (csrc/sv_api.cpp host_slice_locked):
+"""GPU parity of medium one-chunk host batches (csrc/bulk.h host_slice_locked):
 the image read in place from mapped memory, the verdicts written in place
 (SV_BULK_ZC_OUT), on the medium geometry (quad) and the one-lane geometry.
 
@@ -108,7 +108,7 @@ def test_medium_variable_length_fixture_rows(sv, dev, golden, geom):
 @pytest.mark.parametrize("n", [1000, 12289, 29217, 50000])
 def test_uniform_length_variable_batches(sv, dev, signed, n):
     """A variable-length call whose messages all have one length goes to the
-    device as a fixed-length batch (sv_api.cpp uniform_form): messages found
+    device as a fixed-length batch (host_image.h uniform_form): messages found
     by their offsets (here shuffled, and rows sharing one message as a tx's
     pairs share its contents hash) and packed at a fixed stride."""
     P, S, M = signed

@@ -2,7 +2,7 @@
 """Developer tool: the two kernel paths over medium batch
 sizes, kernel-only (HIP events around the launches, device-resident input) and
 per call (host API from pageable arrays), to set the auto crossover
-(kQuickMax, csrc/sv_api.cpp) from measurements on the current kernels.
+(kQuickMax, csrc/engine_state.h) from measurements on the current kernels.
 
   throughput  one lane per signature (prep + persistent main kernel; SV_DBG_NO_QUAD)
   quad        one signature per quad of lanes (sv_quad_kernel; SV_DBG_QUAD)
