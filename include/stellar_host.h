@@ -205,7 +205,17 @@ int svh_check_envelopes(const svh_envelope* env, size_t n, const svh_decorated_s
  *               payload pairs (their own message) are a second batch.  An
  *               engine error re-runs on sv_ed25519_verify_txbodies_cpu
  *               (counted in svh_engine_stats.fallbacks).
- *   prefetch 2  SVH_ERR_INVALID_ARG (no keyed, cache-seeding body form) */
+ *   prefetch 2  SVH_ERR_INVALID_ARG (no keyed, cache-seeding body form)
+ *   prefetch 3  the catchup form with the pairing on the device: each
+ *               transaction's 64-byte signatures (with their hints) and its
+ *               ed25519 signer keys go up as they are, ONE
+ *               sv_ed25519_verify_txbodies_hinted call hashes the bodies, pairs
+ *               signatures with keys by hint and verifies the pairs; the host
+ *               does no hint comparison for them.  Signed-payload pairs are
+ *               still enumerated on the host (their hint is XORed, their
+ *               message their own) and stay the second batch.  An engine error
+ *               re-runs on sv_ed25519_verify_txbodies_hinted_cpu (counted in
+ *               svh_engine_stats.fallbacks).  Results and hashes as prefetch 1. */
 typedef struct svh_envelope_body {
   uint64_t off;
   uint32_t len;
@@ -220,6 +230,20 @@ int svh_check_envelopes_bodies(const svh_envelope* env, size_t n, const svh_deco
                                uint64_t* prefetched_pairs, const uint8_t* network_id, const uint8_t* bodies,
                                const svh_envelope_body* body, uint8_t* contents_hash_out,
                                uint8_t* fee_bump_hash_out);
+
+/* Measurement aid (tools/txpairs_bench.py): bodies with their decorated
+ * signatures and candidate ed25519 keys, in the CSR layout of
+ * sv_ed25519_verify_txbodies_hinted, through SignatureBatchPrefetch's two body
+ * forms: hinted == 0 add() per body (the host's hint comparison and pair
+ * copies) then runBodies (ONE sv_ed25519_verify_txbodies call); hinted != 0
+ * addHinted() then runBodiesHinted.  ms[0]: the add calls, ms[1]: the run call
+ * (building each body's signature / signer objects is outside both);
+ * *pairs / *accepted: pairs verified and verdicts that were 1. */
+int svh_bench_prefetch_bodies(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                              const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                              const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig,
+                              const uint64_t* key_begin, const uint8_t* key, int hinted, double ms[2],
+                              uint64_t* pairs, uint64_t* accepted);
 
 typedef struct svh_mb_stats {
   uint64_t items, batches, flushed_by_size, flushed_by_deadline, max_batch;

@@ -289,6 +289,91 @@ int sv_ed25519_verify_txbodies_cpu(const uint8_t* network_id, const uint8_t* bod
                                    const uint64_t* sig_begin, const uint8_t* pk, const uint8_t* sig, size_t n,
                                    uint8_t* verdict, uint8_t* digests /* optional */, int threads);
 
+/* ---- Pairing by hint on the device --------------------------------------
+ * A transaction carries DecoratedSignature{hint[4], signature[64]} and the
+ * ledger supplies the candidate signer keys; which signature goes with which
+ * key is decided by the hint, the last four bytes of the key
+ * (SignatureUtils::doesHintMatch inside SignatureChecker::checkSignature).
+ * These entry points take what a transaction has and do the pairing on the
+ * device (csrc/sv_txpair.hip) between the contents hash and the verify launch.
+ *
+ *   bodies           as sv_ed25519_verify_txbodies
+ *   n_sigs sigs      hint (n_sigs x 4), sig (n_sigs x 64); body t owns
+ *                    signatures sig_begin[t] .. sig_begin[t+1]-1
+ *   n_keys keys      key (n_keys x 32): body t's candidate ed25519 keys are
+ *                    key_begin[t] .. key_begin[t+1]-1
+ *                    (both CSR arrays: n_bodies + 1 entries, non-decreasing,
+ *                    first 0, last the count; n_sigs, n_keys < 2^32)
+ *   pair_cap         entries the three pair output arrays hold
+ *   pair_begin       out, n_bodies + 1: body t's pairs are
+ *                    pair_begin[t] .. pair_begin[t+1]-1
+ *   pair_sig/key     out, global indices into sig / key
+ *   pair_verdict     out, the verdict for (key[pair_key[i]], sig[pair_sig[i]],
+ *                    contents hash of the body)
+ *   *n_pairs         out, the number of pairs
+ *   digests          optional, n_bodies x 32 bytes out
+ *
+ * A pair (s, k) exists iff s and k belong to the same body and hint[s] equals
+ * bytes 28..31 of key[k].  Pairs are ordered by body, then signature, then key,
+ * all ascending (a key listed twice in a body gives two pairs): the order is a
+ * function of the input only.  n_sigs == 0, n_keys == 0 or zero pairs are legal
+ * (digests are still produced; the pair arrays may be NULL when pair_cap == 0).
+ * If the batch has more pairs than pair_cap the call returns SV_ERR_PAIR_CAP
+ * with the exact number in *n_pairs; the pair outputs are then unspecified
+ * (verdicts are never partial).  sv_txbodies_pair_bound gives a capacity that
+ * always suffices.  Signatures of another length than 64 and signers that are
+ * not ed25519 keys never reach these calls.
+ *
+ * Host buffers: chunks of whole bodies bounded by signatures and keys
+ * (SV_STAGE_CHUNK each) and body bytes (SV_TXBODY_CHUNK_BYTES); per chunk the
+ * engine waits once for the chunk's pair count before it launches the verify,
+ * and packs the next chunk while that verify runs.  With opts->device == -1
+ * the bodies are sliced over the slots at the body boundaries nearest to equal
+ * shares of signatures (the minimum shard counts signatures); every body's
+ * pairs and digest come from one slot, slot g's pairs follow slot g-1's. */
+#define SV_ERR_PAIR_CAP (-8)
+/* sum over the bodies of (signatures x keys): a pair_cap that always suffices
+ * (0 for null arrays; saturates at SIZE_MAX) */
+size_t sv_txbodies_pair_bound(const uint64_t* sig_begin, const uint64_t* key_begin, size_t n_bodies);
+int sv_ed25519_verify_txbodies_hinted(const uint8_t* network_id /* 32 B */, const uint8_t* bodies,
+                                      const uint64_t* body_off, const uint32_t* body_len, const uint8_t* body_kind,
+                                      size_t n_bodies, const uint64_t* sig_begin, const uint8_t* hint,
+                                      const uint8_t* sig, size_t n_sigs, const uint64_t* key_begin,
+                                      const uint8_t* key, size_t n_keys, size_t pair_cap, uint64_t* pair_begin,
+                                      uint32_t* pair_sig, uint32_t* pair_key, uint8_t* pair_verdict, size_t* n_pairs,
+                                      uint8_t* digests /* optional, n_bodies x 32 */, const sv_opts* opts);
+/* Device-resident form: every array is device memory on `device` (d_hint
+ * 4-byte aligned; d_sig, d_key and the optional d_digests 16-byte aligned);
+ * network_id and n_pairs are host memory.  d_pair_bitmap (optional) is laid out
+ * as in sv_ed25519_verify_device over the n_pairs verdicts.  The number of
+ * pairs is only known on the device, so this form WAITS on `stream` once, for
+ * the count, after the hash and pairing kernels; it then enqueues the
+ * verification and returns without waiting for it (stream ordering as
+ * sv_ed25519_verify_device).  If the count exceeds pair_cap it returns
+ * SV_ERR_PAIR_CAP (*n_pairs exact) and enqueues nothing more.  With
+ * d_pair_verdict NULL (and no bitmap) the call stops after the pairing: the
+ * pairs and digests are produced, nothing is verified.  The device
+ * arrays are not validated: ranges are clamped to n_sigs / n_keys, kinds > 2
+ * hash as fee bumps. */
+int sv_ed25519_verify_txbodies_hinted_device(int device, const uint8_t* network_id /* host, 32 B */,
+                                             const void* d_bodies, const uint64_t* d_body_off,
+                                             const uint32_t* d_body_len, const uint8_t* d_body_kind, size_t n_bodies,
+                                             const uint64_t* d_sig_begin, const void* d_hint, const void* d_sig,
+                                             size_t n_sigs, const uint64_t* d_key_begin, const void* d_key,
+                                             size_t n_keys, size_t pair_cap, uint64_t* d_pair_begin,
+                                             uint32_t* d_pair_sig, uint32_t* d_pair_key, void* d_pair_verdict,
+                                             void* d_pair_bitmap, size_t* n_pairs /* host */, void* d_digests,
+                                             void* stream);
+/* The same contract on the engine's CPU path (what a caller runs when one of
+ * the two above returns an engine error; threads as sv_ed25519_verify_batch_cpu). */
+int sv_ed25519_verify_txbodies_hinted_cpu(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                          const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                          const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig,
+                                          size_t n_sigs, const uint64_t* key_begin, const uint8_t* key, size_t n_keys,
+                                          size_t pair_cap, uint64_t* pair_begin, uint32_t* pair_sig,
+                                          uint32_t* pair_key, uint8_t* pair_verdict, size_t* n_pairs,
+                                          uint8_t* digests /* optional */, int threads);
+
 /* ---- Warm-key latency path (csrc/comb.h, csrc/sv_comb.hip) ---------------
  * Each device slot keeps a bounded cache of per-public-key tables
  * ({0..8} * 16^j * (-A), 108 KiB per key) in HBM.  A latency-path host batch

@@ -55,7 +55,9 @@ SV_ERRORS = {
     -5: "SV_ERR_NOT_INIT",
     -6: "SV_ERR_ALIGN",
     -7: "SV_ERR_KERNEL",
+    -8: "SV_ERR_PAIR_CAP",
 }
+SV_ERR_PAIR_CAP = -8
 
 EXPORTED_SYMBOLS = (
     "sv_init", "sv_shutdown", "sv_device_count", "sv_last_error_string", "sv_version",
@@ -68,6 +70,8 @@ EXPORTED_SYMBOLS = (
     "sv_set_key_cache", "sv_key_cache_wait", "sv_key_cache_get_stats", "sv_set_key_tables",
     "sv_ed25519_verify_batch_gather_progress", "sv_host_feed_probe",
     "sv_ed25519_verify_txbodies", "sv_ed25519_verify_txbodies_device", "sv_ed25519_verify_txbodies_cpu",
+    "sv_ed25519_verify_txbodies_hinted", "sv_ed25519_verify_txbodies_hinted_device",
+    "sv_ed25519_verify_txbodies_hinted_cpu", "sv_txbodies_pair_bound",
 )
 
 # body kinds of the tx-body entry points (include/stellar_sigverify.h)
@@ -82,7 +86,14 @@ DBG_DROP_HANDOVER = 0x80
 
 
 class SigVerifyError(RuntimeError):
-    """A device/allocation error.  Never a reject: the batch is unverified."""
+    """A device/allocation error.  Never a reject: the batch is unverified.
+    code: the SV_ERR_* value (None when raised by the binding itself);
+    needed: for SV_ERR_PAIR_CAP, the exact number of pairs of the batch."""
+
+    def __init__(self, message, code=None, needed=None):
+        super().__init__(message)
+        self.code = code
+        self.needed = needed
 
 
 class sv_opts(ctypes.Structure):
@@ -164,6 +175,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.sv_ed25519_verify_txbodies_device.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp, vp,
                                                       vp, vp]
     lib.sv_ed25519_verify_txbodies_cpu.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp, vp, ctypes.c_int]
+    szp = ctypes.POINTER(ctypes.c_size_t)
+    hinted = [vp, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp]
+    lib.sv_ed25519_verify_txbodies_hinted.argtypes = hinted + [szp, vp, vp]
+    lib.sv_ed25519_verify_txbodies_hinted_cpu.argtypes = hinted + [szp, vp, ctypes.c_int]
+    lib.sv_ed25519_verify_txbodies_hinted_device.argtypes = [ctypes.c_int] + hinted + [vp, szp, vp, vp]
+    lib.sv_txbodies_pair_bound.argtypes = [vp, vp, sz]
+    lib.sv_txbodies_pair_bound.restype = sz
     _lib = lib
     return lib
 
@@ -398,6 +416,113 @@ def verify_txbodies_device(device: int, network_id, d_bodies: int, d_body_off: i
                                                  d_sig_begin or None, d_pk or None, d_sig or None, n,
                                                  d_verdict or None, d_bitmap or None, d_digests or None,
                                                  stream or None))
+
+
+def _csr(a, nb, what):
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.uint64).reshape(-1))
+    if a.shape[0] != nb + 1:
+        raise ValueError("%s must hold n_bodies + 1 entries" % what)
+    return a
+
+
+def txbodies_pair_bound(sig_begin, key_begin) -> int:
+    """Sum over the bodies of signatures x keys (sv_txbodies_pair_bound): a
+    pair_cap that always suffices."""
+    lib = load_library()
+    sb = np.ascontiguousarray(np.asarray(sig_begin, dtype=np.uint64).reshape(-1))
+    kb = _csr(key_begin, sb.shape[0] - 1, "key_begin")
+    return int(lib.sv_txbodies_pair_bound(_ptr(sb), _ptr(kb), sb.shape[0] - 1))
+
+
+def _hinted_args(network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, key_begin, key):
+    nid = np.ascontiguousarray(np.frombuffer(bytes(network_id), np.uint8))
+    if nid.size != 32:
+        raise ValueError("network_id must be 32 bytes")
+    hint, sig, key = _u8(hint, 4), _u8(sig, 64), _u8(key, 32)
+    ns, nk = sig.shape[0], key.shape[0]
+    if hint.shape[0] != ns:
+        raise ValueError("hint/sig row mismatch")
+    kind = np.ascontiguousarray(np.asarray(body_kind, dtype=np.uint8).reshape(-1))
+    nb = kind.shape[0]
+    bodies, off, ln = _var_msgs(bodies, body_off, body_len, nb)
+    sb, kb = _csr(sig_begin, nb, "sig_begin"), _csr(key_begin, nb, "key_begin")
+    for name, a, n in (("sig_begin", sb, ns), ("key_begin", kb, nk)):
+        if int(a[0]) != 0 or int(a[-1]) != n or (a[1:] < a[:-1]).any():
+            raise ValueError("%s must start at 0, not decrease and end at the row count" % name)
+    return nid, bodies, off, ln, kind, nb, sb, hint, sig, ns, kb, key, nk
+
+
+def _check_pairs(rc: int, n_pairs) -> None:
+    if rc == SV_ERR_PAIR_CAP:
+        msg = _lib.sv_last_error_string().decode(errors="replace") if _lib else ""
+        raise SigVerifyError("SV_ERR_PAIR_CAP: %s (the batch has %d pairs)" % (msg, n_pairs.value), rc,
+                             int(n_pairs.value))
+    _check(rc)
+
+
+def _hinted_host(fn, last, network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, key_begin, key,
+                 pair_cap):
+    nid, bodies, off, ln, kind, nb, sb, hint, sig, ns, kb, key, nk = _hinted_args(
+        network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, key_begin, key)
+    lib = load_library()
+    cap = int(lib.sv_txbodies_pair_bound(_ptr(sb), _ptr(kb), nb)) if pair_cap is None else int(pair_cap)
+    pb = np.zeros(nb + 1, np.uint64)
+    ps, pk = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+    pv = np.zeros(cap, np.uint8)
+    dig = np.zeros((nb, 32), np.uint8)
+    n_pairs = ctypes.c_size_t(0)
+    none = None if cap == 0 else 1
+    rc = fn(_ptr(nid), _ptr(bodies), _ptr(off), _ptr(ln), _ptr(kind), nb, _ptr(sb), _ptr(hint), _ptr(sig), ns,
+            _ptr(kb), _ptr(key), nk, cap, _ptr(pb), none and _ptr(ps), none and _ptr(pk), none and _ptr(pv),
+            ctypes.byref(n_pairs), _ptr(dig), last)
+    _check_pairs(rc, n_pairs)
+    n = int(n_pairs.value)
+    return pb, ps[:n], pk[:n], pv[:n], dig
+
+
+def verify_txbodies_hinted(network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, key_begin, key,
+                           pair_cap=None, device: int = -1, max_devices: int = 0, path=None):
+    """Pairing by hint on the device (sv_ed25519_verify_txbodies_hinted): body t
+    owns the decorated signatures sig_begin[t]..sig_begin[t+1]-1 (hint n x 4,
+    sig n x 64) and the candidate keys key_begin[t]..key_begin[t+1]-1 (key
+    m x 32).  Returns (pair_begin, pair_sig, pair_key, pair_verdict, digests):
+    the hint-matching pairs in (body, signature, key) order with the engine's
+    verdict over the body's contents hash.  The outputs are sized by
+    txbodies_pair_bound unless pair_cap is given; more pairs than pair_cap
+    raise SigVerifyError with .needed set to the exact count."""
+    lib = load_library()
+    return _hinted_host(lib.sv_ed25519_verify_txbodies_hinted, _opts(device, max_devices, path), network_id, bodies,
+                        body_off, body_len, body_kind, sig_begin, hint, sig, key_begin, key, pair_cap)
+
+
+def verify_txbodies_hinted_cpu(network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, key_begin, key,
+                               pair_cap=None, threads: int = 0):
+    """The same on the engine's CPU path (what a caller runs on an engine error)."""
+    lib = load_library()
+    return _hinted_host(lib.sv_ed25519_verify_txbodies_hinted_cpu, int(threads), network_id, bodies, body_off,
+                        body_len, body_kind, sig_begin, hint, sig, key_begin, key, pair_cap)
+
+
+def verify_txbodies_hinted_device(device: int, network_id, d_bodies: int, d_body_off: int, d_body_len: int,
+                                  d_body_kind: int, n_bodies: int, d_sig_begin: int, d_hint: int, d_sig: int,
+                                  n_sigs: int, d_key_begin: int, d_key: int, n_keys: int, pair_cap: int,
+                                  d_pair_begin: int, d_pair_sig: int, d_pair_key: int, d_pair_verdict: int,
+                                  d_pair_bitmap: int = 0, d_digests: int = 0, stream: int = 0) -> int:
+    """Device-resident form (raw device pointers; network_id is 32 host bytes).
+    Waits on `stream` once for the pair count, enqueues the verification and
+    returns the number of pairs; the results land in the d_pair_* arrays."""
+    lib = load_library()
+    nid = np.ascontiguousarray(np.frombuffer(bytes(network_id), np.uint8))
+    if nid.size != 32:
+        raise ValueError("network_id must be 32 bytes")
+    n_pairs = ctypes.c_size_t(0)
+    rc = lib.sv_ed25519_verify_txbodies_hinted_device(
+        device, _ptr(nid), d_bodies or None, d_body_off or None, d_body_len or None, d_body_kind or None, n_bodies,
+        d_sig_begin or None, d_hint or None, d_sig or None, n_sigs, d_key_begin or None, d_key or None, n_keys,
+        pair_cap, d_pair_begin or None, d_pair_sig or None, d_pair_key or None, d_pair_verdict or None,
+        d_pair_bitmap or None, ctypes.byref(n_pairs), d_digests or None, stream or None)
+    _check_pairs(rc, n_pairs)
+    return int(n_pairs.value)
 
 
 def verify_gather(items, keys: bool = False, device: int = -1, max_devices: int = 0):

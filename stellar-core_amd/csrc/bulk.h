@@ -1,7 +1,8 @@
 // Bulk work of a device slot, on its three streams under Device::mu: the
 // throughput-path launch with its per-key tables, the staged host-buffer
 // pipeline (host_slice), its kernel-less probe (feed_slice), SHA-256 batches
-// (sha_slice) and tx-body batches (tx_slice).  Included by sv_api.cpp.
+// (sha_slice), tx-body batches (tx_slice) and hinted tx-body batches, paired
+// by hint on the device (hinted_slice).  Included by sv_api.cpp.
 #pragma once
 
 #include <chrono>
@@ -638,6 +639,160 @@ inline int tx_slice_locked(Device& D, const TxIn& in, size_t B0, size_t B1, size
 inline int tx_slice(Device& D, const TxIn& in, size_t B0, size_t B1, size_t lo, size_t hi, size_t dig_from,
                     uint8_t* verdict, uint8_t* digests, int path) {
   return with_slot(D, [&] { return tx_slice_locked(D, in, B0, B1, lo, hi, dig_from, verdict, digests, path); });
+}
+
+// ------------------------------------------------- pairing by hint (hinted tx bodies)
+// The gathered key / signature / message arrays of a verify launch over np
+// pairs (caller holds D.mu, device set).  Growing frees the old arrays, which
+// an earlier launch may still read, so the kernel stream is drained first.
+inline int ensure_txpairs(Device& D, size_t np) {
+  if (32 * np <= D.txmsg.cap && 32 * np <= D.txpk.cap && 64 * np <= D.txsg.cap) return SV_OK;
+  SV_HIP(hipStreamSynchronize(D.stream));
+  int rc;
+  if ((rc = D.txmsg.ensure(32 * np)) || (rc = D.txpk.ensure(32 * np)) || (rc = D.txsg.ensure(64 * np))) return rc;
+  return SV_OK;
+}
+
+// Where a slice's pairs go: the caller's arrays (one slot), or vectors of the
+// slice's own that grow with the count (several slots: where a slot's pairs
+// start in the caller's arrays is only known once the slots before it are
+// done).
+struct PairSink {
+  uint32_t* ps = nullptr;
+  uint32_t* pk = nullptr;
+  uint8_t* pv = nullptr;
+  size_t cap = 0;
+  bool own = false;
+  std::vector<uint32_t> vs, vk;
+  std::vector<uint8_t> vv;
+  bool room(size_t total) {
+    if (total > cap) return false;
+    if (own && total > vv.size()) {
+      vs.resize(total);
+      vk.resize(total);
+      vv.resize(total);
+      ps = vs.data();
+      pk = vk.data();
+      pv = vv.data();
+    }
+    return true;
+  }
+};
+
+// A chunk's results in its pinned slot: verdicts (np, padded to 16) | pair_sig
+// (4 np) | pair_key (4 np) | pair_begin (8 k, padded) | digests (32 k).
+struct PairPending {
+  bool busy = false;
+  PairChunk c;
+  size_t np = 0, base = 0;
+};
+inline int pair_drain(Stage& s, PairPending& pd, PairSink& sink, uint64_t* pair_begin, uint8_t* digests) {
+  if (!pd.busy) return SV_OK;
+  SV_HIP(hipEventSynchronize(s.down));
+  pd.busy = false;
+  const PairChunk& c = pd.c;
+  const size_t np = pd.np, k = c.b1 - c.b0;
+  const uint8_t* h = (const uint8_t*)s.h_out.p;
+  const uint32_t* hs = (const uint32_t*)(h + al16(np));
+  const uint32_t* hk = hs + np;
+  const uint64_t* hb = (const uint64_t*)(h + al16(np) + al16(8 * np));
+  if (np) std::memcpy(sink.pv + pd.base, h, np);
+  for (size_t i = 0; i < np; ++i) {
+    sink.ps[pd.base + i] = hs[i] + (uint32_t)c.s0;
+    sink.pk[pd.base + i] = hk[i] + (uint32_t)c.k0;
+  }
+  for (size_t i = 0; i < k; ++i) pair_begin[c.b0 + i] = hb[i] + pd.base;
+  if (digests) std::memcpy(digests + 32 * c.b0, (const uint8_t*)(hb) + al16(8 * k), 32 * k);
+  return SV_OK;
+}
+
+// Bodies [B0, B1) with their signatures and keys on one slot (caller holds
+// D.mu, device set).  Per chunk: pack -> H2D -> contents hashes -> count and
+// scan -> the chunk's pair count back (the one wait: it covers the upload, the
+// hash and the pairing, on the upload stream, not a verify) -> fill and the
+// verify launch (mode 0 over the gathered arrays) -> D2H, over the slot's two
+// staging slots, so chunk c + 1 is packed while chunk c verifies.  pair_begin
+// [B0, B1) and the sink's indices count from the slice's first pair; *count:
+// the slice's exact number of pairs, also when it exceeds the sink (then the
+// remaining chunks only count, and the call returns SV_ERR_PAIR_CAP).
+inline int hinted_slice_locked(Device& D, const HintIn& in, size_t B0, size_t B1, PairSink& sink,
+                               uint64_t* pair_begin, uint8_t* digests, size_t* count, int path) {
+  int rc;
+  *count = 0;
+  const std::vector<PairChunk> plan = pair_plan(in, B0, B1, stage_chunk(), stage_chunk(), txbody_chunk_bytes());
+  if (plan.empty()) return SV_OK;
+  const bool single = plan.size() == 1;
+  hipStream_t up_s = single ? D.stream : D.h2d, down_s = single ? D.stream : D.d2h;
+  PairPending pend[2];
+  size_t total = 0;
+  bool overflow = false;
+  for (size_t ci = 0; ci < plan.size(); ++ci) {
+    const PairChunk& c = plan[ci];
+    Stage& s = D.st[ci & 1];
+    if ((rc = pair_drain(s, pend[ci & 1], sink, pair_begin, digests))) return rc;
+    const size_t m = c.s1 - c.s0, q = c.k1 - c.k0, k = c.b1 - c.b0;
+    const size_t wsb = al16(sv_pair_ws_bytes(k));
+    if ((rc = s.h_in.ensure(c.bytes)) || (rc = s.d_in.ensure(c.bytes)) || (rc = s.d_pair.ensure(wsb + 8 * (k + 1))) ||
+        (rc = s.d_keys.ensure(32 * k)) || (rc = s.h_cnt.ensure(64)))
+      return rc;
+    uint8_t* hp = (uint8_t*)s.h_in.p;
+    uint8_t* d = (uint8_t*)s.d_in.p;
+    pair_pack(in, c, hp);
+    if ((rc = upload_image(D, d, hp, c.bytes, up_s))) return rc;
+    const uint64_t* d_sb = (const uint64_t*)(d + c.o_sb);
+    const uint64_t* d_kb = (const uint64_t*)(d + c.o_kb);
+    const uint64_t* d_off = (const uint64_t*)(d + c.o_off);
+    const uint32_t* d_len = (const uint32_t*)(d + c.o_len);
+    uint64_t* d_pb = (uint64_t*)((uint8_t*)s.d_pair.p + wsb);
+    if (!overflow)
+      SV_HIP(sv_launch_txhash(D.grid * 8, in.nid, d + c.o_body, d_off, d_len, d + c.o_kind, k, nullptr, 0, nullptr,
+                              s.d_keys.p, up_s));
+    SV_HIP(sv_launch_pair_count(d_sb, d + c.o_hint, d + c.o_sig, m, d_kb, d, q, k, s.d_pair.p, d_pb, up_s));
+    SV_HIP(hipMemcpyAsync(s.h_cnt.p, sv_pair_total(s.d_pair.p, k), 8, hipMemcpyDeviceToHost, up_s));
+    SV_HIP(hipEventRecord(s.up, up_s));
+    SV_HIP(hipEventSynchronize(s.up));
+    const size_t np = (size_t)*(const uint64_t*)s.h_cnt.p;
+    const size_t base = total;
+    total += np;
+    if (overflow || !sink.room(total)) {
+      overflow = true;
+      continue;
+    }
+    if (!single) SV_HIP(hipStreamWaitEvent(D.stream, s.up, 0));
+    const size_t o_idx = al16(np), o_pb = o_idx + al16(8 * np), o_dig = o_pb + al16(8 * k);
+    if ((rc = ensure_txpairs(D, np)) || (rc = s.d_verdict.ensure(o_pb + 16)) || (rc = s.h_out.ensure(o_dig + 32 * k)))
+      return rc;
+    uint8_t* dv = (uint8_t*)s.d_verdict.p;
+    SV_HIP(sv_launch_pair_fill(d_sb, d + c.o_hint, d + c.o_sig, m, d_kb, d, q, k, s.d_pair.p, d_pb, np,
+                               (uint32_t*)(dv + o_idx), (uint32_t*)(dv + o_idx) + np, D.txpk.p, D.txsg.p, D.txmsg.p,
+                               s.d_keys.p, D.stream));
+    if (np && (rc = launch_locked(D, 0, path, D.txpk.p, D.txsg.p, D.txmsg.p, nullptr, nullptr, 32, np, dv, nullptr,
+                                  kt_mode() == 1)))
+      return rc;
+    if (!single) {
+      SV_HIP(hipEventRecord(s.done, D.stream));
+      SV_HIP(hipStreamWaitEvent(D.d2h, s.done, 0));
+    }
+    uint8_t* ho = (uint8_t*)s.h_out.p;
+    if (np) SV_HIP(hipMemcpyAsync(ho, dv, o_idx + 8 * np, hipMemcpyDeviceToHost, down_s));
+    SV_HIP(hipMemcpyAsync(ho + o_pb, d_pb, 8 * k, hipMemcpyDeviceToHost, down_s));
+    if (digests) SV_HIP(hipMemcpyAsync(ho + o_dig, s.d_keys.p, 32 * k, hipMemcpyDeviceToHost, down_s));
+    SV_HIP(hipEventRecord(s.down, down_s));
+    pend[ci & 1].busy = true;
+    pend[ci & 1].c = c;
+    pend[ci & 1].np = np;
+    pend[ci & 1].base = base;
+  }
+  for (int i = 0; i < 2; ++i)
+    if ((rc = pair_drain(D.st[i], pend[i], sink, pair_begin, digests))) return rc;
+  *count = total;
+  if (overflow) return fail(SV_ERR_PAIR_CAP, "more pairs than pair_cap holds");
+  return SV_OK;
+}
+
+inline int hinted_slice(Device& D, const HintIn& in, size_t B0, size_t B1, PairSink& sink, uint64_t* pair_begin,
+                        uint8_t* digests, size_t* count, int path) {
+  return with_slot(D, [&] { return hinted_slice_locked(D, in, B0, B1, sink, pair_begin, digests, count, path); });
 }
 
 }  // namespace

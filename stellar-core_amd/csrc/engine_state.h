@@ -190,6 +190,8 @@ struct HostBuf {
 struct Stage {
   HostBuf h_in, h_out;
   DevBuf d_in, d_verdict, d_keys;
+  DevBuf d_pair;  // hinted tx-body chunks: the pairing workspace, then pair_begin / pair_sig / pair_key
+  HostBuf h_cnt;  // ... and the chunk's pair count, read back before its verify launch
   hipEvent_t up = nullptr, done = nullptr, down = nullptr, keys_down = nullptr;
   std::vector<hipEvent_t> pev;  // keys of piece k are down (one-chunk keyed batches)
   bool busy = false;  // a chunk's D2H is pending on `down`
@@ -285,6 +287,10 @@ struct Device {
   DevBuf msg, off, len, keys;  // sha256 batches
   HostBuf h_sha;
   DevBuf txmsg;  // tx-body batches: the n x 32 message array the hash kernel fills (grown after draining `stream`)
+  // hinted tx-body batches: the pairs' keys (n_pairs x 32) and signatures (n_pairs x 64) gathered next to
+  // txmsg for the verify launch, the pairing workspace and the pair count of the device-resident form
+  DevBuf txpk, txsg, txpair;
+  HostBuf h_txcnt;
   KernelTimer timer;  // the bulk launches (launch_locked)
   LatLane lat;
   KeyTabs kt;  // (under mu)
@@ -390,6 +396,7 @@ inline void release_device(Device& D) {
   for (Stage& s : D.st) {
     s.h_in.release(); s.h_out.release();
     s.d_in.release(); s.d_verdict.release(); s.d_keys.release();
+    s.d_pair.release(); s.h_cnt.release();
     if (s.up) (void)hipEventDestroy(s.up);
     if (s.done) (void)hipEventDestroy(s.done);
     if (s.down) (void)hipEventDestroy(s.down);
@@ -400,6 +407,7 @@ inline void release_device(Device& D) {
   }
   D.msg.release(); D.off.release(); D.len.release(); D.keys.release(); D.h_sha.release();
   D.txmsg.release();
+  D.txpk.release(); D.txsg.release(); D.txpair.release(); D.h_txcnt.release();
   D.ws.release();
   D.kt.index.release(); D.kt.store.release(); D.kt.kslot.release(); D.kt.builders.release();
   D.kt.count.release(); D.kt.h_count.release();

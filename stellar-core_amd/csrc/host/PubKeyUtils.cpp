@@ -1036,6 +1036,40 @@ void verifyTxBodiesUncached(const uint8_t* networkID, const uint8_t* bodies, con
   gCpuSigs += n;
 }
 
+size_t verifyTxBodiesHintedUncached(const uint8_t* networkID, const uint8_t* bodies, const uint64_t* bodyOff,
+                                    const uint32_t* bodyLen, const uint8_t* bodyKind, size_t nBodies,
+                                    const uint64_t* sigBegin, const uint8_t* hint, const uint8_t* sig, size_t nSigs,
+                                    const uint64_t* keyBegin, const uint8_t* key, size_t nKeys, size_t pairCap,
+                                    uint64_t* pairBegin, uint32_t* pairSig, uint32_t* pairKey, uint8_t* pairVerdict,
+                                    uint8_t* digests) {
+  pairBegin[0] = 0;
+  if (nBodies == 0) return 0;
+  size_t np = 0;
+  const size_t work = std::max<size_t>(nSigs, 1);
+  int rc = timedBatch(true, work, [&] {
+    return sv_ed25519_verify_txbodies_hinted(networkID, bodies, bodyOff, bodyLen, bodyKind, nBodies, sigBegin, hint,
+                                             sig, nSigs, keyBegin, key, nKeys, pairCap, pairBegin, pairSig, pairKey,
+                                             pairVerdict, &np, digests, nullptr);
+  });
+  if (rc == SV_OK) {
+    gGpuSigs += np;
+    gGpuBatches += 1;
+    return np;
+  }
+  if (rc != SV_ERR_PAIR_CAP) {
+    ++gFallbacks;
+    rc = timedBatch(false, work, [&] {
+      return sv_ed25519_verify_txbodies_hinted_cpu(networkID, bodies, bodyOff, bodyLen, bodyKind, nBodies, sigBegin,
+                                                   hint, sig, nSigs, keyBegin, key, nKeys, pairCap, pairBegin, pairSig,
+                                                   pairKey, pairVerdict, &np, digests, 0);
+    });
+  }
+  if (rc == SV_ERR_PAIR_CAP) throw std::length_error("verifyTxBodiesHintedUncached: pairCap too small");
+  if (rc != SV_OK) throw std::invalid_argument("verifyTxBodiesHintedUncached: malformed batch");
+  gCpuSigs += np;
+  return np;
+}
+
 bool verifySig(PublicKey const& key, Signature const& signature, ByteSlice const& bin) {
   // the hit path as the reference runs it (SecretKey.cpp:446-456): key, one
   // lock, lookup, touch -- no batch bookkeeping; anything else (a miss, or an

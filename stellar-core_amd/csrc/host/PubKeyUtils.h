@@ -159,6 +159,18 @@ void verifyTxBodiesUncached(const uint8_t* networkID, const uint8_t* bodies, con
                             const uint64_t* sigBegin, const uint8_t* pk, const uint8_t* sig, size_t n,
                             uint8_t* verdict, uint8_t* digests);
 
+// The same with the pairing done by the engine (sv_ed25519_verify_txbodies_hinted,
+// same arguments; the pair arrays hold pairCap entries): returns the number of
+// pairs.  One engine call; an engine error re-runs it on the _cpu form and
+// counts a fallback.  Throws std::invalid_argument if both refuse the
+// arguments, std::length_error if pairCap is too small.
+size_t verifyTxBodiesHintedUncached(const uint8_t* networkID, const uint8_t* bodies, const uint64_t* bodyOff,
+                                    const uint32_t* bodyLen, const uint8_t* bodyKind, size_t nBodies,
+                                    const uint64_t* sigBegin, const uint8_t* hint, const uint8_t* sig, size_t nSigs,
+                                    const uint64_t* keyBegin, const uint8_t* key, size_t nKeys, size_t pairCap,
+                                    uint64_t* pairBegin, uint32_t* pairSig, uint32_t* pairKey, uint8_t* pairVerdict,
+                                    uint8_t* digests);
+
 void clearVerifySigCache();
 void maybeSeedVerifySigCache(unsigned int seed);
 void flushVerifySigCacheCounts(uint64_t& hits, uint64_t& misses);

@@ -9,6 +9,7 @@
 #include <mutex>
 #include <thread>
 
+#include "../../../include/stellar_sigverify.h"
 #include "HostPool.h"
 #include "hashes.h"
 
@@ -75,6 +76,9 @@ void SignatureBatchPrefetch::Storage::clear() {
   pk.clear();
   sig.clear();
   msg.clear();
+  hhint.clear();
+  hsig.clear();
+  hkey.clear();
   off.clear();
   len.clear();
   verdict.clear();
@@ -304,6 +308,120 @@ void SignatureBatchPrefetch::runBodies(const uint8_t* networkID, const uint8_t* 
     for (size_t k = 0; k < np; ++k) verdict_[payPair[k]] = pv[k];
   }
   buildTable();  // (after the hashes are in place: the table hashes the message bytes)
+}
+
+void SignatureBatchPrefetch::addHinted(TxBody const& body, std::vector<DecoratedSignature> const& signatures,
+                                       std::vector<Signer> const& signers) {
+  BodyEntry e;
+  e.body = body;
+  e.hashOff = ~0ull;
+  for (auto const& sig : signatures) {
+    if (sig.signature.size() != 64) continue;  // verifySig rejects before verifying
+    const size_t i = hHint_.size() / 4;
+    hHint_.resize(4 * (i + 1));
+    hSig_.resize(64 * (i + 1));
+    std::memcpy(&hHint_[4 * i], sig.hint.data(), 4);
+    std::memcpy(&hSig_[64 * i], sig.signature.data(), 64);
+  }
+  // the signed-payload pairs of this tx go to the pair storage now (st_); the
+  // engine's pairs are put in front of them by runBodiesHinted
+  e.pair0 = len_.size();
+  for (auto const& s : signers) {
+    if (s.key.type == SIGNER_KEY_TYPE_ED25519) {
+      const size_t i = hKey_.size() / 32;
+      hKey_.resize(32 * (i + 1));
+      std::memcpy(&hKey_[32 * i], s.key.key.data(), 32);
+    } else if (s.key.type == SIGNER_KEY_TYPE_ED25519_SIGNED_PAYLOAD) {
+      const SignatureHint sh = SignatureUtils::getSignedPayloadHint(s.key);
+      const uint32_t h = hint32(sh.data());
+      uint64_t payOff = ~0ull;
+      for (auto const& sig : signatures) {
+        if (sig.signature.size() != 64 || hint32(sig.hint.data()) != h) continue;
+        if (payOff == ~0ull) {
+          payOff = msg_.size();
+          msg_.insert(msg_.end(), s.key.payload.begin(), s.key.payload.end());
+        }
+        const size_t i = len_.size();
+        pk_.resize(32 * (i + 1));
+        sig_.resize(64 * (i + 1));
+        std::memcpy(&pk_[32 * i], s.key.key.data(), 32);
+        std::memcpy(&sig_[64 * i], sig.signature.data(), 64);
+        off_.push_back(payOff);
+        len_.push_back((uint32_t)s.key.payload.size());
+      }
+    }
+  }
+  e.pair1 = len_.size();
+  bodies_.push_back(e);
+  hSigBegin_.push_back(hHint_.size() / 4);
+  hKeyBegin_.push_back(hKey_.size() / 32);
+}
+
+void SignatureBatchPrefetch::runBodiesHinted(const uint8_t* networkID, const uint8_t* blob) {
+  const size_t nb = bodies_.size(), npay = len_.size();
+  verdict_.assign(npay, 0);
+  if (nb == 0) return;
+  std::vector<uint64_t> off(nb), pairBegin(nb + 1, 0);
+  std::vector<uint32_t> len(nb);
+  std::vector<uint8_t> kind(nb), digests(32 * nb);
+  for (size_t b = 0; b < nb; ++b) {
+    off[b] = bodies_[b].body.off;
+    len[b] = bodies_[b].body.len;
+    kind[b] = bodies_[b].body.kind;
+  }
+  const size_t ns = hHint_.size() / 4, nk = hKey_.size() / 32;
+  const size_t cap = sv_txbodies_pair_bound(hSigBegin_.data(), hKeyBegin_.data(), nb);
+  std::vector<uint32_t> pairSig(cap), pairKey(cap);
+  std::vector<uint8_t> pv(cap);
+  const size_t np = PubKeyUtils::verifyTxBodiesHintedUncached(
+      networkID, blob, off.data(), len.data(), kind.data(), nb, hSigBegin_.data(), hHint_.data(), hSig_.data(), ns,
+      hKeyBegin_.data(), hKey_.data(), nk, cap, pairBegin.data(), pairSig.data(), pairKey.data(), pv.data(),
+      digests.data());
+  for (size_t b = 0; b < nb; ++b)
+    if (bodies_[b].body.hashOut) std::memcpy(bodies_[b].body.hashOut->data(), &digests[32 * b], 32);
+  // The pair storage: the engine's np pairs first, in its order (body,
+  // signature, key), their messages the digests; behind them the signed-payload
+  // pairs enumerated by addHinted, verified as a batch of their own.
+  RawVec<uint8_t> ppk, psig, pmsg;
+  RawVec<uint64_t> poff;
+  RawVec<uint32_t> plen;
+  ppk.swap(pk_);
+  psig.swap(sig_);
+  pmsg.swap(msg_);
+  poff.swap(off_);
+  plen.swap(len_);
+  const size_t n = np + npay;
+  pk_.resize(32 * n);
+  sig_.resize(64 * n);
+  off_.resize(n);
+  len_.resize(n);
+  msg_.resize(32 * nb + pmsg.size());
+  std::memcpy(msg_.data(), digests.data(), 32 * nb);
+  if (!pmsg.empty()) std::memcpy(&msg_[32 * nb], pmsg.data(), pmsg.size());
+  verdict_.assign(n, 0);
+  txBegin_.resize(nb + 1);
+  for (size_t b = 0; b < nb; ++b) {
+    txBegin_[b] = (uint32_t)pairBegin[b];
+    for (size_t i = pairBegin[b]; i < pairBegin[b + 1]; ++i) {
+      std::memcpy(&pk_[32 * i], &hKey_[32 * (size_t)pairKey[i]], 32);
+      std::memcpy(&sig_[64 * i], &hSig_[64 * (size_t)pairSig[i]], 64);
+      off_[i] = 32 * b;
+      len_[i] = 32;
+      verdict_[i] = pv[i];
+    }
+  }
+  txBegin_[nb] = (uint32_t)np;
+  if (npay) {
+    std::memcpy(&pk_[32 * np], ppk.data(), 32 * npay);
+    std::memcpy(&sig_[64 * np], psig.data(), 64 * npay);
+    for (size_t k = 0; k < npay; ++k) {
+      off_[np + k] = 32 * nb + poff[k];
+      len_[np + k] = plen[k];
+    }
+    PubKeyUtils::verifyBatchUncached(&pk_[32 * np], &sig_[64 * np], msg_.data(), &off_[np], &len_[np], npay,
+                                     &verdict_[np]);
+  }
+  buildTable();
 }
 
 void SignatureBatchPrefetch::addBatch(std::vector<TxRef> const& txs, std::function<void(size_t)> const& prepare) {

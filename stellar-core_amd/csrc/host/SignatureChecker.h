@@ -123,11 +123,32 @@ class SignatureBatchPrefetch {
   void add(TxBody const& body, std::vector<DecoratedSignature> const& signatures,
            std::vector<Signer> const& signers);
   void runBodies(const uint8_t* networkID, const uint8_t* blob);
+  // Hinted body form: the pairing by hint is the engine's too.  addHinted makes
+  // one pass over the transaction and compares no hint: every 64-byte signature
+  // goes in with its hint (other lengths are skipped, as add() skips them),
+  // every ed25519 signer's key goes in as a candidate.  Signed-payload signers
+  // are still enumerated here (their hint is XORed with the payload's, their
+  // message is the payload): they stay the second, normally empty, batch.
+  // runBodiesHinted makes ONE sv_ed25519_verify_txbodies_hinted call (an engine
+  // error re-runs it on the _cpu form and counts a fallback), fills the pair
+  // storage from the returned indices -- body t's pairs are then also found by
+  // position (prefetchTx = t, counted over the addHinted calls) -- stores the
+  // digests through hashOut and builds the side table as runBodies does.
+  // lookup() is unchanged.  A prefetch takes one of the three forms only.
+  void addHinted(TxBody const& body, std::vector<DecoratedSignature> const& signatures,
+                 std::vector<Signer> const& signers);
+  void runBodiesHinted(const uint8_t* networkID, const uint8_t* blob);
   // verdict for (pk, sig, msg) if prefetched (tx: see addBatch)
   static constexpr size_t kNoTx = ~size_t(0);
   bool lookup(uint256 const& pk, Signature const& sig, ByteSlice const& msg, bool& verdict,
               size_t tx = kNoTx) const;
   size_t pairs() const { return len_.size(); }
+  // verdicts that were 1, after a run (measurement and tests)
+  size_t accepted() const {
+    size_t a = 0;
+    for (uint8_t v : verdict_) a += v != 0;
+    return a;
+  }
 
  private:
   void buildTable();
@@ -157,6 +178,7 @@ class SignatureBatchPrefetch {
   using RawVec = std::vector<T, NoInit<T>>;
   struct Storage {
     RawVec<uint8_t> pk, sig, msg;
+    RawVec<uint8_t> hhint, hsig, hkey;  // hinted body form: what goes to the engine (hints, signatures, keys)
     RawVec<uint64_t> off;
     RawVec<uint32_t> len;
     std::vector<uint8_t> verdict;
@@ -173,12 +195,16 @@ class SignatureBatchPrefetch {
     uint64_t hashOff;     // its contents hash in msg_ (~0: none)
   };
   std::vector<BodyEntry> bodies_;
+  std::vector<uint64_t> hSigBegin_{0}, hKeyBegin_{0};  // hinted body form: CSR by body, in addHinted order
   static std::vector<Storage>& spares();
   static constexpr size_t kSpares = 4;
   Storage st_;
   RawVec<uint8_t>& pk_ = st_.pk;
   RawVec<uint8_t>& sig_ = st_.sig;
   RawVec<uint8_t>& msg_ = st_.msg;
+  RawVec<uint8_t>& hHint_ = st_.hhint;
+  RawVec<uint8_t>& hSig_ = st_.hsig;
+  RawVec<uint8_t>& hKey_ = st_.hkey;
   RawVec<uint64_t>& off_ = st_.off;
   RawVec<uint32_t>& len_ = st_.len;
   std::vector<uint8_t>& verdict_ = st_.verdict;

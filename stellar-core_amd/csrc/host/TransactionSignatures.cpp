@@ -130,7 +130,7 @@ TxSigResult checkFeeBumpSignatures(FeeBumpSigInfo const& tx, AccountSnapshot con
 }
 
 void prefetchTransaction(SignatureBatchPrefetch& pre, TransactionSigInfo const& tx, AccountSnapshot const& accounts,
-                         SignatureBatchPrefetch::TxBody const* body) {
+                         SignatureBatchPrefetch::TxBody const* body, bool hinted) {
   std::vector<Signer> all;
   auto addAccount = [&](uint256 const& id, bool noAccountKey) {
     if (AccountSigState const* a = find(accounts, id)) {
@@ -156,17 +156,20 @@ void prefetchTransaction(SignatureBatchPrefetch& pre, TransactionSigInfo const& 
       }
     if (!dup) uniq.push_back(s);
   }
-  if (body) pre.add(*body, tx.signatures, uniq);
+  if (body && hinted) pre.addHinted(*body, tx.signatures, uniq);
+  else if (body) pre.add(*body, tx.signatures, uniq);
   else pre.add(tx.contentsHash, tx.signatures, uniq);
 }
 
 void prefetchFeeBump(SignatureBatchPrefetch& pre, FeeBumpSigInfo const& tx, AccountSnapshot const& accounts,
-                     SignatureBatchPrefetch::TxBody const* outerBody, SignatureBatchPrefetch::TxBody const* innerBody) {
+                     SignatureBatchPrefetch::TxBody const* outerBody, SignatureBatchPrefetch::TxBody const* innerBody,
+                     bool hinted) {
   // (body form: the outer body is added even without a fee-source account, so its hash is still computed)
   AccountSigState const* a = find(accounts, tx.feeSource);
-  if (outerBody) pre.add(*outerBody, tx.signatures, a ? accountSigners(*a) : std::vector<Signer>());
+  if (outerBody && hinted) pre.addHinted(*outerBody, tx.signatures, a ? accountSigners(*a) : std::vector<Signer>());
+  else if (outerBody) pre.add(*outerBody, tx.signatures, a ? accountSigners(*a) : std::vector<Signer>());
   else if (a) pre.add(tx.contentsHash, tx.signatures, accountSigners(*a));
-  prefetchTransaction(pre, tx.inner, accounts, innerBody);
+  prefetchTransaction(pre, tx.inner, accounts, innerBody, hinted);
 }
 
 }  // namespace stellar

@@ -113,11 +113,12 @@ TxSigResult checkFeeBumpSignatures(FeeBumpSigInfo const& tx, AccountSnapshot con
 
 // Adds every (signature, signer) pair the checks of `tx` can reach.  With a
 // body (SignatureBatchPrefetch's body form) the contents hash is not read: it
-// is the hash of that body, delivered by runBodies.
+// is the hash of that body, delivered by runBodies; with `hinted` the body goes
+// in through addHinted (the engine pairs by hint: runBodiesHinted).
 void prefetchTransaction(SignatureBatchPrefetch& pre, TransactionSigInfo const& tx, AccountSnapshot const& accounts,
-                         SignatureBatchPrefetch::TxBody const* body = nullptr);
+                         SignatureBatchPrefetch::TxBody const* body = nullptr, bool hinted = false);
 void prefetchFeeBump(SignatureBatchPrefetch& pre, FeeBumpSigInfo const& tx, AccountSnapshot const& accounts,
                      SignatureBatchPrefetch::TxBody const* outerBody = nullptr,
-                     SignatureBatchPrefetch::TxBody const* innerBody = nullptr);
+                     SignatureBatchPrefetch::TxBody const* innerBody = nullptr, bool hinted = false);
 
 }  // namespace stellar

@@ -478,8 +478,9 @@ int checkEnvelopes(const svh_envelope* env, size_t n, const svh_decorated_sig* s
                    const EnvelopeBodies* eb) {
   try {
     if (eb) {
-      if (prefetch != 0 && prefetch != 1)
-        throw std::invalid_argument("svh_check_envelopes_bodies: prefetch must be 0 or 1 (no keyed, cache-seeding form)");
+      if (prefetch != 0 && prefetch != 1 && prefetch != 3)
+        throw std::invalid_argument(
+            "svh_check_envelopes_bodies: prefetch must be 0, 1 or 3 (no keyed, cache-seeding form)");
       if (!eb->networkID || !eb->contentsHashOut || !eb->feeBumpHashOut || (n && !eb->body))
         throw std::invalid_argument("svh_check_envelopes_bodies: null argument");
       for (size_t t = 0; t < n; ++t) {
@@ -528,16 +529,19 @@ int checkEnvelopes(const svh_envelope* env, size_t n, const svh_decorated_sig* s
     }
     SignatureBatchPrefetch pre;
     if (prefetch && eb) {
-      // the catchup form: pairs enumerated without the hashes, one engine call
-      // from the bodies to the verdicts, the digests taken as the hashes
+      // the catchup form: pairs enumerated without the hashes (prefetch 3: by
+      // the engine, from hints and candidate keys), one engine call from the
+      // bodies to the verdicts, the digests taken as the hashes
+      const bool hinted = prefetch == 3;
       for (size_t t = 0; t < n; ++t) {
         svh_envelope_body const& b = eb->body[t];
         const SignatureBatchPrefetch::TxBody inner{b.off, b.len, (uint8_t)b.kind, &txs[t].inner.contentsHash};
         const SignatureBatchPrefetch::TxBody outer{b.outer_off, b.outer_len, 2, &txs[t].contentsHash};
-        if (env[t].fee_bump) prefetchFeeBump(pre, txs[t], snap, &outer, &inner);
-        else prefetchTransaction(pre, txs[t].inner, snap, &inner);
+        if (env[t].fee_bump) prefetchFeeBump(pre, txs[t], snap, &outer, &inner, hinted);
+        else prefetchTransaction(pre, txs[t].inner, snap, &inner, hinted);
       }
-      pre.runBodies(eb->networkID, eb->blob);
+      if (hinted) pre.runBodiesHinted(eb->networkID, eb->blob);
+      else pre.runBodies(eb->networkID, eb->blob);
     } else if (prefetch) {
       for (size_t t = 0; t < n; ++t) {
         if (env[t].fee_bump) prefetchFeeBump(pre, txs[t], snap);
@@ -592,6 +596,53 @@ int svh_check_envelopes_bodies(const svh_envelope* env, size_t n, const svh_deco
   const EnvelopeBodies eb{network_id, bodies, body, contents_hash_out, fee_bump_hash_out};
   return checkEnvelopes(env, n, sigs, ops, signers, accounts, naccounts, protocol, prefetch, for_apply, results,
                         prefetched_pairs, &eb);
+}
+
+int svh_bench_prefetch_bodies(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                              const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                              const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig,
+                              const uint64_t* key_begin, const uint8_t* key, int hinted, double ms[2],
+                              uint64_t* pairs, uint64_t* accepted) {
+  try {
+    if (!network_id || !sig_begin || !key_begin || !ms || !pairs || !accepted ||
+        (n_bodies && (!body_off || !body_len || !body_kind)))
+      throw std::invalid_argument("svh_bench_prefetch_bodies: null argument");
+    using clock = std::chrono::steady_clock;
+    SignatureBatchPrefetch pre;
+    std::vector<DecoratedSignature> sigs;
+    std::vector<Signer> signers;
+    double add = 0;
+    for (size_t t = 0; t < n_bodies; ++t) {
+      const size_t ns = (size_t)(sig_begin[t + 1] - sig_begin[t]), nk = (size_t)(key_begin[t + 1] - key_begin[t]);
+      sigs.resize(ns);
+      signers.resize(nk);
+      for (size_t i = 0; i < ns; ++i) {
+        const size_t s = (size_t)sig_begin[t] + i;
+        std::memcpy(sigs[i].hint.data(), hint + 4 * s, 4);
+        sigs[i].signature.assign(sig + 64 * s, sig + 64 * s + 64);
+      }
+      for (size_t i = 0; i < nk; ++i) {
+        signers[i].key.type = SIGNER_KEY_TYPE_ED25519;
+        std::memcpy(signers[i].key.key.data(), key + 32 * ((size_t)key_begin[t] + i), 32);
+        signers[i].weight = 1;
+      }
+      const SignatureBatchPrefetch::TxBody b{body_off[t], body_len[t], body_kind[t], nullptr};
+      const auto t0 = clock::now();
+      if (hinted) pre.addHinted(b, sigs, signers);
+      else pre.add(b, sigs, signers);
+      add += std::chrono::duration<double, std::milli>(clock::now() - t0).count();
+    }
+    const auto t0 = clock::now();
+    if (hinted) pre.runBodiesHinted(network_id, bodies);
+    else pre.runBodies(network_id, bodies);
+    ms[0] = add;
+    ms[1] = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
+    *pairs = pre.pairs();
+    *accepted = pre.accepted();
+    return SVH_OK;
+  } catch (std::exception const& e) {
+    return guard_exc(e);
+  }
 }
 
 int svh_mb_run_ex(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off,

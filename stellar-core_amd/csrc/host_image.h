@@ -363,5 +363,128 @@ inline void tx_pack(const TxIn& in, const TxChunk& c, size_t lo, size_t hi, uint
     }
   });
 }
+
+// sv_ed25519_verify_txbodies_hinted: bodies, their decorated signatures (hint
+// + signature) and their candidate keys, both in CSR form.
+struct HintIn {
+  const uint8_t* nid;
+  const uint8_t* bodies;
+  const uint64_t* off;
+  const uint32_t* len;
+  const uint8_t* kind;
+  size_t nb;
+  const uint64_t* sb;  // signatures of body t: [sb[t], sb[t + 1])
+  const uint8_t* hint;
+  const uint8_t* sig;
+  const uint64_t* kb;  // keys of body t: [kb[t], kb[t + 1])
+  const uint8_t* key;
+};
+
+// One staging chunk of it: bodies [b0, b1) with all their signatures [s0, s1)
+// and keys [k0, k1).  Pinned / device image (k bodies, m signatures, q keys):
+//   key (32 q) | sig (64 m) | hint (4 m) | body_off (8 k) | sig_begin (8 (k + 1)) | key_begin (8 (k + 1)) |
+//   body_len (4 k) | kind (k) | bodies
+// key, sig, hint, the CSR block and the body section start 16-byte aligned,
+// every body too (offsets relative to the body section); sig_begin and
+// key_begin are relative to s0 / k0.
+struct PairChunk {
+  size_t b0, b1, s0, s1, k0, k1;
+  size_t body_bytes;
+  size_t o_sig, o_hint, o_off, o_sb, o_kb, o_len, o_kind, o_body, bytes;
+};
+
+// The chunks of bodies [B0, B1): runs of whole bodies of at most max_s
+// signatures, max_k keys and max_b body bytes; a body over a bound is a chunk
+// alone.
+inline std::vector<PairChunk> pair_plan(const HintIn& in, size_t B0, size_t B1, size_t max_s, size_t max_k,
+                                        size_t max_b) {
+  std::vector<PairChunk> out;
+  size_t t = B0;
+  while (t < B1) {
+    PairChunk c{};
+    c.b0 = t;
+    c.s0 = (size_t)in.sb[t];
+    c.k0 = (size_t)in.kb[t];
+    size_t bytes = 0;
+    do {
+      bytes += al16(in.len[t]);
+      ++t;
+    } while (t < B1 && in.sb[t + 1] - c.s0 <= max_s && in.kb[t + 1] - c.k0 <= max_k &&
+             bytes + al16(in.len[t]) <= max_b);
+    c.b1 = t;
+    c.s1 = (size_t)in.sb[t];
+    c.k1 = (size_t)in.kb[t];
+    c.body_bytes = bytes;
+    const size_t m = c.s1 - c.s0, q = c.k1 - c.k0, k = c.b1 - c.b0;
+    c.o_sig = 32 * q;
+    c.o_hint = c.o_sig + 64 * m;
+    c.o_off = al16(c.o_hint + 4 * m);
+    c.o_sb = c.o_off + 8 * k;
+    c.o_kb = c.o_sb + 8 * (k + 1);
+    c.o_len = c.o_kb + 8 * (k + 1);
+    c.o_kind = c.o_len + 4 * k;
+    c.o_body = al16(c.o_kind + k);
+    c.bytes = c.o_body + std::max<size_t>(bytes, 16);
+    out.push_back(c);
+  }
+  return out;
+}
+
+inline void pair_pack(const HintIn& in, const PairChunk& c, uint8_t* h) {
+  const size_t m = c.s1 - c.s0, q = c.k1 - c.k0, k = c.b1 - c.b0;
+  uint64_t* offs = (uint64_t*)(h + c.o_off);
+  uint64_t* sb = (uint64_t*)(h + c.o_sb);
+  uint64_t* kb = (uint64_t*)(h + c.o_kb);
+  size_t pos = 0;
+  for (size_t i = 0; i < k; ++i) {
+    offs[i] = pos;
+    pos += al16(in.len[c.b0 + i]);
+  }
+  for (size_t i = 0; i <= k; ++i) {
+    sb[i] = in.sb[c.b0 + i] - c.s0;
+    kb[i] = in.kb[c.b0 + i] - c.k0;
+  }
+  std::memcpy(h + c.o_len, in.len + c.b0, 4 * k);
+  std::memcpy(h + c.o_kind, in.kind + c.b0, k);
+  Pool& pp = pack_pool();
+  const size_t parts = pack_parts(pp.size(), t_pack_parts, 32 * q + 68 * m + c.body_bytes, pack_part());
+  pp.run(parts, [&](size_t p) {
+    const PackCopy cp;
+    size_t a = q * p / parts, b = q * (p + 1) / parts;
+    if (b > a) cp(h + 32 * a, in.key + 32 * (c.k0 + a), 32 * (b - a));
+    a = m * p / parts, b = m * (p + 1) / parts;
+    if (b > a) {
+      cp(h + c.o_sig + 64 * a, in.sig + 64 * (c.s0 + a), 64 * (b - a));
+      std::memcpy(h + c.o_hint + 4 * a, in.hint + 4 * (c.s0 + a), 4 * (b - a));
+    }
+    for (size_t i = k * p / parts; i < k * (p + 1) / parts; ++i) {
+      const uint32_t l = in.len[c.b0 + i];
+      if (l) cp(h + c.o_body + offs[i], in.bodies + in.off[c.b0 + i], l);
+    }
+  });
+}
+
+// Body boundaries of G slices of bodies [0, nb): boundary g is the body edge
+// whose signature count is nearest to g * n / G (ties: the lower edge), kept
+// non-decreasing.  cut[0] = 0, cut[G] = nb.
+inline std::vector<size_t> pair_slices(const uint64_t* sb, size_t nb, size_t G) {
+  std::vector<size_t> cut(G + 1, 0);
+  const uint64_t n = sb[nb];
+  for (size_t g = 1; g < G; ++g) {
+    const uint64_t want = n / G * g + n % G * g / G;
+    // first edge with sb[e] >= want, and the one before it
+    size_t lo = 0, hi = nb;
+    while (lo < hi) {
+      const size_t mid = (lo + hi) / 2;
+      if (sb[mid] < want) lo = mid + 1;
+      else hi = mid;
+    }
+    size_t e = lo;
+    if (e > 0 && want - sb[e - 1] <= sb[e] - want) --e;
+    cut[g] = std::max(e, cut[g - 1]);
+  }
+  cut[G] = nb;
+  return cut;
+}
 }  // namespace
 }  // namespace sv

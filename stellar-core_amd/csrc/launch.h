@@ -1,6 +1,6 @@
 // The one declaration of every extern "C" launcher and size query that
 // crosses between the kernel files (sv_kernels.hip, sv_comb.hip, sv_hash.hip,
-// sv_txhash.hip), sv_cpu.cpp and the engine (sv_api.cpp and its modules).
+// sv_txhash.hip, sv_txpair.hip), sv_cpu.cpp and the engine (sv_api.cpp and its modules).
 // Included by the callers and by every definer, so a changed parameter list
 // is a compile error instead of arguments corrupted at run time.
 #pragma once
@@ -16,6 +16,14 @@ extern "C" {
 int sv_txbodies_check(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
                       const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies, const uint64_t* sig_begin,
                       const uint8_t* pk, const uint8_t* sig, size_t n, const uint8_t* verdict);
+// ... and of the hinted ones (sv_cpu.cpp): the bodies, the two CSR arrays and
+// the pair outputs against pair_cap.
+int sv_txpairs_check(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                     const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies, const uint64_t* sig_begin,
+                     const uint8_t* hint, const uint8_t* sig, size_t n_sigs, const uint64_t* key_begin,
+                     const uint8_t* key, size_t n_keys, size_t pair_cap, const uint64_t* pair_begin,
+                     const uint32_t* pair_sig, const uint32_t* pair_key, const uint8_t* pair_verdict,
+                     const size_t* n_pairs);
 
 }  // extern "C"
 
@@ -49,6 +57,19 @@ hipError_t sv_launch_hash(int kind, unsigned max_blocks, const void* pk, const v
 hipError_t sv_launch_txhash(unsigned max_blocks, const uint8_t* nid, const void* bodies, const uint64_t* off,
                             const uint32_t* len, const uint8_t* kind, uint64_t n_bodies, const uint64_t* sig_begin,
                             uint64_t n, void* msg, void* digests, hipStream_t s);
+// pairing by hint (sv_txpair.hip): count + scan, then fill; `ws` holds
+// sv_pair_ws_bytes(n_bodies), the pair count is *sv_pair_total(ws, n_bodies)
+int sv_pair_block(void);
+size_t sv_pair_ws_bytes(uint64_t n_bodies);
+const uint64_t* sv_pair_total(const void* ws, uint64_t n_bodies);
+hipError_t sv_launch_pair_count(const uint64_t* sig_begin, const void* hint, const void* sig, uint64_t n_sigs,
+                                const uint64_t* key_begin, const void* key, uint64_t n_keys, uint64_t n_bodies,
+                                void* ws, uint64_t* pair_begin, hipStream_t s);
+hipError_t sv_launch_pair_fill(const uint64_t* sig_begin, const void* hint, const void* sig, uint64_t n_sigs,
+                               const uint64_t* key_begin, const void* key, uint64_t n_keys, uint64_t n_bodies,
+                               void* ws, uint64_t* pair_begin, uint64_t n_pairs, uint32_t* pair_sig,
+                               uint32_t* pair_key, void* gkey, void* gsig, void* gmsg, const void* digests,
+                               hipStream_t s);
 // warm-key latency path (sv_comb.hip)
 size_t sv_comb_btab_bytes(void);
 size_t sv_key_slot_bytes(void);

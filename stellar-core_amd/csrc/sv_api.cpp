@@ -687,6 +687,152 @@ int sv_ed25519_verify_txbodies_device(int device, const uint8_t* network_id, con
       });
 }
 
+int sv_ed25519_verify_txbodies_hinted(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                      const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                      const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig,
+                                      size_t n_sigs, const uint64_t* key_begin, const uint8_t* key, size_t n_keys,
+                                      size_t pair_cap, uint64_t* pair_begin, uint32_t* pair_sig, uint32_t* pair_key,
+                                      uint8_t* pair_verdict, size_t* n_pairs, uint8_t* digests,
+                                      const sv_opts* opts) {
+  LifeGuard life_;
+  int rc = check_opts(opts);
+  if (rc) return rc;
+  if (sv_txpairs_check(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, n_sigs,
+                       key_begin, key, n_keys, pair_cap, pair_begin, pair_sig, pair_key, pair_verdict, n_pairs))
+    return fail(SV_ERR_INVALID_ARG,
+                "hinted tx bodies: null pointer, body kind > 2, 2^32 or more signatures or keys, or a malformed "
+                "sig_begin / key_begin");
+  *n_pairs = 0;
+  pair_begin[0] = 0;
+  if (n_bodies == 0) return SV_OK;
+  if ((rc = debug_fail())) return rc;
+  if ((rc = ensure_init())) return rc;
+  std::vector<Device*> devs;
+  if ((rc = select_devices(opts, n_sigs, devs))) return rc;
+  const int path = path_from_flags(opts ? opts->flags : 0u);
+  const HintIn in{network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, key_begin, key};
+  const size_t G = devs.size();
+  if (G == 1) {
+    PairSink sink;
+    sink.ps = pair_sig;
+    sink.pk = pair_key;
+    sink.pv = pair_verdict;
+    sink.cap = pair_cap;
+    size_t count = 0;
+    rc = hinted_slice(*devs[0], in, 0, n_bodies, sink, pair_begin, digests, &count, path);
+    if (rc == SV_OK || rc == SV_ERR_PAIR_CAP) *n_pairs = count;
+    if (rc == SV_OK) pair_begin[n_bodies] = count;
+    return rc;
+  }
+  // Slices of whole bodies; each slot collects its pairs in arrays of its own,
+  // joined below in slot order.
+  const std::vector<size_t> cut = pair_slices(sig_begin, n_bodies, G);
+  std::vector<PairSink> sinks(G);
+  std::vector<size_t> counts(G, 0);
+  std::vector<int> rcs(G, SV_OK);
+  for (PairSink& s : sinks) {
+    s.own = true;
+    s.cap = pair_cap;
+  }
+  rc = shard(devs, G, [&](Device& D, size_t g, size_t) {
+    if (cut[g] == cut[g + 1]) return SV_OK;
+    const int r = hinted_slice(D, in, cut[g], cut[g + 1], sinks[g], pair_begin, digests, &counts[g], path);
+    rcs[g] = r;
+    return r == SV_ERR_PAIR_CAP ? SV_OK : r;  // (the other slots' exact counts are still wanted)
+  });
+  if (rc) return rc;
+  size_t total = 0;
+  bool over = false;
+  for (size_t g = 0; g < G; ++g) {
+    total += counts[g];
+    over = over || rcs[g] == SV_ERR_PAIR_CAP;
+  }
+  *n_pairs = total;
+  if (over || total > pair_cap) return fail(SV_ERR_PAIR_CAP, "more pairs than pair_cap holds");
+  size_t base = 0;
+  for (size_t g = 0; g < G; ++g) {
+    const size_t c = counts[g];
+    if (c) {
+      std::memcpy(pair_sig + base, sinks[g].ps, 4 * c);
+      std::memcpy(pair_key + base, sinks[g].pk, 4 * c);
+      std::memcpy(pair_verdict + base, sinks[g].pv, c);
+    }
+    if (base)
+      for (size_t t = cut[g]; t < cut[g + 1]; ++t) pair_begin[t] += base;
+    base += c;
+  }
+  pair_begin[n_bodies] = total;
+  return SV_OK;
+}
+
+int sv_ed25519_verify_txbodies_hinted_device(int device, const uint8_t* network_id, const void* d_bodies,
+                                             const uint64_t* d_body_off, const uint32_t* d_body_len,
+                                             const uint8_t* d_body_kind, size_t n_bodies,
+                                             const uint64_t* d_sig_begin, const void* d_hint, const void* d_sig,
+                                             size_t n_sigs, const uint64_t* d_key_begin, const void* d_key,
+                                             size_t n_keys, size_t pair_cap, uint64_t* d_pair_begin,
+                                             uint32_t* d_pair_sig, uint32_t* d_pair_key, void* d_pair_verdict,
+                                             void* d_pair_bitmap, size_t* n_pairs, void* d_digests, void* stream) {
+  LifeGuard life_;
+  if (!network_id || !n_pairs || !d_pair_begin ||
+      (n_bodies && (!d_bodies || !d_body_off || !d_body_len || !d_body_kind || !d_sig_begin || !d_key_begin)) ||
+      (n_sigs && (!d_hint || !d_sig)) || (n_keys && !d_key) ||
+      (pair_cap && (!d_pair_sig || !d_pair_key)) || (d_pair_bitmap && !d_pair_verdict))
+    return fail(SV_ERR_INVALID_ARG, "hinted tx bodies: null pointer");
+  if ((uint64_t)n_sigs >> 32 || (uint64_t)n_keys >> 32)
+    return fail(SV_ERR_INVALID_ARG, "hinted tx bodies: 2^32 or more signatures or keys");
+  if (!aligned16(d_sig) || !aligned16(d_key) || !aligned16(d_digests) || ((uintptr_t)d_hint & 3u) ||
+      ((uintptr_t)d_pair_begin & 7u) || ((uintptr_t)d_pair_sig & 3u) || ((uintptr_t)d_pair_key & 3u))
+    return fail(SV_ERR_ALIGN, "sig/key/digests must be 16-byte aligned, hint and the pair arrays naturally aligned");
+  int rc;
+  if ((rc = debug_fail())) return rc;
+  Device* Dp;
+  if ((rc = slot_arg(device, Dp))) return rc;
+  Device& D = *Dp;
+  *n_pairs = 0;
+  hipStream_t user = (hipStream_t)stream;
+  std::lock_guard<std::mutex> g(D.mu);
+  SV_HIP(hipSetDevice(D.phys));
+  if ((rc = ready_locked(D))) return rc;
+  if (n_bodies == 0) {
+    SV_HIP(hipMemsetAsync(d_pair_begin, 0, 8, user));
+    return SV_OK;
+  }
+  // the pairing workspace, a digest array when the caller wants none, and the
+  // pinned word the count comes back in (growing drains the kernel stream)
+  const size_t wsb = al16(sv_pair_ws_bytes(n_bodies));
+  const size_t need = wsb + (d_digests ? 0 : 32 * n_bodies);
+  if (need > D.txpair.cap) {
+    SV_HIP(hipStreamSynchronize(D.stream));
+    if ((rc = D.txpair.ensure(need))) return rc;
+  }
+  if ((rc = D.h_txcnt.ensure(64))) return rc;
+  void* dig = d_digests ? d_digests : (void*)((uint8_t*)D.txpair.p + wsb);
+  SV_HIP(hipEventRecord(D.dep_in, user));
+  SV_HIP(hipStreamWaitEvent(D.stream, D.dep_in, 0));
+  SV_HIP(sv_launch_txhash(D.grid * 8, network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, nullptr, 0,
+                          nullptr, dig, D.stream));
+  SV_HIP(sv_launch_pair_count(d_sig_begin, d_hint, d_sig, n_sigs, d_key_begin, d_key, n_keys, n_bodies, D.txpair.p,
+                              d_pair_begin, D.stream));
+  SV_HIP(hipMemcpyAsync(D.h_txcnt.p, sv_pair_total(D.txpair.p, n_bodies), 8, hipMemcpyDeviceToHost, D.stream));
+  // the one wait: the number of pairs is only known on the device
+  SV_HIP(hipStreamSynchronize(D.stream));
+  const size_t np = (size_t)*(const uint64_t*)D.h_txcnt.p;
+  *n_pairs = np;
+  if (np > pair_cap) return fail(SV_ERR_PAIR_CAP, "more pairs than pair_cap holds");
+  if ((rc = ensure_txpairs(D, np))) return rc;
+  SV_HIP(sv_launch_pair_fill(d_sig_begin, d_hint, d_sig, n_sigs, d_key_begin, d_key, n_keys, n_bodies, D.txpair.p,
+                             d_pair_begin, np, d_pair_sig, d_pair_key, D.txpk.p, D.txsg.p, D.txmsg.p, dig, D.stream));
+  // (no verdict array: the pairs and digests only)
+  if (np && d_pair_verdict &&
+      (rc = launch_locked(D, 0, SV_PATH_AUTO, D.txpk.p, D.txsg.p, D.txmsg.p, nullptr, nullptr, 32, np,
+                          d_pair_verdict, d_pair_bitmap, kt_mode() == 1)))
+    return rc;
+  SV_HIP(hipEventRecord(D.dep_out, D.stream));
+  SV_HIP(hipStreamWaitEvent(user, D.dep_out, 0));
+  return SV_OK;
+}
+
 int sv_ed25519_verify_device(int device, const void* d_pk, const void* d_sig, const void* d_msg,
                              const uint64_t* d_msg_off, const uint32_t* d_msg_len, uint32_t fixed_msg_len,
                              size_t n, void* d_verdict, void* d_bitmap, void* stream) {
@@ -930,7 +1076,7 @@ int sv_workspace_bytes(int device, size_t* bytes) {
   // (lock order: the lane's mutex before the slot's)
   std::lock_guard<std::mutex> gl(Dp->lat.mu);
   std::lock_guard<std::mutex> g(Dp->mu);
-  size_t b = Dp->ws.cap + Dp->txmsg.cap;
+  size_t b = Dp->ws.cap + Dp->txmsg.cap + Dp->txpk.cap + Dp->txsg.cap + Dp->txpair.cap;
   for (const LatCtx& c : Dp->lat.ctx) b += c.ws.cap + c.d_in.cap + c.d_out.cap + c.d_keys.cap;
   *bytes = b;
   return SV_OK;

@@ -171,6 +171,105 @@ int sv_ed25519_verify_txbodies_cpu(const uint8_t* network_id, const uint8_t* bod
   return sv_ed25519_verify_batch_cpu(pk, sig, msg.data(), off.data(), len.data(), n, verdict, threads);
 }
 
+size_t sv_txbodies_pair_bound(const uint64_t* sig_begin, const uint64_t* key_begin, size_t n_bodies) {
+  if (!sig_begin || !key_begin) return 0;
+  unsigned __int128 sum = 0;
+  for (size_t t = 0; t < n_bodies; ++t) {
+    const uint64_t ns = sig_begin[t + 1] >= sig_begin[t] ? sig_begin[t + 1] - sig_begin[t] : 0;
+    const uint64_t nk = key_begin[t + 1] >= key_begin[t] ? key_begin[t + 1] - key_begin[t] : 0;
+    sum += (unsigned __int128)ns * nk;
+    if (sum > (unsigned __int128)SIZE_MAX) return SIZE_MAX;
+  }
+  return (size_t)sum;
+}
+
+// Argument check shared by the sv_ed25519_verify_txbodies_hinted host-array
+// entry points (declared in launch.h): SV_OK or SV_ERR_INVALID_ARG.
+int sv_txpairs_check(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                     const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies, const uint64_t* sig_begin,
+                     const uint8_t* hint, const uint8_t* sig, size_t n_sigs, const uint64_t* key_begin,
+                     const uint8_t* key, size_t n_keys, size_t pair_cap, const uint64_t* pair_begin,
+                     const uint32_t* pair_sig, const uint32_t* pair_key, const uint8_t* pair_verdict,
+                     const size_t* n_pairs) {
+  if (!network_id || !sig_begin || !key_begin || !pair_begin || !n_pairs) return SV_ERR_INVALID_ARG;
+  if (n_bodies && (!body_off || !body_len || !body_kind)) return SV_ERR_INVALID_ARG;
+  if ((uint64_t)n_sigs >> 32 || (uint64_t)n_keys >> 32) return SV_ERR_INVALID_ARG;
+  if ((n_sigs && (!hint || !sig)) || (n_keys && !key)) return SV_ERR_INVALID_ARG;
+  if (pair_cap && (!pair_sig || !pair_key || !pair_verdict)) return SV_ERR_INVALID_ARG;
+  if (sig_begin[0] != 0 || sig_begin[n_bodies] != n_sigs) return SV_ERR_INVALID_ARG;
+  if (key_begin[0] != 0 || key_begin[n_bodies] != n_keys) return SV_ERR_INVALID_ARG;
+  for (size_t t = 0; t < n_bodies; ++t) {
+    if (sig_begin[t + 1] < sig_begin[t] || key_begin[t + 1] < key_begin[t] || body_kind[t] > 2)
+      return SV_ERR_INVALID_ARG;
+    if (body_len[t] && !bodies) return SV_ERR_INVALID_ARG;
+  }
+  return SV_OK;
+}
+
+int sv_ed25519_verify_txbodies_hinted_cpu(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                          const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                          const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig,
+                                          size_t n_sigs, const uint64_t* key_begin, const uint8_t* key, size_t n_keys,
+                                          size_t pair_cap, uint64_t* pair_begin, uint32_t* pair_sig,
+                                          uint32_t* pair_key, uint8_t* pair_verdict, size_t* n_pairs,
+                                          uint8_t* digests, int threads) {
+  int rc = sv_txpairs_check(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, n_sigs,
+                            key_begin, key, n_keys, pair_cap, pair_begin, pair_sig, pair_key, pair_verdict, n_pairs);
+  if (rc) return rc;
+  auto word = [](const uint8_t* p) {
+    uint32_t w;
+    std::memcpy(&w, p, 4);
+    return w;
+  };
+  // pass 1: the counts (pair_begin), so an overflow is reported before anything is written
+  uint64_t total = 0;
+  for (size_t t = 0; t < n_bodies; ++t) {
+    pair_begin[t] = total;
+    for (uint64_t s = sig_begin[t]; s < sig_begin[t + 1]; ++s) {
+      const uint32_t h = word(hint + 4 * s);
+      for (uint64_t k = key_begin[t]; k < key_begin[t + 1]; ++k) total += word(key + 32 * k + 28) == h ? 1 : 0;
+    }
+  }
+  pair_begin[n_bodies] = total;
+  *n_pairs = (size_t)total;
+  if (total > pair_cap) return SV_ERR_PAIR_CAP;
+  // the digests through the tx-body CPU form (no signatures)
+  std::vector<uint8_t> own;
+  if (!digests && n_bodies) {
+    own.resize(32 * n_bodies);
+    digests = own.data();
+  }
+  if (n_bodies) {
+    const std::vector<uint64_t> none(n_bodies + 1, 0);
+    rc = sv_ed25519_verify_txbodies_cpu(network_id, bodies, body_off, body_len, body_kind, n_bodies, none.data(),
+                                        nullptr, nullptr, 0, nullptr, digests, threads);
+    if (rc) return rc;
+  }
+  if (total == 0) return SV_OK;
+  // pass 2: the pairs in (body, signature, key) order, gathered for the batch verifier
+  const size_t np = (size_t)total;
+  std::vector<uint8_t> gpk(32 * np), gsig(64 * np), gmsg(32 * np);
+  std::vector<uint64_t> off(np);
+  const std::vector<uint32_t> len(np, 32u);
+  size_t i = 0;
+  for (size_t t = 0; t < n_bodies; ++t)
+    for (uint64_t s = sig_begin[t]; s < sig_begin[t + 1]; ++s) {
+      const uint32_t h = word(hint + 4 * s);
+      for (uint64_t k = key_begin[t]; k < key_begin[t + 1]; ++k) {
+        if (word(key + 32 * k + 28) != h) continue;
+        pair_sig[i] = (uint32_t)s;
+        pair_key[i] = (uint32_t)k;
+        std::memcpy(&gpk[32 * i], key + 32 * k, 32);
+        std::memcpy(&gsig[64 * i], sig + 64 * s, 64);
+        std::memcpy(&gmsg[32 * i], digests + 32 * t, 32);
+        off[i] = 32 * i;
+        ++i;
+      }
+    }
+  return sv_ed25519_verify_batch_cpu(gpk.data(), gsig.data(), gmsg.data(), off.data(), len.data(), np, pair_verdict,
+                                     threads);
+}
+
 int sv_ed25519_verify_cpu(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, size_t msg_len) {
   if (!pk || !sig || (!msg && msg_len) || msg_len > 0xffffffffu) return SV_ERR_INVALID_ARG;
   std::call_once(g_once, build_tables);
