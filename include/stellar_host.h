@@ -215,7 +215,24 @@ int svh_check_envelopes(const svh_envelope* env, size_t n, const svh_decorated_s
  *               still enumerated on the host (their hint is XORed, their
  *               message their own) and stay the second batch.  An engine error
  *               re-runs on sv_ed25519_verify_txbodies_hinted_cpu (counted in
- *               svh_engine_stats.fallbacks).  Results and hashes as prefetch 1. */
+ *               svh_engine_stats.fallbacks).  Results and hashes as prefetch 1.
+ *   prefetch 4  SVH_ERR_INVALID_ARG here (it keeps its pipelined meaning of
+ *               svh_check_txset)
+ *   prefetch 5  decided on the device: each transaction's checkSignature calls
+ *               (signer lists with weights, needed weights, in the order the
+ *               checks are made) go up with its bodies, signatures of every
+ *               length and candidate key rows; ONE sv_ed25519_check_txbodies
+ *               call hashes, pairs, verifies and decides every check.  The host
+ *               builds no pair storage and no side table: result codes come
+ *               from the first failing check, the used marks are ORed over a
+ *               transaction's checks, and only a failed check with signed-
+ *               payload signers continues on the host.  *prefetched_pairs
+ *               receives the number of checks decided.  An engine error re-runs
+ *               on sv_ed25519_check_txbodies_cpu (counted in
+ *               svh_engine_stats.fallbacks).  An envelope beyond the engine's
+ *               limits (64 signatures, 64 signers in a check) is checked as
+ *               under prefetch 0, it alone; at protocol 7 the whole call is.
+ *               Results and hashes as prefetch 0. */
 typedef struct svh_envelope_body {
   uint64_t off;
   uint32_t len;

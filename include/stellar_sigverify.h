@@ -374,6 +374,100 @@ int sv_ed25519_verify_txbodies_hinted_cpu(const uint8_t* network_id, const uint8
                                           uint32_t* pair_key, uint8_t* pair_verdict, size_t* n_pairs,
                                           uint8_t* digests /* optional */, int threads);
 
+/* ---- Signature checks decided on the device -----------------------------
+ * What a caller wants from a transaction's signatures is not (signature, key,
+ * verdict) triples but, per SignatureChecker::checkSignature call, "did this
+ * check reach its needed weight" and, per transaction, "was every signature
+ * used".  These entry points take each body's checks -- signer lists with
+ * weights, and the needed weight -- next to what the hinted calls take, run the
+ * hinted pipeline (contents hash, pairing by hint, verification) and then one
+ * more kernel (csrc/sv_txcheck.hip, one lane per check) that replays every
+ * check literally (csrc/txcheck.h: PRE_AUTH_TX, then HASH_X, then ED25519
+ * signers; greedy over the signatures in order; a matched signer is erased;
+ * success ends the check at once).  The pairs stay inside the engine: its
+ * workspace is sized from the device's count, so there is no pair capacity and
+ * no SV_ERR_PAIR_CAP here.
+ *
+ *   bodies, sigs, keys   as sv_ed25519_verify_txbodies_hinted.  PRE_AUTH_TX and
+ *                    HASH_X signers' 32-byte keys sit in the body's key list
+ *                    like ed25519 keys (a signature whose hint happens to match
+ *                    one costs one wasted verification; only ED25519 signers
+ *                    read verdicts)
+ *   checks           the tables below
+ *   check_ok         out, n_checks bytes: 1 if the check succeeded within the
+ *                    PRE_AUTH_TX / HASH_X / ED25519 stages
+ *   check_weight     out, n_checks: the weight accumulated by those stages
+ *                    (saturated at 2^32 - 1)
+ *   check_used       out, n_checks: bit s set iff the check marked the body's
+ *                    signature s (body-local index) used.  Checks are
+ *                    independent: a body's used set is the OR over its checks
+ *   digests          optional, n_bodies x 32 bytes out
+ *
+ * ED25519_SIGNED_PAYLOAD signers (type 3) are accepted and skipped: they come
+ * last in the reference, so for a check that came back 0 the caller continues
+ * on the host from check_weight and the marks.  With needed <= 0 a check
+ * without any match is still 0, as in the reference.  A check considers at
+ * most 64 signers and a body at most 64 signatures.
+ *
+ * The host forms validate everything before any device work
+ * (SV_ERR_INVALID_ARG): a null required pointer, a malformed CSR array, a
+ * signer type > 3, a key index outside its body's key range, a sig_len > 64, a
+ * body with checks and more than 64 signatures, a check with more than 64
+ * signers, protocol_version 7 (every check is true there without the engine).
+ * Host buffers: chunks of whole bodies as in the hinted call, additionally
+ * bounded by checks (SV_STAGE_CHUNK) and signers (8 x SV_STAGE_CHUNK); only the three check
+ * arrays and the digests come back.  With opts->device == -1 the bodies are
+ * sliced as in the hinted call and each slot writes its checks' results
+ * straight into the caller's arrays. */
+typedef struct sv_txchecks {
+  uint32_t struct_size;          /* sizeof(sv_txchecks) */
+  uint32_t protocol_version;     /* weights clamp to 255 from 10 on; 7 is refused */
+  const uint8_t* sig_len;        /* optional, n_sigs: signature lengths (rows stay 64 bytes, zero-padded); NULL: all 64 */
+  const uint64_t* check_begin;   /* n_bodies + 1: body t's checks are check_begin[t] .. check_begin[t+1]-1 */
+  const int32_t* check_needed;   /* n_checks */
+  const uint64_t* signer_begin;  /* n_checks + 1: check c's signers, in list order */
+  const uint8_t* signer_type;    /* n_signers: SV_SIGNER_* */
+  const uint32_t* signer_weight; /* n_signers */
+  const uint32_t* signer_key;    /* n_signers: global index into key, inside the body's key range */
+  size_t n_checks;
+  size_t n_signers;
+} sv_txchecks;
+#define SV_SIGNER_KEY_ED25519 0
+#define SV_SIGNER_KEY_PRE_AUTH_TX 1
+#define SV_SIGNER_KEY_HASH_X 2
+#define SV_SIGNER_KEY_ED25519_SIGNED_PAYLOAD 3
+int sv_ed25519_check_txbodies(const uint8_t* network_id /* 32 B */, const uint8_t* bodies, const uint64_t* body_off,
+                              const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                              const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig, size_t n_sigs,
+                              const uint64_t* key_begin, const uint8_t* key, size_t n_keys, const sv_txchecks* checks,
+                              uint8_t* check_ok, uint32_t* check_weight, uint64_t* check_used,
+                              uint8_t* digests /* optional, n_bodies x 32 */, const sv_opts* opts);
+/* Device-resident form: every array, those `checks` points to included, is
+ * device memory on `device` (alignment as the hinted device form; the check
+ * tables and outputs naturally aligned); network_id and the sv_txchecks struct
+ * itself are host memory.  Stream semantics and the single wait for the pair
+ * count are those of sv_ed25519_verify_txbodies_hinted_device; the check kernel
+ * is enqueued after the verify launch and the call returns without waiting for
+ * either.  The device arrays are not validated: every CSR range and key index
+ * is clamped to its array (an out-of-range key index matches nothing, a check
+ * no body owns is 0), and nothing is written outside the three outputs. */
+int sv_ed25519_check_txbodies_device(int device, const uint8_t* network_id /* host, 32 B */, const void* d_bodies,
+                                     const uint64_t* d_body_off, const uint32_t* d_body_len,
+                                     const uint8_t* d_body_kind, size_t n_bodies, const uint64_t* d_sig_begin,
+                                     const void* d_hint, const void* d_sig, size_t n_sigs,
+                                     const uint64_t* d_key_begin, const void* d_key, size_t n_keys,
+                                     const sv_txchecks* checks /* host struct, device arrays */, void* d_check_ok,
+                                     uint32_t* d_check_weight, uint64_t* d_check_used, void* d_digests, void* stream);
+/* The same contract on the engine's CPU path (what a caller runs when one of
+ * the two above returns an engine error, and the reference on a host without a
+ * GPU; threads as sv_ed25519_verify_batch_cpu). */
+int sv_ed25519_check_txbodies_cpu(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                  const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                  const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig, size_t n_sigs,
+                                  const uint64_t* key_begin, const uint8_t* key, size_t n_keys,
+                                  const sv_txchecks* checks, uint8_t* check_ok, uint32_t* check_weight,
+                                  uint64_t* check_used, uint8_t* digests /* optional */, int threads);
+
 /* ---- Warm-key latency path (csrc/comb.h, csrc/sv_comb.hip) ---------------
  * Each device slot keeps a bounded cache of per-public-key tables
  * ({0..8} * 16^j * (-A), 108 KiB per key) in HBM.  A latency-path host batch

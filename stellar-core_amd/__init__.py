@@ -72,7 +72,11 @@ EXPORTED_SYMBOLS = (
     "sv_ed25519_verify_txbodies", "sv_ed25519_verify_txbodies_device", "sv_ed25519_verify_txbodies_cpu",
     "sv_ed25519_verify_txbodies_hinted", "sv_ed25519_verify_txbodies_hinted_device",
     "sv_ed25519_verify_txbodies_hinted_cpu", "sv_txbodies_pair_bound",
+    "sv_ed25519_check_txbodies", "sv_ed25519_check_txbodies_device", "sv_ed25519_check_txbodies_cpu",
 )
+
+# signer key types of the check entry points (include/stellar_sigverify.h)
+SIGNER_ED25519, SIGNER_PRE_AUTH_TX, SIGNER_HASH_X, SIGNER_SIGNED_PAYLOAD = 0, 1, 2, 3
 
 # body kinds of the tx-body entry points (include/stellar_sigverify.h)
 TXBODY_V1, TXBODY_V0, TXBODY_FEE_BUMP = 0, 1, 2
@@ -99,6 +103,14 @@ class SigVerifyError(RuntimeError):
 class sv_opts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("device", ctypes.c_int32),
                 ("max_devices", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class sv_txchecks(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("protocol_version", ctypes.c_uint32),
+                ("sig_len", ctypes.c_void_p), ("check_begin", ctypes.c_void_p), ("check_needed", ctypes.c_void_p),
+                ("signer_begin", ctypes.c_void_p), ("signer_type", ctypes.c_void_p),
+                ("signer_weight", ctypes.c_void_p), ("signer_key", ctypes.c_void_p),
+                ("n_checks", ctypes.c_size_t), ("n_signers", ctypes.c_size_t)]
 
 
 class FeedStats(ctypes.Structure):
@@ -181,6 +193,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.sv_ed25519_verify_txbodies_hinted_cpu.argtypes = hinted + [szp, vp, ctypes.c_int]
     lib.sv_ed25519_verify_txbodies_hinted_device.argtypes = [ctypes.c_int] + hinted + [vp, szp, vp, vp]
     lib.sv_txbodies_pair_bound.argtypes = [vp, vp, sz]
+    checked = [vp, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp, vp, sz, ctypes.POINTER(sv_txchecks), vp, vp, vp, vp]
+    lib.sv_ed25519_check_txbodies.argtypes = checked + [vp]
+    lib.sv_ed25519_check_txbodies_cpu.argtypes = checked + [ctypes.c_int]
+    lib.sv_ed25519_check_txbodies_device.argtypes = [ctypes.c_int] + checked + [vp]
     lib.sv_txbodies_pair_bound.restype = sz
     _lib = lib
     return lib
@@ -523,6 +539,97 @@ def verify_txbodies_hinted_device(device: int, network_id, d_bodies: int, d_body
         d_pair_bitmap or None, ctypes.byref(n_pairs), d_digests or None, stream or None)
     _check_pairs(rc, n_pairs)
     return int(n_pairs.value)
+
+
+def _checks_desc(protocol_version, sig_len, check_begin, check_needed, signer_begin, signer_type, signer_weight,
+                 signer_key, n_checks, n_signers):
+    """sv_txchecks over raw addresses (host arrays' or device pointers)."""
+    ck = sv_txchecks()
+    ck.struct_size = ctypes.sizeof(sv_txchecks)
+    ck.protocol_version = int(protocol_version)
+    ck.sig_len = sig_len or None
+    ck.check_begin, ck.check_needed, ck.signer_begin = check_begin or None, check_needed or None, signer_begin or None
+    ck.signer_type, ck.signer_weight, ck.signer_key = signer_type or None, signer_weight or None, signer_key or None
+    ck.n_checks, ck.n_signers = int(n_checks), int(n_signers)
+    return ck
+
+
+def _check_host(fn, last, network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, key_begin, key,
+                check_begin, check_needed, signer_begin, signer_type, signer_weight, signer_key, sig_len,
+                protocol_version):
+    nid, bodies, off, ln, kind, nb, sb, hint, sig, ns, kb, key, nk = _hinted_args(
+        network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, key_begin, key)
+    cb = _csr(check_begin, nb, "check_begin")
+    need = np.ascontiguousarray(np.asarray(check_needed, dtype=np.int32).reshape(-1))
+    nc = need.shape[0]
+    gb = _csr(signer_begin, nc, "signer_begin")
+    gt = np.ascontiguousarray(np.asarray(signer_type, dtype=np.uint8).reshape(-1))
+    gw = np.ascontiguousarray(np.asarray(signer_weight, dtype=np.uint32).reshape(-1))
+    gk = np.ascontiguousarray(np.asarray(signer_key, dtype=np.uint32).reshape(-1))
+    ng = gt.shape[0]
+    if gw.shape[0] != ng or gk.shape[0] != ng:
+        raise ValueError("signer_type / signer_weight / signer_key row mismatch")
+    sl = None
+    if sig_len is not None:
+        sl = np.ascontiguousarray(np.asarray(sig_len, dtype=np.uint8).reshape(-1))
+        if sl.shape[0] != ns:
+            raise ValueError("sig_len must hold one byte per signature")
+    a = lambda x: x.__array_interface__["data"][0]  # noqa: E731
+    ck = _checks_desc(protocol_version, a(sl) if sl is not None else 0, a(cb), a(need), a(gb), a(gt), a(gw), a(gk),
+                      nc, ng)
+    ok, weight, used = np.zeros(nc, np.uint8), np.zeros(nc, np.uint32), np.zeros(nc, np.uint64)
+    dig = np.zeros((nb, 32), np.uint8)
+    _check(fn(_ptr(nid), _ptr(bodies), _ptr(off), _ptr(ln), _ptr(kind), nb, _ptr(sb), _ptr(hint), _ptr(sig), ns,
+              _ptr(kb), _ptr(key), nk, ctypes.byref(ck), _ptr(ok), _ptr(weight), _ptr(used), _ptr(dig), last))
+    return ok, weight, used, dig
+
+
+def check_txbodies(network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, key_begin, key,
+                   check_begin, check_needed, signer_begin, signer_type, signer_weight, signer_key, sig_len=None,
+                   protocol_version: int = 21, device: int = -1, max_devices: int = 0, path=None):
+    """Signature checks decided on the device (sv_ed25519_check_txbodies): the
+    inputs of verify_txbodies_hinted plus body t's checks check_begin[t]..
+    check_begin[t+1]-1, each a needed weight and the signers signer_begin[c]..
+    signer_begin[c+1]-1 (type, weight, global key index).  Returns (check_ok,
+    check_weight, check_used, digests): one SignatureChecker::checkSignature
+    decision per check, the weight it accumulated and the mask of the body's
+    signatures it marked used."""
+    lib = load_library()
+    return _check_host(lib.sv_ed25519_check_txbodies, _opts(device, max_devices, path), network_id, bodies, body_off,
+                       body_len, body_kind, sig_begin, hint, sig, key_begin, key, check_begin, check_needed,
+                       signer_begin, signer_type, signer_weight, signer_key, sig_len, protocol_version)
+
+
+def check_txbodies_cpu(network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, key_begin, key,
+                       check_begin, check_needed, signer_begin, signer_type, signer_weight, signer_key, sig_len=None,
+                       protocol_version: int = 21, threads: int = 0):
+    """The same on the engine's CPU path (what a caller runs on an engine error)."""
+    lib = load_library()
+    return _check_host(lib.sv_ed25519_check_txbodies_cpu, int(threads), network_id, bodies, body_off, body_len,
+                       body_kind, sig_begin, hint, sig, key_begin, key, check_begin, check_needed, signer_begin,
+                       signer_type, signer_weight, signer_key, sig_len, protocol_version)
+
+
+def check_txbodies_device(device: int, network_id, d_bodies: int, d_body_off: int, d_body_len: int, d_body_kind: int,
+                          n_bodies: int, d_sig_begin: int, d_hint: int, d_sig: int, n_sigs: int, d_key_begin: int,
+                          d_key: int, n_keys: int, d_check_begin: int, d_check_needed: int, n_checks: int,
+                          d_signer_begin: int, d_signer_type: int, d_signer_weight: int, d_signer_key: int,
+                          n_signers: int, d_check_ok: int, d_check_weight: int, d_check_used: int,
+                          d_sig_len: int = 0, protocol_version: int = 21, d_digests: int = 0, stream: int = 0) -> None:
+    """Device-resident form (raw device pointers; network_id is 32 host bytes).
+    Waits on `stream` once for the pair count, enqueues the verification and
+    the check kernel and returns; the decisions land in the d_check_* arrays."""
+    lib = load_library()
+    nid = np.ascontiguousarray(np.frombuffer(bytes(network_id), np.uint8))
+    if nid.size != 32:
+        raise ValueError("network_id must be 32 bytes")
+    ck = _checks_desc(protocol_version, d_sig_len, d_check_begin, d_check_needed, d_signer_begin, d_signer_type,
+                      d_signer_weight, d_signer_key, n_checks, n_signers)
+    _check(lib.sv_ed25519_check_txbodies_device(
+        device, _ptr(nid), d_bodies or None, d_body_off or None, d_body_len or None, d_body_kind or None, n_bodies,
+        d_sig_begin or None, d_hint or None, d_sig or None, n_sigs, d_key_begin or None, d_key or None, n_keys,
+        ctypes.byref(ck), d_check_ok or None, d_check_weight or None, d_check_used or None, d_digests or None,
+        stream or None))
 
 
 def verify_gather(items, keys: bool = False, device: int = -1, max_devices: int = 0):

@@ -795,5 +795,119 @@ inline int hinted_slice(Device& D, const HintIn& in, size_t B0, size_t B1, PairS
   return with_slot(D, [&] { return hinted_slice_locked(D, in, B0, B1, sink, pair_begin, digests, count, path); });
 }
 
+// ------------------------------------------------- checks decided on the device
+// Where a slice's decisions go: the caller's arrays, indexed by global check.
+struct CheckOut {
+  uint8_t* ok;
+  uint32_t* weight;
+  uint64_t* used;
+  uint8_t* digests;  // optional
+};
+
+// A chunk's results in its pinned slot: check_used (8 nc) | check_weight (4 nc)
+// | check_ok (nc, padded to 16) | digests (32 k).
+struct CheckPending {
+  bool busy = false;
+  CheckChunk c;
+};
+inline int check_drain(Stage& s, CheckPending& pd, const CheckOut& out) {
+  if (!pd.busy) return SV_OK;
+  SV_HIP(hipEventSynchronize(s.down));
+  pd.busy = false;
+  const CheckChunk& c = pd.c;
+  const size_t nc = c.c1 - c.c0, k = c.p.b1 - c.p.b0;
+  const uint8_t* h = (const uint8_t*)s.h_out.p;
+  if (nc) {
+    std::memcpy(out.used + c.c0, h, 8 * nc);
+    std::memcpy(out.weight + c.c0, h + 8 * nc, 4 * nc);
+    std::memcpy(out.ok + c.c0, h + 12 * nc, nc);
+  }
+  if (out.digests) std::memcpy(out.digests + 32 * c.p.b0, h + al16(13 * nc), 32 * k);
+  return SV_OK;
+}
+
+// Bodies [B0, B1) with their signatures, keys and checks on one slot (caller
+// holds D.mu, device set): hinted_slice_locked's sequence per chunk -- pack ->
+// H2D -> contents hashes -> count and scan -> the pair count back (the one
+// wait) -> fill -> verify launch -- followed by the check kernel on the same
+// stream; only the three check arrays and the digests come back.  The pairs
+// live in the stage's device buffer, sized from the count.
+inline int check_slice_locked(Device& D, const CheckIn& in, size_t B0, size_t B1, int clamp, const CheckOut& out,
+                              int path) {
+  int rc;
+  // (a signer is 9 bytes of image against a signature's 68: eight staging chunks of them bound a chunk, so a
+  // multisig batch is not cut many times more often than its signatures would cut it -- every chunk waits once
+  // for its pair count)
+  const std::vector<CheckChunk> plan = check_plan(in, B0, B1, stage_chunk(), stage_chunk(), txbody_chunk_bytes(),
+                                                  stage_chunk(), 8 * stage_chunk());
+  if (plan.empty()) return SV_OK;
+  const bool single = plan.size() == 1;
+  hipStream_t up_s = single ? D.stream : D.h2d, down_s = single ? D.stream : D.d2h;
+  CheckPending pend[2];
+  for (size_t ci = 0; ci < plan.size(); ++ci) {
+    const CheckChunk& c = plan[ci];
+    Stage& s = D.st[ci & 1];
+    if ((rc = check_drain(s, pend[ci & 1], out))) return rc;
+    const size_t m = c.p.s1 - c.p.s0, q = c.p.k1 - c.p.k0, k = c.p.b1 - c.p.b0;
+    const size_t nc = c.c1 - c.c0, ng = c.g1 - c.g0;
+    const size_t wsb = al16(sv_pair_ws_bytes(k));
+    if ((rc = s.h_in.ensure(c.bytes)) || (rc = s.d_in.ensure(c.bytes)) || (rc = s.d_pair.ensure(wsb + 8 * (k + 1))) ||
+        (rc = s.d_keys.ensure(32 * k)) || (rc = s.h_cnt.ensure(64)))
+      return rc;
+    uint8_t* hp = (uint8_t*)s.h_in.p;
+    uint8_t* d = (uint8_t*)s.d_in.p;
+    check_pack(in, c, hp);
+    if ((rc = upload_image(D, d, hp, c.bytes, up_s))) return rc;
+    const uint64_t* d_sb = (const uint64_t*)(d + c.p.o_sb);
+    const uint64_t* d_kb = (const uint64_t*)(d + c.p.o_kb);
+    uint64_t* d_pb = (uint64_t*)((uint8_t*)s.d_pair.p + wsb);
+    SV_HIP(sv_launch_txhash(D.grid * 8, in.h.nid, d + c.p.o_body, (const uint64_t*)(d + c.p.o_off),
+                            (const uint32_t*)(d + c.p.o_len), d + c.p.o_kind, k, nullptr, 0, nullptr, s.d_keys.p,
+                            up_s));
+    SV_HIP(sv_launch_pair_count(d_sb, d + c.p.o_hint, d + c.p.o_sig, m, d_kb, d, q, k, s.d_pair.p, d_pb, up_s));
+    SV_HIP(hipMemcpyAsync(s.h_cnt.p, sv_pair_total(s.d_pair.p, k), 8, hipMemcpyDeviceToHost, up_s));
+    SV_HIP(hipEventRecord(s.up, up_s));
+    SV_HIP(hipEventSynchronize(s.up));
+    const size_t np = (size_t)*(const uint64_t*)s.h_cnt.p;
+    if (!single) SV_HIP(hipStreamWaitEvent(D.stream, s.up, 0));
+    // verdicts (np, padded) | pair_sig, pair_key (4 np each, padded) | used | weight | ok
+    const size_t o_idx = al16(np), o_res = o_idx + al16(8 * np), o_dig = al16(13 * nc);
+    if ((rc = ensure_txpairs(D, np)) || (rc = s.d_verdict.ensure(o_res + 13 * nc + 16)) ||
+        (rc = s.h_out.ensure(o_dig + 32 * k)))
+      return rc;
+    uint8_t* dv = (uint8_t*)s.d_verdict.p;
+    uint32_t* d_ps = (uint32_t*)(dv + o_idx);
+    uint32_t* d_pk = d_ps + np;
+    SV_HIP(sv_launch_pair_fill(d_sb, d + c.p.o_hint, d + c.p.o_sig, m, d_kb, d, q, k, s.d_pair.p, d_pb, np, d_ps, d_pk,
+                               D.txpk.p, D.txsg.p, D.txmsg.p, s.d_keys.p, D.stream));
+    if (np && (rc = launch_locked(D, 0, path, D.txpk.p, D.txsg.p, D.txmsg.p, nullptr, nullptr, 32, np, dv, nullptr,
+                                  kt_mode() == 1)))
+      return rc;
+    SV_HIP(sv_launch_txcheck(d_sb, d + c.p.o_hint, d + c.p.o_sig, in.sig_len ? d + c.o_sl : nullptr, m, d_kb, d, q, k,
+                             d_pb, d_ps, d_pk, dv, np, s.d_keys.p, (const uint64_t*)(d + c.o_cb),
+                             (const int32_t*)(d + c.o_need), nc, (const uint64_t*)(d + c.o_gb), d + c.o_gt,
+                             (const uint32_t*)(d + c.o_gw), (const uint32_t*)(d + c.o_gk), ng, clamp,
+                             dv + o_res + 12 * nc, (uint32_t*)(dv + o_res + 8 * nc), (uint64_t*)(dv + o_res),
+                             D.stream));
+    if (!single) {
+      SV_HIP(hipEventRecord(s.done, D.stream));
+      SV_HIP(hipStreamWaitEvent(D.d2h, s.done, 0));
+    }
+    uint8_t* ho = (uint8_t*)s.h_out.p;
+    if (nc) SV_HIP(hipMemcpyAsync(ho, dv + o_res, 13 * nc, hipMemcpyDeviceToHost, down_s));
+    if (out.digests) SV_HIP(hipMemcpyAsync(ho + o_dig, s.d_keys.p, 32 * k, hipMemcpyDeviceToHost, down_s));
+    SV_HIP(hipEventRecord(s.down, down_s));
+    pend[ci & 1].busy = true;
+    pend[ci & 1].c = c;
+  }
+  for (int i = 0; i < 2; ++i)
+    if ((rc = check_drain(D.st[i], pend[i], out))) return rc;
+  return SV_OK;
+}
+
+inline int check_slice(Device& D, const CheckIn& in, size_t B0, size_t B1, int clamp, const CheckOut& out, int path) {
+  return with_slot(D, [&] { return check_slice_locked(D, in, B0, B1, clamp, out, path); });
+}
+
 }  // namespace
 }  // namespace sv

@@ -291,6 +291,7 @@ struct Device {
   // txmsg for the verify launch, the pairing workspace and the pair count of the device-resident form
   DevBuf txpk, txsg, txpair;
   HostBuf h_txcnt;
+  DevBuf txchk;  // device-resident check calls: the pairs' indices and verdicts, which stay inside the engine
   KernelTimer timer;  // the bulk launches (launch_locked)
   LatLane lat;
   KeyTabs kt;  // (under mu)
@@ -407,7 +408,7 @@ inline void release_device(Device& D) {
   }
   D.msg.release(); D.off.release(); D.len.release(); D.keys.release(); D.h_sha.release();
   D.txmsg.release();
-  D.txpk.release(); D.txsg.release(); D.txpair.release(); D.h_txcnt.release();
+  D.txpk.release(); D.txsg.release(); D.txpair.release(); D.h_txcnt.release(); D.txchk.release();
   D.ws.release();
   D.kt.index.release(); D.kt.store.release(); D.kt.kslot.release(); D.kt.builders.release();
   D.kt.count.release(); D.kt.h_count.release();

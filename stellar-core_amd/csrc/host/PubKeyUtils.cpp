@@ -1070,6 +1070,32 @@ size_t verifyTxBodiesHintedUncached(const uint8_t* networkID, const uint8_t* bod
   return np;
 }
 
+void checkTxBodiesUncached(const uint8_t* networkID, const uint8_t* bodies, const uint64_t* bodyOff,
+                           const uint32_t* bodyLen, const uint8_t* bodyKind, size_t nBodies, const uint64_t* sigBegin,
+                           const uint8_t* hint, const uint8_t* sig, size_t nSigs, const uint64_t* keyBegin,
+                           const uint8_t* key, size_t nKeys, const ::sv_txchecks& checks, uint8_t* checkOk,
+                           uint32_t* checkWeight, uint64_t* checkUsed, uint8_t* digests) {
+  if (nBodies == 0) return;
+  const size_t work = std::max<size_t>(nSigs, 1);
+  int rc = timedBatch(true, work, [&] {
+    return sv_ed25519_check_txbodies(networkID, bodies, bodyOff, bodyLen, bodyKind, nBodies, sigBegin, hint, sig, nSigs,
+                                     keyBegin, key, nKeys, &checks, checkOk, checkWeight, checkUsed, digests, nullptr);
+  });
+  if (rc == SV_OK) {
+    gGpuSigs += nSigs;
+    gGpuBatches += 1;
+    return;
+  }
+  ++gFallbacks;
+  rc = timedBatch(false, work, [&] {
+    return sv_ed25519_check_txbodies_cpu(networkID, bodies, bodyOff, bodyLen, bodyKind, nBodies, sigBegin, hint, sig,
+                                         nSigs, keyBegin, key, nKeys, &checks, checkOk, checkWeight, checkUsed,
+                                         digests, 0);
+  });
+  if (rc != SV_OK) throw std::invalid_argument("checkTxBodiesUncached: malformed batch");
+  gCpuSigs += nSigs;
+}
+
 bool verifySig(PublicKey const& key, Signature const& signature, ByteSlice const& bin) {
   // the hit path as the reference runs it (SecretKey.cpp:446-456): key, one
   // lock, lookup, touch -- no batch bookkeeping; anything else (a miss, or an

@@ -36,6 +36,8 @@
 #include <stdexcept>
 #include <vector>
 
+struct sv_txchecks;  // include/stellar_sigverify.h
+
 namespace stellar {
 
 using uint256 = std::array<uint8_t, 32>;
@@ -170,6 +172,16 @@ size_t verifyTxBodiesHintedUncached(const uint8_t* networkID, const uint8_t* bod
                                     const uint64_t* keyBegin, const uint8_t* key, size_t nKeys, size_t pairCap,
                                     uint64_t* pairBegin, uint32_t* pairSig, uint32_t* pairKey, uint8_t* pairVerdict,
                                     uint8_t* digests);
+
+// One sv_ed25519_check_txbodies call over host arrays (the check tables of
+// include/stellar_sigverify.h sv_txchecks): an engine error re-runs the batch on
+// sv_ed25519_check_txbodies_cpu and counts a fallback; a malformed batch throws
+// std::invalid_argument.  No cache interaction.
+void checkTxBodiesUncached(const uint8_t* networkID, const uint8_t* bodies, const uint64_t* bodyOff,
+                           const uint32_t* bodyLen, const uint8_t* bodyKind, size_t nBodies, const uint64_t* sigBegin,
+                           const uint8_t* hint, const uint8_t* sig, size_t nSigs, const uint64_t* keyBegin,
+                           const uint8_t* key, size_t nKeys, const ::sv_txchecks& checks, uint8_t* checkOk,
+                           uint32_t* checkWeight, uint64_t* checkUsed, uint8_t* digests);
 
 void clearVerifySigCache();
 void maybeSeedVerifySigCache(unsigned int seed);

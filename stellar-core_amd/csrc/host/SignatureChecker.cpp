@@ -7,6 +7,7 @@
 #include <cstring>
 #include <exception>
 #include <mutex>
+#include <stdexcept>
 #include <thread>
 
 #include "../../../include/stellar_sigverify.h"
@@ -422,6 +423,95 @@ void SignatureBatchPrefetch::runBodiesHinted(const uint8_t* networkID, const uin
                                      &verdict_[np]);
   }
   buildTable();
+}
+
+bool SignatureBatchPrefetch::addDecided(TxBody const& body, std::vector<DecoratedSignature> const& signatures,
+                                        std::vector<SignatureCheck> const& checks) {
+  if (signatures.size() > 64) return false;
+  for (auto const& sig : signatures)
+    if (sig.signature.size() > 64) return false;
+  for (auto const& c : checks)
+    if (c.signers.size() > 64) return false;
+  Decided& d = dec_;
+  BodyEntry e;
+  e.body = body;
+  e.pair0 = e.pair1 = 0;
+  e.hashOff = ~0ull;
+  bodies_.push_back(e);
+  for (auto const& sig : signatures) {
+    const size_t i = d.sigLen.size();
+    d.hint.resize(4 * (i + 1));
+    d.sig.resize(64 * (i + 1), 0);
+    std::memcpy(&d.hint[4 * i], sig.hint.data(), 4);
+    if (!sig.signature.empty()) std::memcpy(&d.sig[64 * i], sig.signature.data(), sig.signature.size());
+    d.sigLen.push_back((uint8_t)sig.signature.size());
+  }
+  // the body's candidate rows: every distinct 32-byte key its checks name (the
+  // source account's signers recur in every operation's check)
+  const size_t k0 = d.key.size() / 32;
+  for (auto const& c : checks) {
+    for (auto const& s : c.signers) {
+      if (s.key.type == SIGNER_KEY_TYPE_ED25519_SIGNED_PAYLOAD) continue;  // the caller's stage
+      size_t k = k0;
+      const size_t k1 = d.key.size() / 32;
+      while (k < k1 && std::memcmp(&d.key[32 * k], s.key.key.data(), 32) != 0) ++k;
+      if (k == k1) {
+        d.key.resize(32 * (k1 + 1));
+        std::memcpy(&d.key[32 * k1], s.key.key.data(), 32);
+      }
+      d.type.push_back((uint8_t)s.key.type);
+      d.weight.push_back(s.weight);
+      d.keyIndex.push_back((uint32_t)k);
+    }
+    d.needed.push_back(c.needed);
+    d.signerBegin.push_back(d.type.size());
+  }
+  d.sigBegin.push_back(d.sigLen.size());
+  d.keyBegin.push_back(d.key.size() / 32);
+  d.checkBegin.push_back(d.needed.size());
+  return true;
+}
+
+void SignatureBatchPrefetch::runDecided(const uint8_t* networkID, const uint8_t* blob, uint32_t protocolVersion) {
+  Decided& d = dec_;
+  const size_t nb = bodies_.size(), nc = d.needed.size();
+  d.ok.assign(nc, 0);
+  d.outWeight.assign(nc, 0);
+  d.used.assign(nc, 0);
+  if (nb == 0) return;
+  std::vector<uint64_t> off(nb);
+  std::vector<uint32_t> len(nb);
+  std::vector<uint8_t> kind(nb), digests(32 * nb);
+  for (size_t b = 0; b < nb; ++b) {
+    off[b] = bodies_[b].body.off;
+    len[b] = bodies_[b].body.len;
+    kind[b] = bodies_[b].body.kind;
+  }
+  sv_txchecks ck;
+  ck.struct_size = sizeof ck;
+  ck.protocol_version = protocolVersion;
+  ck.sig_len = d.sigLen.data();
+  ck.check_begin = d.checkBegin.data();
+  ck.check_needed = d.needed.data();
+  ck.signer_begin = d.signerBegin.data();
+  ck.signer_type = d.type.data();
+  ck.signer_weight = d.weight.data();
+  ck.signer_key = d.keyIndex.data();
+  ck.n_checks = nc;
+  ck.n_signers = d.type.size();
+  PubKeyUtils::checkTxBodiesUncached(networkID, blob, off.data(), len.data(), kind.data(), nb, d.sigBegin.data(),
+                                     d.hint.data(), d.sig.data(), d.sigLen.size(), d.keyBegin.data(), d.key.data(),
+                                     d.key.size() / 32, ck, d.ok.data(), d.outWeight.data(), d.used.data(),
+                                     digests.data());
+  for (size_t b = 0; b < nb; ++b)
+    if (bodies_[b].body.hashOut) std::memcpy(bodies_[b].body.hashOut->data(), &digests[32 * b], 32);
+}
+
+SignatureBatchPrefetch::Decision SignatureBatchPrefetch::decision(size_t body, size_t check) const {
+  const size_t c = (size_t)dec_.checkBegin.at(body) + check;
+  if (c >= dec_.checkBegin.at(body + 1) || c >= dec_.ok.size())
+    throw std::out_of_range("SignatureBatchPrefetch::decision: no such check (or runDecided has not run)");
+  return Decision{dec_.ok[c] != 0, dec_.outWeight[c], dec_.used[c]};
 }
 
 void SignatureBatchPrefetch::addBatch(std::vector<TxRef> const& txs, std::function<void(size_t)> const& prepare) {

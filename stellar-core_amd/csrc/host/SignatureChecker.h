@@ -68,6 +68,12 @@ bool verifyHashX(DecoratedSignature const& sig, SignerKey const& signerKey);
 bool verifyEd25519SignedPayload(DecoratedSignature const& sig, SignerKey const& signer);
 }  // namespace SignatureUtils
 
+// One checkSignature call: a signer list and the needed weight.
+struct SignatureCheck {
+  std::vector<Signer> signers;
+  int32_t needed = 0;
+};
+
 // Verdicts computed ahead of the checkers.
 class SignatureBatchPrefetch {
  public:
@@ -138,6 +144,29 @@ class SignatureBatchPrefetch {
   void addHinted(TxBody const& body, std::vector<DecoratedSignature> const& signatures,
                  std::vector<Signer> const& signers);
   void runBodiesHinted(const uint8_t* networkID, const uint8_t* blob);
+  // Decided form: not verdicts but decisions.  addDecided takes a transaction
+  // body, its signatures (every length up to 64) and the checkSignature calls
+  // its validation makes, in order; runDecided makes ONE
+  // sv_ed25519_check_txbodies call (an engine error re-runs it on the _cpu form
+  // and counts a fallback) and stores the digests through hashOut.  No pair
+  // storage and no table are built: decision(body, k) is check k of the
+  // addDecided call number `body` -- did it reach its needed weight within the
+  // PRE_AUTH_TX / HASH_X / ED25519 stages, the weight those stages accumulated
+  // and the signatures they marked used.  Signed-payload signers stay with the
+  // caller (they are not sent).  addDecided returns false, adding nothing, for
+  // what the engine does not take: more than 64 signatures, a signature longer
+  // than 64 bytes, a check with more than 64 signers.  A prefetch takes one
+  // form only.
+  struct Decision {
+    bool ok;
+    uint32_t weight;
+    uint64_t used;
+  };
+  bool addDecided(TxBody const& body, std::vector<DecoratedSignature> const& signatures,
+                  std::vector<SignatureCheck> const& checks);
+  void runDecided(const uint8_t* networkID, const uint8_t* blob, uint32_t protocolVersion);
+  Decision decision(size_t body, size_t check) const;
+  size_t decidedChecks() const { return dec_.needed.size(); }
   // verdict for (pk, sig, msg) if prefetched (tx: see addBatch)
   static constexpr size_t kNoTx = ~size_t(0);
   bool lookup(uint256 const& pk, Signature const& sig, ByteSlice const& msg, bool& verdict,
@@ -195,6 +224,12 @@ class SignatureBatchPrefetch {
     uint64_t hashOff;     // its contents hash in msg_ (~0: none)
   };
   std::vector<BodyEntry> bodies_;
+  struct Decided {  // the decided form's tables (include/stellar_sigverify.h sv_txchecks) and results
+    std::vector<uint8_t> hint, sig, sigLen, key, type, ok;
+    std::vector<uint64_t> sigBegin{0}, keyBegin{0}, checkBegin{0}, signerBegin{0}, used;
+    std::vector<int32_t> needed;
+    std::vector<uint32_t> weight, keyIndex, outWeight;
+  } dec_;
   std::vector<uint64_t> hSigBegin_{0}, hKeyBegin_{0};  // hinted body form: CSR by body, in addHinted order
   static std::vector<Storage>& spares();
   static constexpr size_t kSpares = 4;

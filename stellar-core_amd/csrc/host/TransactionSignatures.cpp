@@ -49,57 +49,6 @@ Signer noAccountSigner(uint256 const& id) {
 
 }  // namespace
 
-TxSigResult checkTransactionSignatures(TransactionSigInfo const& tx, AccountSnapshot const& accounts,
-                                       uint32_t protocol, SignatureBatchPrefetch const* prefetched, bool forApply) {
-  TxSigResult r;
-  SignatureChecker checker(protocol, tx.contentsHash, tx.signatures, prefetched);
-  AccountSigState const* src = find(accounts, tx.sourceAccount);
-  if (!src) {  // commonValidPreSeqNum
-    r.code = txNO_ACCOUNT;
-    return r;
-  }
-  if (!checker.checkSignature(accountSigners(*src), src->thresholds[THRESHOLD_LOW_LEVEL])) {
-    r.code = txBAD_AUTH;
-    return r;
-  }
-  if (protocol >= 19 && !tx.extraSigners.empty() &&
-      !checker.checkSignature(extraSignerList(tx.extraSigners), (int32_t)tx.extraSigners.size())) {
-    r.code = txBAD_AUTH;
-    return r;
-  }
-  if (forApply && protocol < 10) return r;  // processSignatures, TransactionFrame.cpp:1100-1103
-  for (size_t i = 0; i < tx.operations.size(); ++i) {
-    auto const& op = tx.operations[i];
-    uint256 const& id = op.sourceAccount ? *op.sourceAccount : tx.sourceAccount;
-    AccountSigState const* acc = find(accounts, id);
-    bool ok;
-    int32_t opc = opINNER;
-    if (acc) {
-      ok = checker.checkSignature(accountSigners(*acc), acc->thresholds[op.level]);
-      if (!ok) opc = opBAD_AUTH;
-    } else if (!op.sourceAccount) {
-      // (processSignatures calls OperationFrame::checkSignature with
-      // forApply = false, TransactionFrame.cpp:1130-1131: a missing op-source
-      // account is checked by its key alone in BOTH modes; only a missing
-      // transaction source gives opNO_ACCOUNT, OperationFrame.cpp:194-198)
-      ok = false;
-      opc = opNO_ACCOUNT;
-    } else {
-      ok = checker.checkSignature({noAccountSigner(id)}, 0);
-      if (!ok) opc = opBAD_AUTH;
-    }
-    if (!ok && r.code != txFAILED) {
-      r.code = txFAILED;
-      r.failedOp = (int32_t)i;
-      r.opCode = opc;
-      if (!forApply) return r;  // checkValid fast-fails on the first invalid operation
-    }
-  }
-  if (r.code == txFAILED) return r;
-  if (!checker.checkAllSignaturesUsed()) r.code = txBAD_AUTH_EXTRA;
-  return r;
-}
-
 TxSigResult checkFeeBumpSignatures(FeeBumpSigInfo const& tx, AccountSnapshot const& accounts, uint32_t protocol,
                                    SignatureBatchPrefetch const* prefetched, bool forApply) {
   TxSigResult r;
@@ -122,6 +71,176 @@ TxSigResult checkFeeBumpSignatures(FeeBumpSigInfo const& tx, AccountSnapshot con
     return r;
   }
   TxSigResult inner = checkTransactionSignatures(tx.inner, accounts, protocol, prefetched, forApply);
+  r.code = inner.code == txSUCCESS ? txFEE_BUMP_INNER_SUCCESS : txFEE_BUMP_INNER_FAILED;
+  r.innerCode = inner.code;
+  r.failedOp = inner.failedOp;
+  r.opCode = inner.opCode;
+  return r;
+}
+
+namespace {
+
+// The sequence of checks of one transaction -- the one copy of it -- over any
+// checker: check(signers, needed) -> bool, allUsed() -> bool.  A SignatureChecker
+// (checkTransactionSignatures), a list (listTransactionChecks) and the engine's
+// decisions (checkTransactionSignaturesDecided) all walk it.
+template <class Check, class AllUsed>
+TxSigResult walkTransaction(TransactionSigInfo const& tx, AccountSnapshot const& accounts, uint32_t protocol,
+                            bool forApply, Check&& check, AllUsed&& allUsed) {
+  TxSigResult r;
+  AccountSigState const* src = find(accounts, tx.sourceAccount);
+  if (!src) {  // commonValidPreSeqNum
+    r.code = txNO_ACCOUNT;
+    return r;
+  }
+  if (!check(accountSigners(*src), (int32_t)src->thresholds[THRESHOLD_LOW_LEVEL])) {
+    r.code = txBAD_AUTH;
+    return r;
+  }
+  if (protocol >= 19 && !tx.extraSigners.empty() &&
+      !check(extraSignerList(tx.extraSigners), (int32_t)tx.extraSigners.size())) {
+    r.code = txBAD_AUTH;
+    return r;
+  }
+  if (forApply && protocol < 10) return r;  // processSignatures, TransactionFrame.cpp:1100-1103
+  for (size_t i = 0; i < tx.operations.size(); ++i) {
+    auto const& op = tx.operations[i];
+    uint256 const& id = op.sourceAccount ? *op.sourceAccount : tx.sourceAccount;
+    AccountSigState const* acc = find(accounts, id);
+    bool ok;
+    int32_t opc = opINNER;
+    if (acc) {
+      ok = check(accountSigners(*acc), (int32_t)acc->thresholds[op.level]);
+      if (!ok) opc = opBAD_AUTH;
+    } else if (!op.sourceAccount) {
+      // (processSignatures calls OperationFrame::checkSignature with
+      // forApply = false, TransactionFrame.cpp:1130-1131: a missing op-source
+      // account is checked by its key alone in BOTH modes; only a missing
+      // transaction source gives opNO_ACCOUNT, OperationFrame.cpp:194-198)
+      ok = false;
+      opc = opNO_ACCOUNT;
+    } else {
+      ok = check(std::vector<Signer>{noAccountSigner(id)}, 0);
+      if (!ok) opc = opBAD_AUTH;
+    }
+    if (!ok && r.code != txFAILED) {
+      r.code = txFAILED;
+      r.failedOp = (int32_t)i;
+      r.opCode = opc;
+      if (!forApply) return r;  // checkValid fast-fails on the first invalid operation
+    }
+  }
+  if (r.code == txFAILED) return r;
+  if (!allUsed()) r.code = txBAD_AUTH_EXTRA;
+  return r;
+}
+
+// A checker that consumes the engine's decisions of one body in order.
+class DecidedChecker {
+ public:
+  DecidedChecker(uint32_t protocol, std::vector<DecoratedSignature> const& signatures,
+                 SignatureBatchPrefetch const& pre, size_t body)
+      : mProtocol(protocol), mSignatures(signatures), mPre(pre), mBody(body) {}
+  bool check(std::vector<Signer> const& signers, int32_t needed) {
+    const SignatureBatchPrefetch::Decision d = mPre.decision(mBody, mNext++);
+    mUsed |= d.used;
+    if (d.ok) return true;
+    // the reference's last stage, from the state the engine's three left
+    std::vector<Signer const*> rest;
+    for (auto const& s : signers)
+      if (s.key.type == SIGNER_KEY_TYPE_ED25519_SIGNED_PAYLOAD) rest.push_back(&s);
+    if (rest.empty()) return false;
+    int64_t total = d.weight;
+    for (size_t i = 0; i < mSignatures.size(); ++i)
+      for (auto it = rest.begin(); it != rest.end(); ++it)
+        if (SignatureUtils::verifyEd25519SignedPayload(mSignatures[i], (*it)->key)) {
+          mUsed |= 1ull << i;
+          const uint32_t w = (*it)->weight;
+          total += mProtocol >= 10 && w > 255 ? 255 : w;
+          if (total >= needed) return true;
+          rest.erase(it);
+          break;
+        }
+    return false;
+  }
+  bool allUsed() const {
+    const size_t n = mSignatures.size();
+    const uint64_t want = n >= 64 ? ~0ull : (1ull << n) - 1;
+    return (mUsed & want) == want;
+  }
+
+ private:
+  uint32_t mProtocol;
+  std::vector<DecoratedSignature> const& mSignatures;
+  SignatureBatchPrefetch const& mPre;
+  size_t mBody, mNext = 0;
+  uint64_t mUsed = 0;
+};
+
+}  // namespace
+
+TxSigResult checkTransactionSignatures(TransactionSigInfo const& tx, AccountSnapshot const& accounts,
+                                       uint32_t protocol, SignatureBatchPrefetch const* prefetched, bool forApply) {
+  SignatureChecker checker(protocol, tx.contentsHash, tx.signatures, prefetched);
+  return walkTransaction(
+      tx, accounts, protocol, forApply,
+      [&](std::vector<Signer> const& signers, int32_t needed) { return checker.checkSignature(signers, needed); },
+      [&] { return checker.checkAllSignaturesUsed(); });
+}
+
+std::vector<SignatureCheck> listTransactionChecks(TransactionSigInfo const& tx, AccountSnapshot const& accounts,
+                                                  uint32_t protocol, bool forApply) {
+  std::vector<SignatureCheck> out;
+  (void)walkTransaction(
+      tx, accounts, protocol, forApply,
+      [&](std::vector<Signer> signers, int32_t needed) {
+        out.push_back(SignatureCheck{std::move(signers), needed});
+        return true;
+      },
+      [] { return true; });
+  return out;
+}
+
+std::vector<SignatureCheck> listFeeBumpOuterChecks(FeeBumpSigInfo const& tx, AccountSnapshot const& accounts) {
+  std::vector<SignatureCheck> out;
+  if (AccountSigState const* fee = find(accounts, tx.feeSource))
+    out.push_back(SignatureCheck{accountSigners(*fee), (int32_t)fee->thresholds[THRESHOLD_LOW_LEVEL]});
+  return out;
+}
+
+TxSigResult checkTransactionSignaturesDecided(TransactionSigInfo const& tx, AccountSnapshot const& accounts,
+                                              uint32_t protocol, SignatureBatchPrefetch const& pre, size_t body,
+                                              bool forApply) {
+  DecidedChecker checker(protocol, tx.signatures, pre, body);
+  return walkTransaction(
+      tx, accounts, protocol, forApply,
+      [&](std::vector<Signer> const& signers, int32_t needed) { return checker.check(signers, needed); },
+      [&] { return checker.allUsed(); });
+}
+
+TxSigResult checkFeeBumpSignaturesDecided(FeeBumpSigInfo const& tx, AccountSnapshot const& accounts,
+                                          uint32_t protocol, SignatureBatchPrefetch const& pre, size_t outerBody,
+                                          size_t innerBody, bool forApply) {
+  TxSigResult r;
+  if (protocol < 13) {
+    r.code = txNOT_SUPPORTED;
+    return r;
+  }
+  DecidedChecker checker(protocol, tx.signatures, pre, outerBody);
+  AccountSigState const* fee = find(accounts, tx.feeSource);
+  if (!fee) {
+    r.code = txNO_ACCOUNT;
+    return r;
+  }
+  if (!checker.check(accountSigners(*fee), (int32_t)fee->thresholds[THRESHOLD_LOW_LEVEL])) {
+    r.code = txBAD_AUTH;
+    return r;
+  }
+  if (!checker.allUsed()) {
+    r.code = txBAD_AUTH_EXTRA;
+    return r;
+  }
+  TxSigResult inner = checkTransactionSignaturesDecided(tx.inner, accounts, protocol, pre, innerBody, forApply);
   r.code = inner.code == txSUCCESS ? txFEE_BUMP_INNER_SUCCESS : txFEE_BUMP_INNER_FAILED;
   r.innerCode = inner.code;
   r.failedOp = inner.failedOp;

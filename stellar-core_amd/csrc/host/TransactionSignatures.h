@@ -111,6 +111,33 @@ TxSigResult checkTransactionSignatures(TransactionSigInfo const& tx, AccountSnap
 TxSigResult checkFeeBumpSignatures(FeeBumpSigInfo const& tx, AccountSnapshot const& accounts, uint32_t protocol,
                                    SignatureBatchPrefetch const* prefetched = nullptr, bool forApply = false);
 
+// The checkSignature calls checkTransactionSignatures makes for `tx`, in its
+// order, as long as every one passes: the source account at LOW, the extra
+// signers (protocol >= 19), then each operation -- its source account at the
+// operation's level, or the no-account single-key check with needed 0.  Empty
+// when the source account is missing (txNO_ACCOUNT is decided without a check);
+// an operation of a missing transaction source adds none (opNO_ACCOUNT).
+std::vector<SignatureCheck> listTransactionChecks(TransactionSigInfo const& tx, AccountSnapshot const& accounts,
+                                                  uint32_t protocol, bool forApply = false);
+// ... and the one check of a fee bump's outer envelope: the fee source at LOW
+// (none without the account).
+std::vector<SignatureCheck> listFeeBumpOuterChecks(FeeBumpSigInfo const& tx, AccountSnapshot const& accounts);
+
+// The two check functions over decisions instead of a SignatureChecker: `pre`
+// is a prefetch whose runDecided has run, `body` / `outerBody` / `innerBody`
+// the addDecided indices of the transaction's bodies, added with the lists
+// above.  Result codes come from the first failing check in order; the used
+// marks are ORed over the transaction's checks and consulted only when every
+// check passed (exactly when the reference had run them all); a check that
+// came back false and has signed-payload signers continues on the host from
+// its weight and marks (SignatureUtils::verifyEd25519SignedPayload).
+TxSigResult checkTransactionSignaturesDecided(TransactionSigInfo const& tx, AccountSnapshot const& accounts,
+                                              uint32_t protocol, SignatureBatchPrefetch const& pre, size_t body,
+                                              bool forApply = false);
+TxSigResult checkFeeBumpSignaturesDecided(FeeBumpSigInfo const& tx, AccountSnapshot const& accounts,
+                                          uint32_t protocol, SignatureBatchPrefetch const& pre, size_t outerBody,
+                                          size_t innerBody, bool forApply = false);
+
 // Adds every (signature, signer) pair the checks of `tx` can reach.  With a
 // body (SignatureBatchPrefetch's body form) the contents hash is not read: it
 // is the hash of that body, delivered by runBodies; with `hinted` the body goes

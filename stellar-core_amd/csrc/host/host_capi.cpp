@@ -478,9 +478,9 @@ int checkEnvelopes(const svh_envelope* env, size_t n, const svh_decorated_sig* s
                    const EnvelopeBodies* eb) {
   try {
     if (eb) {
-      if (prefetch != 0 && prefetch != 1 && prefetch != 3)
+      if (prefetch != 0 && prefetch != 1 && prefetch != 3 && prefetch != 5)
         throw std::invalid_argument(
-            "svh_check_envelopes_bodies: prefetch must be 0, 1 or 3 (no keyed, cache-seeding form)");
+            "svh_check_envelopes_bodies: prefetch must be 0, 1, 3 or 5 (no keyed, cache-seeding form)");
       if (!eb->networkID || !eb->contentsHashOut || !eb->feeBumpHashOut || (n && !eb->body))
         throw std::invalid_argument("svh_check_envelopes_bodies: null argument");
       for (size_t t = 0; t < n; ++t) {
@@ -528,7 +528,48 @@ int checkEnvelopes(const svh_envelope* env, size_t n, const svh_decorated_sig* s
       }
     }
     SignatureBatchPrefetch pre;
-    if (prefetch && eb) {
+    // prefetch 5: every transaction's checks go to the engine with its bodies
+    // and come back decided.  An envelope the engine does not take (addDecided:
+    // more than 64 signatures or 64 signers in a check) is checked by a plain
+    // SignatureChecker over host-computed hashes, it alone; protocol 7 (every
+    // check is true without looking) takes that path for the whole call.
+    constexpr size_t kPlain = ~size_t(0);
+    std::vector<size_t> innerBody, outerBody;
+    bool decidedRun = false;
+    if (prefetch == 5 && eb) {
+      auto at = [&](uint64_t off) { return eb->blob ? eb->blob + off : nullptr; };
+      innerBody.assign(n, kPlain);
+      outerBody.assign(n, kPlain);
+      size_t nbodies = 0;
+      for (size_t t = 0; t < n; ++t) {
+        svh_envelope_body const& b = eb->body[t];
+        const bool bump = env[t].fee_bump != 0;
+        bool taken = protocol != 7;
+        // (a fee bump below protocol 13 is txNOT_SUPPORTED before any check: its bodies go in for their hashes)
+        if (taken && bump) {
+          const SignatureBatchPrefetch::TxBody outer{b.outer_off, b.outer_len, 2, &txs[t].contentsHash};
+          taken = pre.addDecided(outer, txs[t].signatures,
+                                 protocol >= 13 ? listFeeBumpOuterChecks(txs[t], snap) : std::vector<SignatureCheck>());
+          if (taken) outerBody[t] = nbodies++;
+        }
+        if (taken) {
+          const SignatureBatchPrefetch::TxBody inner{b.off, b.len, (uint8_t)b.kind, &txs[t].inner.contentsHash};
+          taken = pre.addDecided(inner, txs[t].inner.signatures,
+                                 !bump || protocol >= 13
+                                     ? listTransactionChecks(txs[t].inner, snap, protocol, for_apply != 0)
+                                     : std::vector<SignatureCheck>());
+          if (taken) innerBody[t] = nbodies++;
+        }
+        if (!taken) {
+          // (an outer body already added stays in the batch: only its hash slot is written twice)
+          innerBody[t] = kPlain;
+          txs[t].inner.contentsHash = hostContentsHash(eb->networkID, b.kind, at(b.off), b.len);
+          if (bump) txs[t].contentsHash = hostContentsHash(eb->networkID, 2, at(b.outer_off), b.outer_len);
+        }
+      }
+      pre.runDecided(eb->networkID, eb->blob, protocol);
+      decidedRun = true;
+    } else if (prefetch && eb) {
       // the catchup form: pairs enumerated without the hashes (prefetch 3: by
       // the engine, from hints and candidate keys), one engine call from the
       // bodies to the verdicts, the digests taken as the hashes
@@ -554,12 +595,20 @@ int checkEnvelopes(const svh_envelope* env, size_t n, const svh_decorated_sig* s
         std::memcpy(eb->contentsHashOut + 32 * t, txs[t].inner.contentsHash.data(), 32);
         std::memcpy(eb->feeBumpHashOut + 32 * t, txs[t].contentsHash.data(), 32);  // (zeros without a fee bump)
       }
-    if (prefetched_pairs) *prefetched_pairs = pre.pairs();
+    if (prefetched_pairs) *prefetched_pairs = decidedRun ? pre.decidedChecks() : pre.pairs();
     SignatureBatchPrefetch const* p = prefetch ? &pre : nullptr;
     auto check = [&](size_t a, size_t b) {
       for (size_t t = a; t < b; ++t) {
-        TxSigResult r = env[t].fee_bump ? checkFeeBumpSignatures(txs[t], snap, protocol, p, for_apply != 0)
-                                        : checkTransactionSignatures(txs[t].inner, snap, protocol, p, for_apply != 0);
+        TxSigResult r;
+        if (decidedRun && innerBody[t] != kPlain)
+          r = env[t].fee_bump ? checkFeeBumpSignaturesDecided(txs[t], snap, protocol, pre, outerBody[t], innerBody[t],
+                                                              for_apply != 0)
+                              : checkTransactionSignaturesDecided(txs[t].inner, snap, protocol, pre, innerBody[t],
+                                                                  for_apply != 0);
+        else
+          r = env[t].fee_bump ? checkFeeBumpSignatures(txs[t], snap, protocol, decidedRun ? nullptr : p, for_apply != 0)
+                              : checkTransactionSignatures(txs[t].inner, snap, protocol, decidedRun ? nullptr : p,
+                                                           for_apply != 0);
         results[t].code = r.code;
         results[t].inner_code = r.innerCode;
         results[t].failed_op = r.failedOp;

@@ -464,6 +464,117 @@ inline void pair_pack(const HintIn& in, const PairChunk& c, uint8_t* h) {
   });
 }
 
+// sv_ed25519_check_txbodies: the hinted inputs plus each body's checks (signer
+// lists with weights, and the needed weight), all in CSR form.
+struct CheckIn {
+  HintIn h;
+  const uint8_t* sig_len;   // per signature, or nullptr: all 64
+  const uint64_t* cb;       // checks of body t: [cb[t], cb[t + 1])
+  const int32_t* need;      // per check
+  const uint64_t* gb;       // signers of check c: [gb[c], gb[c + 1])
+  const uint8_t* gtype;     // per signer
+  const uint32_t* gweight;
+  const uint32_t* gkey;     // global index into h.key
+};
+
+// One staging chunk of it: the hinted image of bodies [b0, b1) (PairChunk p,
+// bytes [0, p.bytes)) followed, 16-byte aligned, by the chunk's check tables
+// (nc checks [c0, c1), ng signers [g0, g1), m signatures):
+//   check_begin (8 (k + 1)) | signer_begin (8 (nc + 1)) | needed (4 nc) | signer_weight (4 ng) |
+//   signer_key (4 ng) | signer_type (ng) | sig_len (m, only with CheckIn::sig_len)
+// check_begin, signer_begin and signer_key are relative to c0 / g0 / p.k0.
+struct CheckChunk {
+  PairChunk p;
+  size_t c0, c1, g0, g1;
+  size_t o_cb, o_gb, o_need, o_gw, o_gk, o_gt, o_sl, bytes;
+};
+
+// The hinted image of exactly bodies [b0, b1): pair_plan's layout for a given run.
+inline PairChunk pair_chunk(const HintIn& in, size_t b0, size_t b1, size_t body_bytes) {
+  PairChunk c{};
+  c.b0 = b0;
+  c.b1 = b1;
+  c.s0 = (size_t)in.sb[b0];
+  c.s1 = (size_t)in.sb[b1];
+  c.k0 = (size_t)in.kb[b0];
+  c.k1 = (size_t)in.kb[b1];
+  c.body_bytes = body_bytes;
+  const size_t m = c.s1 - c.s0, q = c.k1 - c.k0, k = b1 - b0;
+  c.o_sig = 32 * q;
+  c.o_hint = c.o_sig + 64 * m;
+  c.o_off = al16(c.o_hint + 4 * m);
+  c.o_sb = c.o_off + 8 * k;
+  c.o_kb = c.o_sb + 8 * (k + 1);
+  c.o_len = c.o_kb + 8 * (k + 1);
+  c.o_kind = c.o_len + 4 * k;
+  c.o_body = al16(c.o_kind + k);
+  c.bytes = c.o_body + std::max<size_t>(body_bytes, 16);
+  return c;
+}
+
+// The chunks of bodies [B0, B1): pair_plan's runs of whole bodies, additionally
+// bounded by max_c checks and max_g signers (a body over a bound is a chunk
+// alone).
+inline std::vector<CheckChunk> check_plan(const CheckIn& in, size_t B0, size_t B1, size_t max_s, size_t max_k,
+                                          size_t max_b, size_t max_c, size_t max_g) {
+  std::vector<CheckChunk> out;
+  const HintIn& hi = in.h;
+  size_t t = B0;
+  while (t < B1) {
+    const size_t b0 = t, s0 = (size_t)hi.sb[t], k0 = (size_t)hi.kb[t], c0 = (size_t)in.cb[t], g0 = (size_t)in.gb[c0];
+    size_t bytes = 0;
+    do {
+      bytes += al16(hi.len[t]);
+      ++t;
+    } while (t < B1 && hi.sb[t + 1] - s0 <= max_s && hi.kb[t + 1] - k0 <= max_k && in.cb[t + 1] - c0 <= max_c &&
+             in.gb[in.cb[t + 1]] - g0 <= max_g && bytes + al16(hi.len[t]) <= max_b);
+    CheckChunk c{};
+    c.p = pair_chunk(hi, b0, t, bytes);
+    c.c0 = c0;
+    c.c1 = (size_t)in.cb[t];
+    c.g0 = g0;
+    c.g1 = (size_t)in.gb[c.c1];
+    const size_t k = t - b0, nc = c.c1 - c.c0, ng = c.g1 - c.g0, m = c.p.s1 - c.p.s0;
+    c.o_cb = al16(c.p.bytes);
+    c.o_gb = c.o_cb + 8 * (k + 1);
+    c.o_need = c.o_gb + 8 * (nc + 1);
+    c.o_gw = c.o_need + 4 * nc;
+    c.o_gk = c.o_gw + 4 * ng;
+    c.o_gt = c.o_gk + 4 * ng;
+    c.o_sl = c.o_gt + ng;
+    c.bytes = al16(c.o_sl + (in.sig_len ? m : 0) + 1);
+    out.push_back(c);
+  }
+  return out;
+}
+
+inline void check_pack(const CheckIn& in, const CheckChunk& c, uint8_t* h) {
+  pair_pack(in.h, c.p, h);
+  const size_t k = c.p.b1 - c.p.b0, nc = c.c1 - c.c0, ng = c.g1 - c.g0, m = c.p.s1 - c.p.s0;
+  uint64_t* cb = (uint64_t*)(h + c.o_cb);
+  uint64_t* gb = (uint64_t*)(h + c.o_gb);
+  uint32_t* gk = (uint32_t*)(h + c.o_gk);
+  cb[k] = in.cb[c.p.b1] - c.c0;
+  gb[nc] = in.gb[c.c1] - c.g0;
+  // the tables in parts of the pack pool: rebased CSR words and key indices, plain copies of the rest
+  Pool& pp = pack_pool();
+  const size_t parts = pack_parts(pp.size(), t_pack_parts, 8 * k + 12 * nc + 9 * ng + m, pack_part());
+  pp.run(parts, [&](size_t p) {
+    for (size_t i = k * p / parts; i < k * (p + 1) / parts; ++i) cb[i] = in.cb[c.p.b0 + i] - c.c0;
+    size_t a = nc * p / parts, b = nc * (p + 1) / parts;
+    for (size_t i = a; i < b; ++i) gb[i] = in.gb[c.c0 + i] - c.g0;
+    if (b > a) std::memcpy(h + c.o_need + 4 * a, in.need + c.c0 + a, 4 * (b - a));
+    a = ng * p / parts, b = ng * (p + 1) / parts;
+    if (b > a) {
+      std::memcpy(h + c.o_gw + 4 * a, in.gweight + c.g0 + a, 4 * (b - a));
+      for (size_t i = a; i < b; ++i) gk[i] = in.gkey[c.g0 + i] - (uint32_t)c.p.k0;
+      std::memcpy(h + c.o_gt + a, in.gtype + c.g0 + a, b - a);
+    }
+    a = m * p / parts, b = m * (p + 1) / parts;
+    if (in.sig_len && b > a) std::memcpy(h + c.o_sl + a, in.sig_len + c.p.s0 + a, b - a);
+  });
+}
+
 // Body boundaries of G slices of bodies [0, nb): boundary g is the body edge
 // whose signature count is nearest to g * n / G (ties: the lower edge), kept
 // non-decreasing.  cut[0] = 0, cut[G] = nb.

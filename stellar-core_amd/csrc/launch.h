@@ -1,6 +1,6 @@
 // The one declaration of every extern "C" launcher and size query that
 // crosses between the kernel files (sv_kernels.hip, sv_comb.hip, sv_hash.hip,
-// sv_txhash.hip, sv_txpair.hip), sv_cpu.cpp and the engine (sv_api.cpp and its modules).
+// sv_txhash.hip, sv_txpair.hip, sv_txcheck.hip), sv_cpu.cpp and the engine (sv_api.cpp and its modules).
 // Included by the callers and by every definer, so a changed parameter list
 // is a compile error instead of arguments corrupted at run time.
 #pragma once
@@ -24,6 +24,16 @@ int sv_txpairs_check(const uint8_t* network_id, const uint8_t* bodies, const uin
                      const uint8_t* key, size_t n_keys, size_t pair_cap, const uint64_t* pair_begin,
                      const uint32_t* pair_sig, const uint32_t* pair_key, const uint8_t* pair_verdict,
                      const size_t* n_pairs);
+// ... and of the check entry points (sv_cpu.cpp): the hinted inputs, sig_len,
+// the check tables of `checks` (every CSR array, signer types, key indices
+// inside their bodies, the 64-signature / 64-signer limits, the protocol) and
+// the three outputs.
+struct sv_txchecks;
+int sv_txchecks_check(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                      const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies, const uint64_t* sig_begin,
+                      const uint8_t* hint, const uint8_t* sig, size_t n_sigs, const uint64_t* key_begin,
+                      const uint8_t* key, size_t n_keys, const struct sv_txchecks* checks, const uint8_t* check_ok,
+                      const uint32_t* check_weight, const uint64_t* check_used);
 
 }  // extern "C"
 
@@ -70,6 +80,18 @@ hipError_t sv_launch_pair_fill(const uint64_t* sig_begin, const void* hint, cons
                                void* ws, uint64_t* pair_begin, uint64_t n_pairs, uint32_t* pair_sig,
                                uint32_t* pair_key, void* gkey, void* gsig, void* gmsg, const void* digests,
                                hipStream_t s);
+// one checkSignature decision per check (sv_txcheck.hip), after the pairing and the verify launch on the same
+// stream; sig_len may be nullptr (all 64)
+int sv_check_block(void);
+hipError_t sv_launch_txcheck(const uint64_t* sig_begin, const void* hint, const void* sig, const uint8_t* sig_len,
+                             uint64_t n_sigs, const uint64_t* key_begin, const void* key, uint64_t n_keys,
+                             uint64_t n_bodies, const uint64_t* pair_begin, const uint32_t* pair_sig,
+                             const uint32_t* pair_key, const void* pair_verdict, uint64_t n_pairs,
+                             const void* digests, const uint64_t* check_begin, const int32_t* check_needed,
+                             uint64_t n_checks, const uint64_t* signer_begin, const uint8_t* signer_type,
+                             const uint32_t* signer_weight, const uint32_t* signer_key, uint64_t n_signers,
+                             int clamp, uint8_t* check_ok, uint32_t* check_weight, uint64_t* check_used,
+                             hipStream_t s);
 // warm-key latency path (sv_comb.hip)
 size_t sv_comb_btab_bytes(void);
 size_t sv_key_slot_bytes(void);

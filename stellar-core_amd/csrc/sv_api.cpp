@@ -833,6 +833,118 @@ int sv_ed25519_verify_txbodies_hinted_device(int device, const uint8_t* network_
   return SV_OK;
 }
 
+int sv_ed25519_check_txbodies(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                              const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                              const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig, size_t n_sigs,
+                              const uint64_t* key_begin, const uint8_t* key, size_t n_keys, const sv_txchecks* checks,
+                              uint8_t* check_ok, uint32_t* check_weight, uint64_t* check_used, uint8_t* digests,
+                              const sv_opts* opts) {
+  LifeGuard life_;
+  int rc = check_opts(opts);
+  if (rc) return rc;
+  if (sv_txchecks_check(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, n_sigs,
+                        key_begin, key, n_keys, checks, check_ok, check_weight, check_used))
+    return fail(SV_ERR_INVALID_ARG,
+                "tx checks: null pointer, body kind > 2, malformed CSR array, signer type > 3, key index outside its "
+                "body, sig_len > 64, more than 64 signatures or signers in a check, or protocol 7");
+  if (n_bodies == 0) return SV_OK;
+  if ((rc = debug_fail())) return rc;
+  if ((rc = ensure_init())) return rc;
+  std::vector<Device*> devs;
+  if ((rc = select_devices(opts, n_sigs, devs))) return rc;
+  const int path = path_from_flags(opts ? opts->flags : 0u);
+  const CheckIn in{{network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, key_begin, key},
+                   checks->sig_len,      checks->check_begin,   checks->check_needed, checks->signer_begin,
+                   checks->signer_type, checks->signer_weight, checks->signer_key};
+  const int clamp = checks->protocol_version >= 10;
+  const CheckOut out{check_ok, check_weight, check_used, digests};
+  const size_t G = devs.size();
+  if (G == 1) return check_slice(*devs[0], in, 0, n_bodies, clamp, out, path);
+  // Slices of whole bodies: a body's checks are contiguous, so every slot
+  // writes its decisions straight into the caller's arrays.
+  const std::vector<size_t> cut = pair_slices(sig_begin, n_bodies, G);
+  return shard(devs, G, [&](Device& D, size_t g, size_t) {
+    if (cut[g] == cut[g + 1]) return SV_OK;
+    return check_slice(D, in, cut[g], cut[g + 1], clamp, out, path);
+  });
+}
+
+int sv_ed25519_check_txbodies_device(int device, const uint8_t* network_id, const void* d_bodies,
+                                     const uint64_t* d_body_off, const uint32_t* d_body_len,
+                                     const uint8_t* d_body_kind, size_t n_bodies, const uint64_t* d_sig_begin,
+                                     const void* d_hint, const void* d_sig, size_t n_sigs,
+                                     const uint64_t* d_key_begin, const void* d_key, size_t n_keys,
+                                     const sv_txchecks* ck, void* d_check_ok, uint32_t* d_check_weight,
+                                     uint64_t* d_check_used, void* d_digests, void* stream) {
+  LifeGuard life_;
+  if (!network_id || !ck || ck->struct_size < sizeof(sv_txchecks) ||
+      (n_bodies && (!d_bodies || !d_body_off || !d_body_len || !d_body_kind || !d_sig_begin || !d_key_begin ||
+                    !ck->check_begin)) ||
+      (n_sigs && (!d_hint || !d_sig)) || (n_keys && !d_key) ||
+      (ck->n_checks && (n_bodies == 0 || !ck->check_needed || !ck->signer_begin || !d_check_ok || !d_check_weight ||
+                        !d_check_used)) ||
+      (ck->n_signers && (!ck->signer_type || !ck->signer_weight || !ck->signer_key)))
+    return fail(SV_ERR_INVALID_ARG, "tx checks: null pointer");
+  if (ck->protocol_version == 7) return fail(SV_ERR_INVALID_ARG, "tx checks: protocol 7 needs no engine");
+  if ((uint64_t)n_sigs >> 32 || (uint64_t)n_keys >> 32)
+    return fail(SV_ERR_INVALID_ARG, "tx checks: 2^32 or more signatures or keys");
+  if (!aligned16(d_sig) || !aligned16(d_key) || !aligned16(d_digests) || ((uintptr_t)d_hint & 3u) ||
+      ((uintptr_t)ck->check_begin & 7u) || ((uintptr_t)ck->signer_begin & 7u) || ((uintptr_t)ck->check_needed & 3u) ||
+      ((uintptr_t)ck->signer_weight & 3u) || ((uintptr_t)ck->signer_key & 3u) || ((uintptr_t)d_check_weight & 3u) ||
+      ((uintptr_t)d_check_used & 7u))
+    return fail(SV_ERR_ALIGN, "sig/key/digests must be 16-byte aligned, hint and the check arrays naturally aligned");
+  int rc;
+  if ((rc = debug_fail())) return rc;
+  Device* Dp;
+  if ((rc = slot_arg(device, Dp))) return rc;
+  Device& D = *Dp;
+  if (n_bodies == 0) return SV_OK;
+  hipStream_t user = (hipStream_t)stream;
+  std::lock_guard<std::mutex> g(D.mu);
+  SV_HIP(hipSetDevice(D.phys));
+  if ((rc = ready_locked(D))) return rc;
+  // the pairing workspace, pair_begin, a digest array when the caller wants
+  // none, and the pinned word the count comes back in (growing drains the
+  // kernel stream)
+  const size_t wsb = al16(sv_pair_ws_bytes(n_bodies)), pbb = al16(8 * (n_bodies + 1));
+  const size_t need = wsb + pbb + (d_digests ? 0 : 32 * n_bodies);
+  if (need > D.txpair.cap) {
+    SV_HIP(hipStreamSynchronize(D.stream));
+    if ((rc = D.txpair.ensure(need))) return rc;
+  }
+  if ((rc = D.h_txcnt.ensure(64))) return rc;
+  uint64_t* d_pb = (uint64_t*)((uint8_t*)D.txpair.p + wsb);
+  void* dig = d_digests ? d_digests : (void*)((uint8_t*)D.txpair.p + wsb + pbb);
+  SV_HIP(hipEventRecord(D.dep_in, user));
+  SV_HIP(hipStreamWaitEvent(D.stream, D.dep_in, 0));
+  SV_HIP(sv_launch_txhash(D.grid * 8, network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, nullptr, 0,
+                          nullptr, dig, D.stream));
+  SV_HIP(sv_launch_pair_count(d_sig_begin, d_hint, d_sig, n_sigs, d_key_begin, d_key, n_keys, n_bodies, D.txpair.p,
+                              d_pb, D.stream));
+  SV_HIP(hipMemcpyAsync(D.h_txcnt.p, sv_pair_total(D.txpair.p, n_bodies), 8, hipMemcpyDeviceToHost, D.stream));
+  // the one wait: the number of pairs is only known on the device (the stream
+  // is idle afterwards, so the pair arrays may grow here)
+  SV_HIP(hipStreamSynchronize(D.stream));
+  const size_t np = (size_t)*(const uint64_t*)D.h_txcnt.p;
+  const size_t o_idx = al16(np);
+  if ((rc = ensure_txpairs(D, np)) || (rc = D.txchk.ensure(o_idx + 8 * np + 16))) return rc;
+  uint8_t* dv = (uint8_t*)D.txchk.p;
+  uint32_t* d_ps = (uint32_t*)(dv + o_idx);
+  uint32_t* d_pk = d_ps + np;
+  SV_HIP(sv_launch_pair_fill(d_sig_begin, d_hint, d_sig, n_sigs, d_key_begin, d_key, n_keys, n_bodies, D.txpair.p,
+                             d_pb, np, d_ps, d_pk, D.txpk.p, D.txsg.p, D.txmsg.p, dig, D.stream));
+  if (np && (rc = launch_locked(D, 0, SV_PATH_AUTO, D.txpk.p, D.txsg.p, D.txmsg.p, nullptr, nullptr, 32, np, dv,
+                                nullptr, kt_mode() == 1)))
+    return rc;
+  SV_HIP(sv_launch_txcheck(d_sig_begin, d_hint, d_sig, ck->sig_len, n_sigs, d_key_begin, d_key, n_keys, n_bodies, d_pb,
+                           d_ps, d_pk, dv, np, dig, ck->check_begin, ck->check_needed, ck->n_checks, ck->signer_begin,
+                           ck->signer_type, ck->signer_weight, ck->signer_key, ck->n_signers,
+                           ck->protocol_version >= 10, (uint8_t*)d_check_ok, d_check_weight, d_check_used, D.stream));
+  SV_HIP(hipEventRecord(D.dep_out, D.stream));
+  SV_HIP(hipStreamWaitEvent(user, D.dep_out, 0));
+  return SV_OK;
+}
+
 int sv_ed25519_verify_device(int device, const void* d_pk, const void* d_sig, const void* d_msg,
                              const uint64_t* d_msg_off, const uint32_t* d_msg_len, uint32_t fixed_msg_len,
                              size_t n, void* d_verdict, void* d_bitmap, void* stream) {
@@ -1076,7 +1188,7 @@ int sv_workspace_bytes(int device, size_t* bytes) {
   // (lock order: the lane's mutex before the slot's)
   std::lock_guard<std::mutex> gl(Dp->lat.mu);
   std::lock_guard<std::mutex> g(Dp->mu);
-  size_t b = Dp->ws.cap + Dp->txmsg.cap + Dp->txpk.cap + Dp->txsg.cap + Dp->txpair.cap;
+  size_t b = Dp->ws.cap + Dp->txmsg.cap + Dp->txpk.cap + Dp->txsg.cap + Dp->txpair.cap + Dp->txchk.cap;
   for (const LatCtx& c : Dp->lat.ctx) b += c.ws.cap + c.d_in.cap + c.d_out.cap + c.d_keys.cap;
   *bytes = b;
   return SV_OK;

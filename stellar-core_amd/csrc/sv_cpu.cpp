@@ -26,6 +26,7 @@
 #pragma GCC diagnostic push
 #pragma GCC diagnostic ignored "-Wunused-function"
 #include "txhash.h"
+#include "txcheck.h"
 #pragma GCC diagnostic pop
 
 #include <algorithm>
@@ -268,6 +269,118 @@ int sv_ed25519_verify_txbodies_hinted_cpu(const uint8_t* network_id, const uint8
     }
   return sv_ed25519_verify_batch_cpu(gpk.data(), gsig.data(), gmsg.data(), off.data(), len.data(), np, pair_verdict,
                                      threads);
+}
+
+// Argument check shared by the sv_ed25519_check_txbodies host-array entry
+// points (declared in launch.h): SV_OK or SV_ERR_INVALID_ARG.
+int sv_txchecks_check(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                      const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies, const uint64_t* sig_begin,
+                      const uint8_t* hint, const uint8_t* sig, size_t n_sigs, const uint64_t* key_begin,
+                      const uint8_t* key, size_t n_keys, const sv_txchecks* ck, const uint8_t* check_ok,
+                      const uint32_t* check_weight, const uint64_t* check_used) {
+  if (!network_id || !sig_begin || !key_begin || !ck || ck->struct_size < sizeof(sv_txchecks))
+    return SV_ERR_INVALID_ARG;
+  if (n_bodies && (!body_off || !body_len || !body_kind)) return SV_ERR_INVALID_ARG;
+  if ((uint64_t)n_sigs >> 32 || (uint64_t)n_keys >> 32) return SV_ERR_INVALID_ARG;
+  if ((n_sigs && (!hint || !sig)) || (n_keys && !key)) return SV_ERR_INVALID_ARG;
+  if (sig_begin[0] != 0 || sig_begin[n_bodies] != n_sigs) return SV_ERR_INVALID_ARG;
+  if (key_begin[0] != 0 || key_begin[n_bodies] != n_keys) return SV_ERR_INVALID_ARG;
+  const size_t nc = ck->n_checks, ng = ck->n_signers;
+  if (ck->protocol_version == 7) return SV_ERR_INVALID_ARG;
+  if (!ck->check_begin || !ck->signer_begin) return SV_ERR_INVALID_ARG;
+  if (nc && (!ck->check_needed || !check_ok || !check_weight || !check_used)) return SV_ERR_INVALID_ARG;
+  if (ng && (!ck->signer_type || !ck->signer_weight || !ck->signer_key)) return SV_ERR_INVALID_ARG;
+  if (ck->check_begin[0] != 0 || ck->check_begin[n_bodies] != nc) return SV_ERR_INVALID_ARG;
+  if (ck->signer_begin[0] != 0 || ck->signer_begin[nc] != ng) return SV_ERR_INVALID_ARG;
+  // per body: its CSR entries, signature lengths, limits, and per check of it
+  // the signer range, signer types and key indices (every pass here is linear
+  // in the batch, so large batches are threaded over bodies)
+  auto bodies_ok = [&](size_t t0, size_t t1) {
+    for (size_t t = t0; t < t1; ++t) {
+      if (sig_begin[t + 1] < sig_begin[t] || key_begin[t + 1] < key_begin[t] || body_kind[t] > 2) return false;
+      if (sig_begin[t + 1] > n_sigs || key_begin[t + 1] > n_keys) return false;
+      if (body_len[t] && !bodies) return false;
+      if (ck->sig_len)
+        for (uint64_t i = sig_begin[t]; i < sig_begin[t + 1]; ++i)
+          if (ck->sig_len[i] > 64) return false;
+      const uint64_t c0 = ck->check_begin[t], c1 = ck->check_begin[t + 1];
+      if (c1 < c0 || c1 > nc) return false;
+      if (c1 > c0 && sig_begin[t + 1] - sig_begin[t] > SV_TXCHECK_MAX) return false;
+      for (uint64_t c = c0; c < c1; ++c) {
+        const uint64_t g0 = ck->signer_begin[c], g1 = ck->signer_begin[c + 1];
+        if (g1 < g0 || g1 > ng || g1 - g0 > SV_TXCHECK_MAX) return false;
+        for (uint64_t g = g0; g < g1; ++g)
+          if (ck->signer_type[g] > 3 || ck->signer_key[g] < key_begin[t] || ck->signer_key[g] >= key_begin[t + 1])
+            return false;
+      }
+    }
+    return true;
+  };
+  const size_t T = std::max<size_t>(1, std::min<size_t>({(size_t)8, n_bodies / 16384,
+                                                         (size_t)std::max(1u, std::thread::hardware_concurrency())}));
+  if (T == 1) return bodies_ok(0, n_bodies) ? SV_OK : SV_ERR_INVALID_ARG;
+  std::vector<uint8_t> good(T, 0);
+  std::vector<std::thread> th;
+  for (size_t i = 1; i < T; ++i)
+    th.emplace_back([&, i] { good[i] = bodies_ok(n_bodies * i / T, n_bodies * (i + 1) / T) ? 1 : 0; });
+  good[0] = bodies_ok(0, n_bodies / T) ? 1 : 0;
+  for (auto& x : th) x.join();
+  for (uint8_t g : good)
+    if (!g) return SV_ERR_INVALID_ARG;
+  return SV_OK;
+}
+
+int sv_ed25519_check_txbodies_cpu(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                  const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                  const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig, size_t n_sigs,
+                                  const uint64_t* key_begin, const uint8_t* key, size_t n_keys,
+                                  const sv_txchecks* ck, uint8_t* check_ok, uint32_t* check_weight,
+                                  uint64_t* check_used, uint8_t* digests, int threads) {
+  int rc = sv_txchecks_check(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, n_sigs,
+                             key_begin, key, n_keys, ck, check_ok, check_weight, check_used);
+  if (rc) return rc;
+  if (n_bodies == 0) return SV_OK;
+  // the pairs and their verdicts through the hinted CPU form, the arrays sized by the bound
+  const size_t cap = sv_txbodies_pair_bound(sig_begin, key_begin, n_bodies);
+  std::vector<uint64_t> pb(n_bodies + 1);
+  std::vector<uint32_t> ps(cap + 1), pk(cap + 1);
+  std::vector<uint8_t> pv(cap + 1), own;
+  if (!digests) {
+    own.resize(32 * n_bodies);
+    digests = own.data();
+  }
+  size_t np = 0;
+  rc = sv_ed25519_verify_txbodies_hinted_cpu(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin,
+                                             hint, sig, n_sigs, key_begin, key, n_keys, cap, pb.data(), ps.data(),
+                                             pk.data(), pv.data(), &np, digests, threads);
+  if (rc) return rc;
+  const bool clamp = ck->protocol_version >= 10;
+  for (size_t t = 0; t < n_bodies; ++t) {
+    sv_txcheck_body b;
+    b.hint = hint;
+    b.sig = sig;
+    b.sig_len = ck->sig_len;
+    b.key = key;
+    b.pair_sig = ps.data();
+    b.pair_key = pk.data();
+    b.pair_verdict = pv.data();
+    b.digest = digests + 32 * t;
+    b.s0 = sig_begin[t];
+    b.ns = (uint32_t)(sig_begin[t + 1] - sig_begin[t]);
+    b.k0 = key_begin[t];
+    b.k1 = key_begin[t + 1];
+    b.p0 = pb[t];
+    b.p1 = pb[t + 1];
+    for (uint64_t c = ck->check_begin[t]; c < ck->check_begin[t + 1]; ++c) {
+      const uint64_t g0 = ck->signer_begin[c];
+      const sv_txcheck_result r = sv_txcheck<true>(b, ck->signer_type + g0, ck->signer_weight + g0, ck->signer_key + g0,
+                                             (uint32_t)(ck->signer_begin[c + 1] - g0), ck->check_needed[c], clamp);
+      check_ok[c] = (uint8_t)r.ok;
+      check_weight[c] = r.total;
+      check_used[c] = r.used;
+    }
+  }
+  return SV_OK;
 }
 
 int sv_ed25519_verify_cpu(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, size_t msg_len) {
