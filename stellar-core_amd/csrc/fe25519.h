@@ -14,9 +14,16 @@
 //
 // Bounds vocabulary ("M" = limb bound in units of 2^26 for even / 2^25 for odd
 // limbs):  R  = output of mul/sq/carry (M ~ 1),  fe_add(R,R) -> M2,
-// fe_sub(R,R) -> M3.  fe_mul/fe_sq accept inputs up to M3 (19 * 3 * 2^26 <
-// 2^32 for the premultiplied operand; column sums < 2^62.8).  Callers that
-// form 3-term expressions re-carry with fe_weak() (see ge25519.h).
+// fe_sub(R,R) -> M3, fe_sub4(R,M3) -> M5.  What a product accepts is set by
+// its g operand, whose limbs 1..9 are pre-multiplied by 19 (19 g_j < 2^32: even
+// limbs < 3.37 2^26, odd limbs < 6.73 2^25; limb 0 never is): g <= M3, or a
+// partially carried g (fe_weak_even: limbs 2, 4, 6, 8 R, limb 0 and the odd
+// limbs up to M6).  f may be M5.  The worst pair the code forms is the quad
+// doublings' X (M5) by T (M6 partially carried, quad.h): column sums < 2^62.9,
+// 19 g_odd = 0.892 2^32.  fe_sq takes <= M3 (the code hands it M2 at most),
+// fe_mul2 / fe_sq2 R+.  Callers that form longer expressions re-carry with
+// fe_weak() (see ge25519.h).  tests/fe_bounds.py derives both operands' bounds
+// at every call site; the CPU and GPU suites run each product there.
 //
 // Reference semantics restated: libsodium 1.0.18 fe25519_* as used by
 // crypto_sign_verify_detached (called from stellar-core
@@ -98,10 +105,13 @@ SV_HD void fe_weak(fe& h) {
 }
 
 // Carry of the even limbs 2, 4, 6, 8 only (into 3, 5, 7, 9): enough to use an
-// M5 value as a product's g operand.  g's limbs 1..9 are pre-multiplied by 19
-// (19 g_j < 2^32 needs g_even <= 3.37 2^26, g_odd <= 6.7 2^25; limb 0 never is),
-// so after this even limbs are R and odd ones <= 5 2^25 + 5; the column sums
-// stay < 2^63 with an M5 f operand (tests/test_host_arith.py fuzzes it).
+// M5 or M6 value as a product's g operand.  g's limbs 1..9 are pre-multiplied
+// by 19 (19 g_j < 2^32 needs g_even <= 3.37 2^26, g_odd <= 6.73 2^25; limb 0
+// never is), so after this even limbs are R and odd ones <= 5 2^25 + 2^17
+// (ge_dbl's T) or <= 6 2^25 + 2^18 + 1 (the quad doublings' T, whose 2 Z^2 is
+// M2); with an M5 f operand the column sums stay < 2^62.7 and < 2^62.9
+// (tests/fe_bounds.py; run at these bounds by tests/test_fe_asm_sim.py,
+// tests/test_host_arith.py and on the device by tests/test_gpu_devcore.py).
 SV_HD void fe_weak_even(fe& h) {
   SV_UNROLL for (int i = 2; i < 10; i += 2) {
     const uint32_t c = h.v[i] >> 26;
@@ -165,7 +175,7 @@ SV_HD void sv_mad(uint64_t& acc, uint32_t a, uint32_t b) { sv_mad_k(acc, a, b, 0
 // shift and one mask, and no separate 64-bit add per column (9 fewer per
 // product than summing the columns first and carrying after).  The price is one dependent chain per product instead of
 // ten interleaved accumulators.  Bounds: the carry (< 2^38) adds nothing
-// measurable to a column sum (< 2^62.8), and the output is R as above.
+// measurable to a column sum (< 2^62.9), and the output is R as above.
 // One column as ONE inline-asm statement (z: the first mad opens with 0, a:
 // with acc).  Per-mad statements cost an s_nop between every two dependent
 // ones: LLVM's gfx950 hazard recognizer assumes any inline asm may carry the

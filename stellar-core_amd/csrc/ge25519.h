@@ -18,7 +18,9 @@
 // stellar-core src/crypto/SecretKey.cpp:461-463).
 //
 // Limb-bound bookkeeping (see fe25519.h): every fe_mul/fe_sq input is <= M3,
-// except the f operand of the p1p1 conversions after a doubling (<= M5).
+// except, in the p1p1 conversions after a doubling, the f operand X (<= M5)
+// and the g operand T (M5 with its even limbs 2..8 carried, fe_weak_even).
+// tests/fe_bounds.py lists both operands' bounds at every call site.
 #pragma once
 
 #include "fe25519.h"
@@ -39,11 +41,12 @@ SV_HD void ge_p2_identity(ge_p2& p) {
   fe_1(p.Z);
 }
 
-// r = 2p.  Inputs R.  Outputs: X M5, Y M2, Z M3, T R+.
+// r = 2p.  Inputs R+.  Outputs: X M5, Y M2, Z M3, T M5 with limbs 2, 4, 6, 8
+// carried (limb 0 <= 5 2^26, odd limbs <= 5 2^25 + 2^17).
 // X is left at M5 (one carry pass saved per doubling): the conversions only
 // ever use p1p1 X as the f operand of fe_mul, which tolerates M5 (fe25519.h
 // header; fuzzed at the bound in tests/test_host_arith.py), never as the
-// 19-premultiplied g operand, which needs <= M3.
+// 19-premultiplied g operand, which needs even limbs <= M3.
 SV_HD void ge_dbl(ge_p1p1& r, const fe& X, const fe& Y, const fe& Z) {
   fe XX, YY, ZZ2, A, AA;
   fe_add(A, X, Y);

@@ -12,9 +12,14 @@
 //
 // with the results exchanged by DPP quad broadcasts (v_mov_b32 quad_perm), so
 // every lane of the quad holds the whole point between operations.  The
-// formulas, the limb bounds and the operation order are exactly those of
-// ge_dbl / ge_add_preswapped / ge_p1p1_to_p3 (ge25519.h); only the assignment
-// of field operations to lanes differs, so verdicts are the per-lane path's.
+// formulas and the operation order are exactly those of ge_dbl /
+// ge_add_preswapped / ge_p1p1_to_p3 (ge25519.h); only the assignment of field
+// operations to lanes differs, so verdicts are the per-lane path's.  The limb
+// bounds are ge25519.h's too, with one exception: a doubling forms 2 Z^2 as
+// sq + sq (M2, where ge_dbl's fe_sq2 leaves R), so its T is M6 before
+// fe_weak_even, not M5: limb 0 <= 6 2^26, odd limbs <= 6 2^25 + 2^18 + 1.  It
+// is the g operand of the conversion products X T (X at M5) and Z T, within
+// what fe_mul takes (fe25519.h header; tests/fe_bounds.py).
 //
 // Lane role r = lane & 3 selects the operand of its field operation.
 #pragma once
@@ -70,7 +75,7 @@ __device__ __forceinline__ void qd_dbl(ge_p3& P, const qd_role& q, bool wantT) {
   fe_add(A, P.X, P.Y);
   fe_pick4(s, q, P.X, P.Y, P.Z, A);
   fe_sq(sq, s);
-  if (q.r2) fe_add(sq, sq, sq);  // 2 Z^2 (M2; the bound ge_dbl's fe_sub4 below accepts)
+  if (q.r2) fe_add(sq, sq, sq);  // 2 Z^2 (M2, so T below is M6: see the header)
   fe_from<0>(XX, sq);
   fe_from<1>(YY, sq);
   fe_from<2>(ZZ2, sq);
@@ -120,8 +125,9 @@ __device__ __forceinline__ void qd_add(ge_p3& P, const fe& mine, const qd_role& 
 // broadcasting every result to every lane and picking from four, and the
 // conversion products keep a fixed lane map (X, Y, Z, T on lanes 0..3), so
 // no step ever rebuilds the whole point until the end (qo_expand).  Same
-// field operations, operand order and bounds as ge_dbl / ge_add_preswapped /
-// ge_p1p1_to_p3 (ge25519.h), hence the same verdicts.
+// field operations and operand order as ge_dbl / ge_add_preswapped /
+// ge_p1p1_to_p3 (ge25519.h), hence the same verdicts; same bounds but for the
+// doubling's M6 T (header).
 
 // value of lane P<r> of this lane's quad, for lane r
 template <int P0, int P1, int P2, int P3>
@@ -160,7 +166,7 @@ __device__ __forceinline__ void qo_dbl(fe& h, const qd_role& q) {
   fe_add(s, x, y);  // X + Y (M2)
   SV_UNROLL for (int i = 0; i < 10; ++i) s.v[i] = q.r3 ? s.v[i] : h.v[i];
   fe_sq(sq, s);
-  if (q.r2) fe_add(sq, sq, sq);  // 2 Z^2 (M2; the bound ge_dbl's fe_sub4 below accepts)
+  if (q.r2) fe_add(sq, sq, sq);  // 2 Z^2 (M2, so T below is M6: see the header)
   fe XX, YY, u, w;
   fe_from<0>(XX, sq);
   fe_from<1>(YY, sq);
@@ -170,7 +176,7 @@ __device__ __forceinline__ void qo_dbl(fe& h, const qd_role& q) {
   fe_add(Yp, YY, XX);   // y^2 + x^2            M2
   fe_sub(Zp, YY, XX);   // y^2 - x^2            M3
   fe_sub4(Xp, u, Yp);   // 2xy (lanes 0, 3)     M5
-  fe_sub4(Tp, w, Zp);   // (lanes 0, 2)         M5
+  fe_sub4(Tp, w, Zp);   // (lanes 0, 2)         M6
   fe_weak_even(Tp);  // (T: a conversion product's g operand only)
   // lane 0 X'T', 1 Y'Z', 2 Z'T', 3 X'Y' (p1p1 X is always the f operand)
   fe f, g;

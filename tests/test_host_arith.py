@@ -265,6 +265,26 @@ def test_lattice_reduce_invariants(hostcore):
     assert long_pairs <= 12  # only the hand-picked degenerate h need long pairs
 
 
+def test_lattice_reduce_near_exact_quotients(hostcore):
+    """h = ceil(8L / q) + d makes the first quotient 8L / h = q - (tiny), which
+    a double rounds UP to q: the exact Euclid step is right only because it
+    under-estimates its quotient (the 1 - 2^-40 factor).  For odd q the pair
+    is known in closed form, (c0, c1) = (q h - 8L, +q)."""
+    from test_gpu_devcore import near_exact_h
+    c0 = ctypes.create_string_buffer(32)
+    c1 = ctypes.create_string_buffer(32)
+    neg = ctypes.c_int()
+    for q, h in near_exact_h():
+        nb = hostcore.hc_lattice_reduce(h.to_bytes(32, "little"), c0, c1, ctypes.byref(neg))
+        a = int.from_bytes(c0.raw, "little")
+        b = int.from_bytes(c1.raw, "little")
+        sb = -b if neg.value else b
+        assert (a - sb * h) % N8 == 0 and b % 2 == 1, (q, h)
+        assert nb == max(a.bit_length(), b.bit_length(), 1), (q, h)
+        if q & 1:
+            assert (a, sb) == (q * h - N8, q), (q, h)
+
+
 def test_lattice_reduce_pinned_outputs(hostcore):
     """The exact (c0, c1, sign, bit length) of every h in a fixed 20,012-value
     set, as a digest recorded from the round-3/4 implementation: a rewrite of
@@ -344,3 +364,46 @@ def test_madcount_constants_match_generated_products():
     for name, c in counts.items():
         want = const["SV_MADS_SQ"] if name.startswith("fe_sq") else const["SV_MADS_MUL"]
         assert c == want, (name, c, want)
+
+
+# ------------------------------------- the bounds of the real call sites (tests/fe_bounds.py)
+def test_fe_cm_forms_at_call_site_maxima(hostcore):
+    """fe_mul_cm / fe_sq_cm (the host build's products, and the device's with
+    -DSV_FE_ASM_ON=0) at the limb-wise maximum over each form's call sites:
+    the quad doublings' M6 partially carried g operand with an M5 f operand
+    for fe_mul, the R+ operands of fe_mul2 / fe_sq2, X + Y for fe_sq."""
+    import fe_bounds as fb
+    o = (ctypes.c_uint32 * 8)()
+    u10 = ctypes.c_uint32 * 10
+    for fn, dbl in (("fe_mul", 0), ("fe_mul_g19", 0), ("fe_mul2", 1), ("fe_sq", 0), ("fe_sq2", 1)):
+        rnd = random.Random("cm" + fn)
+        fbound, gbound = fb.function_max(fn)
+        for trial in range(400):
+            if trial < 200:
+                cut = 0 if trial == 0 else 2**8
+                lf = [b - rnd.randint(0, cut) for b in fbound]
+                lg = None if gbound is None else [b - rnd.randint(0, cut) for b in gbound]
+            else:
+                lf = [rnd.randint(0, b) for b in fbound]
+                lg = None if gbound is None else [rnd.randint(0, b) for b in gbound]
+            if gbound is None:
+                hostcore.hc_fe_sq_limbs(o, u10(*lf), dbl)
+                assert _words(o) == (1 + dbl) * _val(lf) ** 2 % P, (fn, lf)
+            else:
+                hostcore.hc_fe_mul_limbs(o, u10(*lf), u10(*lg), dbl)
+                assert _words(o) == (1 + dbl) * _val(lf) * _val(lg) % P, (fn, lf, lg)
+
+
+def test_devcore_exports_every_probe():
+    """tests/native/libdevcore.so (the probe kernels of tests/test_gpu_devcore.py,
+    built for gfx950) builds here and exports every dc_* entry point the GPU
+    tests call: a build break shows up before the GPU run."""
+    import os
+    import subprocess
+    import test_gpu_devcore
+    d = os.path.join(REPO, "tests", "native")
+    subprocess.run(["make", "-s", "libdevcore.so"], cwd=d, check=True)
+    out = subprocess.run(["nm", "-D", "--defined-only", os.path.join(d, "libdevcore.so")], check=True,
+                         stdout=subprocess.PIPE, text=True).stdout
+    exported = {ln.split()[-1] for ln in out.splitlines() if ln.split()[-1].startswith("dc_")}
+    assert exported == {"dc_" + k for k in test_gpu_devcore.PROBES}
