@@ -232,7 +232,13 @@ int svh_check_envelopes(const svh_envelope* env, size_t n, const svh_decorated_s
  *               svh_engine_stats.fallbacks).  An envelope beyond the engine's
  *               limits (64 signatures, 64 signers in a check) is checked as
  *               under prefetch 0, it alone; at protocol 7 the whole call is.
- *               Results and hashes as prefetch 0. */
+ *               Results and hashes as prefetch 0.
+ *   prefetch 6  prefetch 5 with the signed-payload signers sent along as the
+ *               bodies' payload candidates (sv_txchecks_payload): the engine
+ *               pairs them by their XORed hint, verifies the pairs over the
+ *               payloads and runs the fourth stage, so every decision is final
+ *               and no check continues on the host.  Fallback, limits and
+ *               results as prefetch 5. */
 typedef struct svh_envelope_body {
   uint64_t off;
   uint32_t len;

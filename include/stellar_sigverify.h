@@ -395,7 +395,8 @@ int sv_ed25519_verify_txbodies_hinted_cpu(const uint8_t* network_id, const uint8
  *                    read verdicts)
  *   checks           the tables below
  *   check_ok         out, n_checks bytes: 1 if the check succeeded within the
- *                    PRE_AUTH_TX / HASH_X / ED25519 stages
+ *                    PRE_AUTH_TX / HASH_X / ED25519 stages (with the payload
+ *                    tables, below: within all four)
  *   check_weight     out, n_checks: the weight accumulated by those stages
  *                    (saturated at 2^32 - 1)
  *   check_used       out, n_checks: bit s set iff the check marked the body's
@@ -403,20 +404,40 @@ int sv_ed25519_verify_txbodies_hinted_cpu(const uint8_t* network_id, const uint8
  *                    independent: a body's used set is the OR over its checks
  *   digests          optional, n_bodies x 32 bytes out
  *
- * ED25519_SIGNED_PAYLOAD signers (type 3) are accepted and skipped: they come
- * last in the reference, so for a check that came back 0 the caller continues
- * on the host from check_weight and the marks.  With needed <= 0 a check
- * without any match is still 0, as in the reference.  A check considers at
- * most 64 signers and a body at most 64 signatures.
+ * ED25519_SIGNED_PAYLOAD signers (type 3) come last in the reference.  Without
+ * the payload tables (a plain sv_txchecks, or an sv_txchecks_payload whose
+ * pkey_begin == NULL) they are accepted and skipped: for a check that came back 0 the
+ * caller continues on the host from check_weight and the marks.  With the
+ * tables the engine runs that fourth stage too (CAP-40,
+ * SignatureUtils::verifyEd25519SignedPayload): each body has a second candidate
+ * list, its signed-payload candidates (key, payload, payload length), a type-3
+ * signer's signer_key is a global index into it, and a signer matches a
+ * signature iff the signature's hint equals hint(key) XOR hint(payload)
+ * (hint(payload): its last 4 bytes, or all of it followed by zeros when it is
+ * shorter), the signature is 64 bytes long and it verifies over the payload
+ * under the key.  The stage runs after the ED25519 stage with the weight carried
+ * over, only if that stage did not succeed, at every protocol version (the
+ * reference has no gate there), and check_ok / check_weight / check_used are
+ * then the state after all four stages.  The (signature, payload candidate)
+ * pairs are made by hint on the device (csrc/sv_txpair.hip) and verified by a
+ * second, variable-length launch; like the ed25519 pairs they never leave the
+ * engine.  A call whose tables are absent or hold no candidate launches and
+ * copies exactly what it did before the tables existed.
+ * With needed <= 0 a check without any match is still 0, as in the reference.
+ * A check considers at most 64 signers and a body at most 64 signatures.
  *
  * The host forms validate everything before any device work
  * (SV_ERR_INVALID_ARG): a null required pointer, a malformed CSR array, a
  * signer type > 3, a key index outside its body's key range, a sig_len > 64, a
  * body with checks and more than 64 signatures, a check with more than 64
- * signers, protocol_version 7 (every check is true there without the engine).
+ * signers, protocol_version 7 (every check is true there without the engine);
+ * with the payload tables also a malformed pkey_begin, a pkey_len > 64, a null
+ * table with n_pkeys > 0, n_pkeys >= 2^32 and a type-3 signer whose index lies
+ * outside its body's payload candidates.
  * Host buffers: chunks of whole bodies as in the hinted call, additionally
  * bounded by checks (SV_STAGE_CHUNK) and signers (8 x SV_STAGE_CHUNK); only the three check
- * arrays and the digests come back.  With opts->device == -1 the bodies are
+ * arrays and the digests come back; a chunk carries its bodies' payload
+ * candidates, which count towards its key bound.  With opts->device == -1 the bodies are
  * sliced as in the hinted call and each slot writes its checks' results
  * straight into the caller's arrays. */
 typedef struct sv_txchecks {
@@ -432,6 +453,20 @@ typedef struct sv_txchecks {
   size_t n_checks;
   size_t n_signers;
 } sv_txchecks;
+/* sv_txchecks extended at its end by the payload tables.  A caller that has them fills this struct, sets
+ * checks.struct_size = sizeof(sv_txchecks_payload) and passes &checks to the entry points below; every one of them
+ * accepts struct_size >= sizeof(sv_txchecks) and reads the tables only when struct_size covers them and
+ * pkey_begin != NULL.  (The extension has a name of its own so that a caller written against sv_txchecks, which
+ * sets struct_size = sizeof(sv_txchecks) and may leave no zeroed bytes behind it, means the same after it is
+ * recompiled.)  With the tables a type-3 signer's signer_key is a global index into pkey, inside its body's range. */
+typedef struct sv_txchecks_payload {
+  sv_txchecks checks;
+  const uint64_t* pkey_begin;    /* n_bodies + 1: body t's payload candidates are pkey_begin[t] .. pkey_begin[t+1]-1 */
+  const uint8_t* pkey;           /* n_pkeys x 32: signedPayload.ed25519 */
+  const uint8_t* pkey_payload;   /* n_pkeys x 64: signedPayload.payload, rows zero-padded */
+  const uint8_t* pkey_len;       /* n_pkeys: payload length, <= 64 */
+  size_t n_pkeys;
+} sv_txchecks_payload;
 #define SV_SIGNER_KEY_ED25519 0
 #define SV_SIGNER_KEY_PRE_AUTH_TX 1
 #define SV_SIGNER_KEY_HASH_X 2
@@ -450,7 +485,10 @@ int sv_ed25519_check_txbodies(const uint8_t* network_id /* 32 B */, const uint8_
  * is enqueued after the verify launch and the call returns without waiting for
  * either.  The device arrays are not validated: every CSR range and key index
  * is clamped to its array (an out-of-range key index matches nothing, a check
- * no body owns is 0), and nothing is written outside the three outputs. */
+ * no body owns is 0; a pkey_len above 64 is read as 64), and nothing is written
+ * outside the three outputs.  With payload candidates the payload pairing runs
+ * beside the ed25519 pairing and both counts come back in the one wait; pkey and
+ * pkey_payload are 16-byte aligned. */
 int sv_ed25519_check_txbodies_device(int device, const uint8_t* network_id /* host, 32 B */, const void* d_bodies,
                                      const uint64_t* d_body_off, const uint32_t* d_body_len,
                                      const uint8_t* d_body_kind, size_t n_bodies, const uint64_t* d_sig_begin,

@@ -110,7 +110,11 @@ class sv_txchecks(ctypes.Structure):
                 ("sig_len", ctypes.c_void_p), ("check_begin", ctypes.c_void_p), ("check_needed", ctypes.c_void_p),
                 ("signer_begin", ctypes.c_void_p), ("signer_type", ctypes.c_void_p),
                 ("signer_weight", ctypes.c_void_p), ("signer_key", ctypes.c_void_p),
-                ("n_checks", ctypes.c_size_t), ("n_signers", ctypes.c_size_t)]
+                ("n_checks", ctypes.c_size_t), ("n_signers", ctypes.c_size_t),
+                # sv_txchecks_payload: the same struct extended by the payload tables (read only when struct_size
+                # covers them and pkey_begin is set)
+                ("pkey_begin", ctypes.c_void_p), ("pkey", ctypes.c_void_p), ("pkey_payload", ctypes.c_void_p),
+                ("pkey_len", ctypes.c_void_p), ("n_pkeys", ctypes.c_size_t)]
 
 
 class FeedStats(ctypes.Structure):
@@ -542,10 +546,15 @@ def verify_txbodies_hinted_device(device: int, network_id, d_bodies: int, d_body
 
 
 def _checks_desc(protocol_version, sig_len, check_begin, check_needed, signer_begin, signer_type, signer_weight,
-                 signer_key, n_checks, n_signers):
-    """sv_txchecks over raw addresses (host arrays' or device pointers)."""
+                 signer_key, n_checks, n_signers, payload=None):
+    """sv_txchecks over raw addresses (host arrays' or device pointers).
+    payload: (pkey_begin, pkey, pkey_payload, pkey_len, n_pkeys) or None -- then
+    the struct is the one without the payload tables, by its struct_size."""
     ck = sv_txchecks()
-    ck.struct_size = ctypes.sizeof(sv_txchecks)
+    ck.struct_size = ctypes.sizeof(sv_txchecks) if payload is not None else sv_txchecks.pkey_begin.offset
+    if payload is not None:
+        ck.pkey_begin, ck.pkey, ck.pkey_payload, ck.pkey_len = (x or None for x in payload[:4])
+        ck.n_pkeys = int(payload[4])
     ck.protocol_version = int(protocol_version)
     ck.sig_len = sig_len or None
     ck.check_begin, ck.check_needed, ck.signer_begin = check_begin or None, check_needed or None, signer_begin or None
@@ -556,7 +565,7 @@ def _checks_desc(protocol_version, sig_len, check_begin, check_needed, signer_be
 
 def _check_host(fn, last, network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, key_begin, key,
                 check_begin, check_needed, signer_begin, signer_type, signer_weight, signer_key, sig_len,
-                protocol_version):
+                protocol_version, pkey_begin=None, pkey=None, pkey_payload=None, pkey_len=None):
     nid, bodies, off, ln, kind, nb, sb, hint, sig, ns, kb, key, nk = _hinted_args(
         network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, key_begin, key)
     cb = _csr(check_begin, nb, "check_begin")
@@ -575,8 +584,19 @@ def _check_host(fn, last, network_id, bodies, body_off, body_len, body_kind, sig
         if sl.shape[0] != ns:
             raise ValueError("sig_len must hold one byte per signature")
     a = lambda x: x.__array_interface__["data"][0]  # noqa: E731
+    payload = None
+    if pkey_begin is not None:
+        qb = _csr(pkey_begin, nb, "pkey_begin")
+        qk, qp = _u8(pkey if pkey is not None else [], 32), _u8(pkey_payload if pkey_payload is not None else [], 64)
+        ql = np.ascontiguousarray(np.asarray(pkey_len if pkey_len is not None else [], dtype=np.uint8).reshape(-1))
+        nq = qk.shape[0]
+        if qp.shape[0] != nq or ql.shape[0] != nq:
+            raise ValueError("pkey / pkey_payload / pkey_len row mismatch")
+        payload = (a(qb), a(qk) if nq else 0, a(qp) if nq else 0, a(ql) if nq else 0, nq)
+    elif pkey is not None or pkey_payload is not None or pkey_len is not None:
+        raise ValueError("payload tables need pkey_begin")
     ck = _checks_desc(protocol_version, a(sl) if sl is not None else 0, a(cb), a(need), a(gb), a(gt), a(gw), a(gk),
-                      nc, ng)
+                      nc, ng, payload)
     ok, weight, used = np.zeros(nc, np.uint8), np.zeros(nc, np.uint32), np.zeros(nc, np.uint64)
     dig = np.zeros((nb, 32), np.uint8)
     _check(fn(_ptr(nid), _ptr(bodies), _ptr(off), _ptr(ln), _ptr(kind), nb, _ptr(sb), _ptr(hint), _ptr(sig), ns,
@@ -586,28 +606,35 @@ def _check_host(fn, last, network_id, bodies, body_off, body_len, body_kind, sig
 
 def check_txbodies(network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, key_begin, key,
                    check_begin, check_needed, signer_begin, signer_type, signer_weight, signer_key, sig_len=None,
-                   protocol_version: int = 21, device: int = -1, max_devices: int = 0, path=None):
+                   protocol_version: int = 21, device: int = -1, max_devices: int = 0, path=None, pkey_begin=None,
+                   pkey=None, pkey_payload=None, pkey_len=None):
     """Signature checks decided on the device (sv_ed25519_check_txbodies): the
     inputs of verify_txbodies_hinted plus body t's checks check_begin[t]..
     check_begin[t+1]-1, each a needed weight and the signers signer_begin[c]..
     signer_begin[c+1]-1 (type, weight, global key index).  Returns (check_ok,
     check_weight, check_used, digests): one SignatureChecker::checkSignature
     decision per check, the weight it accumulated and the mask of the body's
-    signatures it marked used."""
+    signatures it marked used.  With the payload tables (pkey_begin: CSR over
+    the bodies; pkey n x 32, pkey_payload n x 64 zero-padded, pkey_len n) a
+    type-3 signer's key is a global index into pkey and the decision includes
+    the ED25519_SIGNED_PAYLOAD stage; without them type-3 signers are skipped."""
     lib = load_library()
     return _check_host(lib.sv_ed25519_check_txbodies, _opts(device, max_devices, path), network_id, bodies, body_off,
                        body_len, body_kind, sig_begin, hint, sig, key_begin, key, check_begin, check_needed,
-                       signer_begin, signer_type, signer_weight, signer_key, sig_len, protocol_version)
+                       signer_begin, signer_type, signer_weight, signer_key, sig_len, protocol_version, pkey_begin,
+                       pkey, pkey_payload, pkey_len)
 
 
 def check_txbodies_cpu(network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, key_begin, key,
                        check_begin, check_needed, signer_begin, signer_type, signer_weight, signer_key, sig_len=None,
-                       protocol_version: int = 21, threads: int = 0):
+                       protocol_version: int = 21, threads: int = 0, pkey_begin=None, pkey=None, pkey_payload=None,
+                       pkey_len=None):
     """The same on the engine's CPU path (what a caller runs on an engine error)."""
     lib = load_library()
     return _check_host(lib.sv_ed25519_check_txbodies_cpu, int(threads), network_id, bodies, body_off, body_len,
                        body_kind, sig_begin, hint, sig, key_begin, key, check_begin, check_needed, signer_begin,
-                       signer_type, signer_weight, signer_key, sig_len, protocol_version)
+                       signer_type, signer_weight, signer_key, sig_len, protocol_version, pkey_begin, pkey,
+                       pkey_payload, pkey_len)
 
 
 def check_txbodies_device(device: int, network_id, d_bodies: int, d_body_off: int, d_body_len: int, d_body_kind: int,
@@ -615,16 +642,20 @@ def check_txbodies_device(device: int, network_id, d_bodies: int, d_body_off: in
                           d_key: int, n_keys: int, d_check_begin: int, d_check_needed: int, n_checks: int,
                           d_signer_begin: int, d_signer_type: int, d_signer_weight: int, d_signer_key: int,
                           n_signers: int, d_check_ok: int, d_check_weight: int, d_check_used: int,
-                          d_sig_len: int = 0, protocol_version: int = 21, d_digests: int = 0, stream: int = 0) -> None:
+                          d_sig_len: int = 0, protocol_version: int = 21, d_digests: int = 0, stream: int = 0,
+                          d_pkey_begin: int = 0, d_pkey: int = 0, d_pkey_payload: int = 0, d_pkey_len: int = 0,
+                          n_pkeys=None) -> None:
     """Device-resident form (raw device pointers; network_id is 32 host bytes).
     Waits on `stream` once for the pair count, enqueues the verification and
-    the check kernel and returns; the decisions land in the d_check_* arrays."""
+    the check kernel and returns; the decisions land in the d_check_* arrays.
+    n_pkeys (not None) passes the payload tables d_pkey_*."""
     lib = load_library()
     nid = np.ascontiguousarray(np.frombuffer(bytes(network_id), np.uint8))
     if nid.size != 32:
         raise ValueError("network_id must be 32 bytes")
     ck = _checks_desc(protocol_version, d_sig_len, d_check_begin, d_check_needed, d_signer_begin, d_signer_type,
-                      d_signer_weight, d_signer_key, n_checks, n_signers)
+                      d_signer_weight, d_signer_key, n_checks, n_signers,
+                      None if n_pkeys is None else (d_pkey_begin, d_pkey, d_pkey_payload, d_pkey_len, n_pkeys))
     _check(lib.sv_ed25519_check_txbodies_device(
         device, _ptr(nid), d_bodies or None, d_body_off or None, d_body_len or None, d_body_kind or None, n_bodies,
         d_sig_begin or None, d_hint or None, d_sig or None, n_sigs, d_key_begin or None, d_key or None, n_keys,

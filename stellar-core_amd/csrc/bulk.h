@@ -653,6 +653,52 @@ inline int ensure_txpairs(Device& D, size_t np) {
   return SV_OK;
 }
 
+// The payload pairs of a check call (sv_txpair.hip sv_ppair_*) in D.txpp, np of them: verdicts (np) | pair_sig,
+// pair_key (4 np each) | message lengths (4 np) | message offsets (8 np) | keys (32 np) | signatures (64 np) |
+// payload rows (64 np), every section 16-byte aligned.  Shared by a call's chunks like the ed25519 pairs' gathered
+// arrays: everything that touches it runs on D.stream in order, and growing drains that stream first.
+struct PPairBufs {
+  size_t o_idx, o_len, o_off, o_key, o_sig, o_msg, bytes;
+};
+inline PPairBufs ppair_layout(size_t np) {
+  PPairBufs b;
+  b.o_idx = al16(np);
+  b.o_len = b.o_idx + al16(8 * np);
+  b.o_off = b.o_len + al16(4 * np);
+  b.o_key = b.o_off + al16(8 * np);
+  b.o_sig = b.o_key + 32 * np;
+  b.o_msg = b.o_sig + 64 * np;
+  b.bytes = b.o_msg + 64 * np + 16;
+  return b;
+}
+inline int ensure_txpp(Device& D, size_t bytes) {
+  if (bytes <= D.txpp.cap) return SV_OK;
+  SV_HIP(hipStreamSynchronize(D.stream));
+  return D.txpp.ensure(bytes);
+}
+
+// The payload tables of a check call on the device (all device pointers; nq == 0: none) and, after
+// ppair_run, its payload pairs for the check kernel.
+struct PayloadDev {
+  const uint64_t* qb = nullptr;  // n_bodies + 1
+  const uint8_t* key = nullptr;
+  const uint8_t* payload = nullptr;
+  const uint8_t* len = nullptr;
+  size_t nq = 0;
+};
+// Fill and verify the npp payload pairs counted by sv_launch_ppair_count (caller holds D.mu, device set, D.txpp
+// holds ppair_layout(npp)): the second, variable-length verify launch of a check call, on D.stream.
+inline int ppair_run(Device& D, const PayloadDev& pd, const uint64_t* d_sb, const void* d_hint, const void* d_sig,
+                     size_t m, size_t k, void* ws, void* pws, uint64_t* d_ppb, size_t npp, int path) {
+  const PPairBufs L = ppair_layout(npp);
+  uint8_t* b = (uint8_t*)D.txpp.p;
+  SV_HIP(sv_launch_ppair_fill(d_sb, d_hint, d_sig, m, pd.qb, pd.key, pd.payload, pd.len, pd.nq, k, ws, pws, d_ppb, npp,
+                              (uint32_t*)(b + L.o_idx), (uint32_t*)(b + L.o_idx) + npp, b + L.o_key, b + L.o_sig,
+                              b + L.o_msg, (uint64_t*)(b + L.o_off), (uint32_t*)(b + L.o_len), D.stream));
+  return launch_locked(D, 1, path, b + L.o_key, b + L.o_sig, b + L.o_msg, (const uint64_t*)(b + L.o_off),
+                       (const uint32_t*)(b + L.o_len), 0, npp, b, nullptr);
+}
+
 // Where a slice's pairs go: the caller's arrays (one slot), or vectors of the
 // slice's own that grow with the count (several slots: where a slot's pairs
 // start in the caller's arrays is only known once the slots before it are
@@ -849,15 +895,18 @@ inline int check_slice_locked(Device& D, const CheckIn& in, size_t B0, size_t B1
     Stage& s = D.st[ci & 1];
     if ((rc = check_drain(s, pend[ci & 1], out))) return rc;
     const size_t m = c.p.s1 - c.p.s0, q = c.p.k1 - c.p.k0, k = c.p.b1 - c.p.b0;
-    const size_t nc = c.c1 - c.c0, ng = c.g1 - c.g0;
-    const size_t wsb = al16(sv_pair_ws_bytes(k));
-    if ((rc = s.h_in.ensure(c.bytes)) || (rc = s.d_in.ensure(c.bytes)) || (rc = s.d_pair.ensure(wsb + 8 * (k + 1))) ||
+    const PayloadChunk pc = payload_chunk(in, c);
+    const size_t nc = c.c1 - c.c0, ng = c.g1 - c.g0, nq = pc.q1 - pc.q0;
+    const size_t wsb = al16(sv_pair_ws_bytes(k)), pbb = al16(8 * (k + 1)), pwsb = al16(sv_ppair_ws_bytes(k));
+    if ((rc = s.h_in.ensure(pc.bytes)) || (rc = s.d_in.ensure(pc.bytes)) ||
+        (rc = s.d_pair.ensure(wsb + pbb + (nq ? pwsb + pbb : 0))) ||
         (rc = s.d_keys.ensure(32 * k)) || (rc = s.h_cnt.ensure(64)))
       return rc;
     uint8_t* hp = (uint8_t*)s.h_in.p;
     uint8_t* d = (uint8_t*)s.d_in.p;
     check_pack(in, c, hp);
-    if ((rc = upload_image(D, d, hp, c.bytes, up_s))) return rc;
+    payload_pack(in, c, pc, hp);
+    if ((rc = upload_image(D, d, hp, pc.bytes, up_s))) return rc;
     const uint64_t* d_sb = (const uint64_t*)(d + c.p.o_sb);
     const uint64_t* d_kb = (const uint64_t*)(d + c.p.o_kb);
     uint64_t* d_pb = (uint64_t*)((uint8_t*)s.d_pair.p + wsb);
@@ -865,11 +914,26 @@ inline int check_slice_locked(Device& D, const CheckIn& in, size_t B0, size_t B1
                             (const uint32_t*)(d + c.p.o_len), d + c.p.o_kind, k, nullptr, 0, nullptr, s.d_keys.p,
                             up_s));
     SV_HIP(sv_launch_pair_count(d_sb, d + c.p.o_hint, d + c.p.o_sig, m, d_kb, d, q, k, s.d_pair.p, d_pb, up_s));
-    SV_HIP(hipMemcpyAsync(s.h_cnt.p, sv_pair_total(s.d_pair.p, k), 8, hipMemcpyDeviceToHost, up_s));
+    // the chunk's payload candidates: their pairing beside it, both counts in the one copy
+    PayloadDev pl;
+    void* d_pws = (uint8_t*)s.d_pair.p + wsb + pbb;
+    uint64_t* d_ppb = (uint64_t*)((uint8_t*)s.d_pair.p + wsb + pbb + pwsb);
+    if (nq) {
+      pl.qb = (const uint64_t*)(d + pc.o_qb);
+      pl.key = d + pc.o_qk;
+      pl.payload = d + pc.o_qp;
+      pl.len = d + pc.o_ql;
+      pl.nq = nq;
+      SV_HIP(sv_launch_ppair_count(d_sb, d + c.p.o_hint, m, pl.qb, pl.key, pl.payload, pl.len, nq, k, s.d_pair.p, d_pws,
+                                   d_ppb, up_s));
+    }
+    SV_HIP(hipMemcpyAsync(s.h_cnt.p, sv_pair_total(s.d_pair.p, k), nq ? 16 : 8, hipMemcpyDeviceToHost, up_s));
     SV_HIP(hipEventRecord(s.up, up_s));
     SV_HIP(hipEventSynchronize(s.up));
     const size_t np = (size_t)*(const uint64_t*)s.h_cnt.p;
+    const size_t npp = nq ? (size_t)((const uint64_t*)s.h_cnt.p)[1] : 0;
     if (!single) SV_HIP(hipStreamWaitEvent(D.stream, s.up, 0));
+    if (npp && (rc = ensure_txpp(D, ppair_layout(npp).bytes))) return rc;
     // verdicts (np, padded) | pair_sig, pair_key (4 np each, padded) | used | weight | ok
     const size_t o_idx = al16(np), o_res = o_idx + al16(8 * np), o_dig = al16(13 * nc);
     if ((rc = ensure_txpairs(D, np)) || (rc = s.d_verdict.ensure(o_res + 13 * nc + 16)) ||
@@ -883,12 +947,16 @@ inline int check_slice_locked(Device& D, const CheckIn& in, size_t B0, size_t B1
     if (np && (rc = launch_locked(D, 0, path, D.txpk.p, D.txsg.p, D.txmsg.p, nullptr, nullptr, 32, np, dv, nullptr,
                                   kt_mode() == 1)))
       return rc;
-    SV_HIP(sv_launch_txcheck(d_sb, d + c.p.o_hint, d + c.p.o_sig, in.sig_len ? d + c.o_sl : nullptr, m, d_kb, d, q, k,
-                             d_pb, d_ps, d_pk, dv, np, s.d_keys.p, (const uint64_t*)(d + c.o_cb),
-                             (const int32_t*)(d + c.o_need), nc, (const uint64_t*)(d + c.o_gb), d + c.o_gt,
-                             (const uint32_t*)(d + c.o_gw), (const uint32_t*)(d + c.o_gk), ng, clamp,
-                             dv + o_res + 12 * nc, (uint32_t*)(dv + o_res + 8 * nc), (uint64_t*)(dv + o_res),
-                             D.stream));
+    if (npp && (rc = ppair_run(D, pl, d_sb, d + c.p.o_hint, d + c.p.o_sig, m, k, s.d_pair.p, d_pws, d_ppb, npp, path)))
+      return rc;
+    const PPairBufs L = ppair_layout(npp);
+    const uint8_t* dpp = (const uint8_t*)D.txpp.p;
+    SV_HIP(sv_launch_txcheck_payload(
+        d_sb, d + c.p.o_hint, d + c.p.o_sig, in.sig_len ? d + c.o_sl : nullptr, m, d_kb, d, q, k, d_pb, d_ps, d_pk, dv,
+        np, s.d_keys.p, (const uint64_t*)(d + c.o_cb), (const int32_t*)(d + c.o_need), nc,
+        (const uint64_t*)(d + c.o_gb), d + c.o_gt, (const uint32_t*)(d + c.o_gw), (const uint32_t*)(d + c.o_gk), ng,
+        clamp, d_ppb, (const uint32_t*)(dpp + L.o_idx), (const uint32_t*)(dpp + L.o_idx) + npp, dpp, npp, pl.qb, nq,
+        dv + o_res + 12 * nc, (uint32_t*)(dv + o_res + 8 * nc), (uint64_t*)(dv + o_res), D.stream));
     if (!single) {
       SV_HIP(hipEventRecord(s.done, D.stream));
       SV_HIP(hipStreamWaitEvent(D.d2h, s.done, 0));

@@ -292,6 +292,7 @@ struct Device {
   DevBuf txpk, txsg, txpair;
   HostBuf h_txcnt;
   DevBuf txchk;  // device-resident check calls: the pairs' indices and verdicts, which stay inside the engine
+  DevBuf txpp;   // check calls with payload candidates: the payload pairs' verdicts, indices and gathered arrays
   KernelTimer timer;  // the bulk launches (launch_locked)
   LatLane lat;
   KeyTabs kt;  // (under mu)
@@ -408,7 +409,7 @@ inline void release_device(Device& D) {
   }
   D.msg.release(); D.off.release(); D.len.release(); D.keys.release(); D.h_sha.release();
   D.txmsg.release();
-  D.txpk.release(); D.txsg.release(); D.txpair.release(); D.h_txcnt.release(); D.txchk.release();
+  D.txpk.release(); D.txsg.release(); D.txpair.release(); D.h_txcnt.release(); D.txchk.release(); D.txpp.release();
   D.ws.release();
   D.kt.index.release(); D.kt.store.release(); D.kt.kslot.release(); D.kt.builders.release();
   D.kt.count.release(); D.kt.h_count.release();

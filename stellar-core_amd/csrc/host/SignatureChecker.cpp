@@ -426,13 +426,18 @@ void SignatureBatchPrefetch::runBodiesHinted(const uint8_t* networkID, const uin
 }
 
 bool SignatureBatchPrefetch::addDecided(TxBody const& body, std::vector<DecoratedSignature> const& signatures,
-                                        std::vector<SignatureCheck> const& checks) {
+                                        std::vector<SignatureCheck> const& checks, bool withPayload) {
   if (signatures.size() > 64) return false;
   for (auto const& sig : signatures)
     if (sig.signature.size() > 64) return false;
-  for (auto const& c : checks)
+  for (auto const& c : checks) {
     if (c.signers.size() > 64) return false;
+    if (withPayload)
+      for (auto const& s : c.signers)
+        if (s.key.type == SIGNER_KEY_TYPE_ED25519_SIGNED_PAYLOAD && s.key.payload.size() > 64) return false;
+  }
   Decided& d = dec_;
+  d.payload = withPayload;
   BodyEntry e;
   e.body = body;
   e.pair0 = e.pair1 = 0;
@@ -448,10 +453,29 @@ bool SignatureBatchPrefetch::addDecided(TxBody const& body, std::vector<Decorate
   }
   // the body's candidate rows: every distinct 32-byte key its checks name (the
   // source account's signers recur in every operation's check)
-  const size_t k0 = d.key.size() / 32;
+  const size_t k0 = d.key.size() / 32, q0 = d.pkeyLen.size();
   for (auto const& c : checks) {
     for (auto const& s : c.signers) {
-      if (s.key.type == SIGNER_KEY_TYPE_ED25519_SIGNED_PAYLOAD) continue;  // the caller's stage
+      if (s.key.type == SIGNER_KEY_TYPE_ED25519_SIGNED_PAYLOAD) {
+        if (!withPayload) continue;  // the caller's stage
+        // the body's payload candidates: every distinct (key, payload) its checks name
+        const size_t n = s.key.payload.size(), q1 = d.pkeyLen.size();
+        size_t q = q0;
+        while (q < q1 && !(d.pkeyLen[q] == n && std::memcmp(&d.pkey[32 * q], s.key.key.data(), 32) == 0 &&
+                           (n == 0 || std::memcmp(&d.pkeyPayload[64 * q], s.key.payload.data(), n) == 0)))
+          ++q;
+        if (q == q1) {
+          d.pkey.resize(32 * (q1 + 1));
+          d.pkeyPayload.resize(64 * (q1 + 1), 0);
+          std::memcpy(&d.pkey[32 * q1], s.key.key.data(), 32);
+          if (n) std::memcpy(&d.pkeyPayload[64 * q1], s.key.payload.data(), n);
+          d.pkeyLen.push_back((uint8_t)n);
+        }
+        d.type.push_back((uint8_t)s.key.type);
+        d.weight.push_back(s.weight);
+        d.keyIndex.push_back((uint32_t)q);
+        continue;
+      }
       size_t k = k0;
       const size_t k1 = d.key.size() / 32;
       while (k < k1 && std::memcmp(&d.key[32 * k], s.key.key.data(), 32) != 0) ++k;
@@ -469,6 +493,7 @@ bool SignatureBatchPrefetch::addDecided(TxBody const& body, std::vector<Decorate
   d.sigBegin.push_back(d.sigLen.size());
   d.keyBegin.push_back(d.key.size() / 32);
   d.checkBegin.push_back(d.needed.size());
+  d.pkeyBegin.push_back(d.pkeyLen.size());
   return true;
 }
 
@@ -487,8 +512,15 @@ void SignatureBatchPrefetch::runDecided(const uint8_t* networkID, const uint8_t*
     len[b] = bodies_[b].body.len;
     kind[b] = bodies_[b].body.kind;
   }
-  sv_txchecks ck;
-  ck.struct_size = sizeof ck;
+  // (the plain struct unless the payload candidates go along: the engine reads only what struct_size covers)
+  sv_txchecks_payload ckp;
+  sv_txchecks& ck = ckp.checks;
+  ck.struct_size = d.payload ? sizeof ckp : sizeof ck;
+  ckp.pkey_begin = d.pkeyBegin.data();
+  ckp.pkey = d.pkey.data();
+  ckp.pkey_payload = d.pkeyPayload.data();
+  ckp.pkey_len = d.pkeyLen.data();
+  ckp.n_pkeys = d.pkeyLen.size();
   ck.protocol_version = protocolVersion;
   ck.sig_len = d.sigLen.data();
   ck.check_begin = d.checkBegin.data();

@@ -155,7 +155,12 @@ class SignatureBatchPrefetch {
   // and the signatures they marked used.  Signed-payload signers stay with the
   // caller (they are not sent).  addDecided returns false, adding nothing, for
   // what the engine does not take: more than 64 signatures, a signature longer
-  // than 64 bytes, a check with more than 64 signers.  A prefetch takes one
+  // than 64 bytes, a check with more than 64 signers.  With withPayload (every
+  // addDecided call of a prefetch, or none) the signed-payload signers go to
+  // the engine too, as the body's payload candidates (sv_txchecks_payload:
+  // distinct (key, payload) rows; a payload longer than 64 bytes is not
+  // taken): the decisions are then those of all four stages and final
+  // (decidedFinal()), with nothing left to the caller.  A prefetch takes one
   // form only.
   struct Decision {
     bool ok;
@@ -163,7 +168,8 @@ class SignatureBatchPrefetch {
     uint64_t used;
   };
   bool addDecided(TxBody const& body, std::vector<DecoratedSignature> const& signatures,
-                  std::vector<SignatureCheck> const& checks);
+                  std::vector<SignatureCheck> const& checks, bool withPayload = false);
+  bool decidedFinal() const { return dec_.payload; }
   void runDecided(const uint8_t* networkID, const uint8_t* blob, uint32_t protocolVersion);
   Decision decision(size_t body, size_t check) const;
   size_t decidedChecks() const { return dec_.needed.size(); }
@@ -229,6 +235,10 @@ class SignatureBatchPrefetch {
     std::vector<uint64_t> sigBegin{0}, keyBegin{0}, checkBegin{0}, signerBegin{0}, used;
     std::vector<int32_t> needed;
     std::vector<uint32_t> weight, keyIndex, outWeight;
+    // withPayload: the payload candidates (sv_txchecks_payload)
+    bool payload = false;
+    std::vector<uint64_t> pkeyBegin{0};
+    std::vector<uint8_t> pkey, pkeyPayload, pkeyLen;
   } dec_;
   std::vector<uint64_t> hSigBegin_{0}, hKeyBegin_{0};  // hinted body form: CSR by body, in addHinted order
   static std::vector<Storage>& spares();

@@ -145,6 +145,7 @@ class DecidedChecker {
     const SignatureBatchPrefetch::Decision d = mPre.decision(mBody, mNext++);
     mUsed |= d.used;
     if (d.ok) return true;
+    if (mPre.decidedFinal()) return false;  // (the engine ran the signed-payload stage too)
     // the reference's last stage, from the state the engine's three left
     std::vector<Signer const*> rest;
     for (auto const& s : signers)

@@ -130,7 +130,9 @@ std::vector<SignatureCheck> listFeeBumpOuterChecks(FeeBumpSigInfo const& tx, Acc
 // marks are ORed over the transaction's checks and consulted only when every
 // check passed (exactly when the reference had run them all); a check that
 // came back false and has signed-payload signers continues on the host from
-// its weight and marks (SignatureUtils::verifyEd25519SignedPayload).
+// its weight and marks (SignatureUtils::verifyEd25519SignedPayload) -- unless
+// the bodies were added with addDecided's withPayload, where the engine ran
+// that stage too and every decision is final (pre.decidedFinal()).
 TxSigResult checkTransactionSignaturesDecided(TransactionSigInfo const& tx, AccountSnapshot const& accounts,
                                               uint32_t protocol, SignatureBatchPrefetch const& pre, size_t body,
                                               bool forApply = false);

@@ -478,9 +478,9 @@ int checkEnvelopes(const svh_envelope* env, size_t n, const svh_decorated_sig* s
                    const EnvelopeBodies* eb) {
   try {
     if (eb) {
-      if (prefetch != 0 && prefetch != 1 && prefetch != 3 && prefetch != 5)
+      if (prefetch != 0 && prefetch != 1 && prefetch != 3 && prefetch != 5 && prefetch != 6)
         throw std::invalid_argument(
-            "svh_check_envelopes_bodies: prefetch must be 0, 1, 3 or 5 (no keyed, cache-seeding form)");
+            "svh_check_envelopes_bodies: prefetch must be 0, 1, 3, 5 or 6 (no keyed, cache-seeding form)");
       if (!eb->networkID || !eb->contentsHashOut || !eb->feeBumpHashOut || (n && !eb->body))
         throw std::invalid_argument("svh_check_envelopes_bodies: null argument");
       for (size_t t = 0; t < n; ++t) {
@@ -533,10 +533,13 @@ int checkEnvelopes(const svh_envelope* env, size_t n, const svh_decorated_sig* s
     // more than 64 signatures or 64 signers in a check) is checked by a plain
     // SignatureChecker over host-computed hashes, it alone; protocol 7 (every
     // check is true without looking) takes that path for the whole call.
+    // prefetch 6: the same with the signed-payload signers sent along as payload
+    // candidates, so the decisions are final and no check continues on the host.
+    const bool withPayload = prefetch == 6;
     constexpr size_t kPlain = ~size_t(0);
     std::vector<size_t> innerBody, outerBody;
     bool decidedRun = false;
-    if (prefetch == 5 && eb) {
+    if ((prefetch == 5 || prefetch == 6) && eb) {
       auto at = [&](uint64_t off) { return eb->blob ? eb->blob + off : nullptr; };
       innerBody.assign(n, kPlain);
       outerBody.assign(n, kPlain);
@@ -549,7 +552,8 @@ int checkEnvelopes(const svh_envelope* env, size_t n, const svh_decorated_sig* s
         if (taken && bump) {
           const SignatureBatchPrefetch::TxBody outer{b.outer_off, b.outer_len, 2, &txs[t].contentsHash};
           taken = pre.addDecided(outer, txs[t].signatures,
-                                 protocol >= 13 ? listFeeBumpOuterChecks(txs[t], snap) : std::vector<SignatureCheck>());
+                                 protocol >= 13 ? listFeeBumpOuterChecks(txs[t], snap) : std::vector<SignatureCheck>(),
+                                 withPayload);
           if (taken) outerBody[t] = nbodies++;
         }
         if (taken) {
@@ -557,7 +561,8 @@ int checkEnvelopes(const svh_envelope* env, size_t n, const svh_decorated_sig* s
           taken = pre.addDecided(inner, txs[t].inner.signatures,
                                  !bump || protocol >= 13
                                      ? listTransactionChecks(txs[t].inner, snap, protocol, for_apply != 0)
-                                     : std::vector<SignatureCheck>());
+                                     : std::vector<SignatureCheck>(),
+                                 withPayload);
           if (taken) innerBody[t] = nbodies++;
         }
         if (!taken) {

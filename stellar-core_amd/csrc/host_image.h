@@ -474,7 +474,12 @@ struct CheckIn {
   const uint64_t* gb;       // signers of check c: [gb[c], gb[c + 1])
   const uint8_t* gtype;     // per signer
   const uint32_t* gweight;
-  const uint32_t* gkey;     // global index into h.key
+  const uint32_t* gkey;     // global index into h.key (a type-3 signer with payload tables: into qkey)
+  // the payload tables (sv_txchecks::pkey_begin ...), or qb == nullptr: none, or no candidate in the call
+  const uint64_t* qb = nullptr;   // payload candidates of body t: [qb[t], qb[t + 1])
+  const uint8_t* qkey = nullptr;  // 32 B rows
+  const uint8_t* qpay = nullptr;  // 64 B rows
+  const uint8_t* qlen = nullptr;  // per candidate
 };
 
 // One staging chunk of it: the hinted image of bodies [b0, b1) (PairChunk p,
@@ -483,11 +488,48 @@ struct CheckIn {
 //   check_begin (8 (k + 1)) | signer_begin (8 (nc + 1)) | needed (4 nc) | signer_weight (4 ng) |
 //   signer_key (4 ng) | signer_type (ng) | sig_len (m, only with CheckIn::sig_len)
 // check_begin, signer_begin and signer_key are relative to c0 / g0 / p.k0.
+// With payload tables the type-3 signers' signer_key is relative to the chunk's
+// first payload candidate instead.
 struct CheckChunk {
   PairChunk p;
   size_t c0, c1, g0, g1;
   size_t o_cb, o_gb, o_need, o_gw, o_gk, o_gt, o_sl, bytes;
 };
+
+// A chunk whose bodies have payload candidates [q0, q1) (nq of them) carries
+// them behind the CheckChunk image, at its `bytes`:
+//   pkey (32 nq) | payload (64 nq) | pkey_begin (8 (k + 1)) | pkey_len (nq)
+// with pkey_begin relative to q0; `bytes` is then the whole image.  A chunk
+// without candidates has no such section: bytes == the CheckChunk's.
+struct PayloadChunk {
+  size_t q0, q1, o_qk, o_qp, o_qb, o_ql, bytes;
+};
+inline PayloadChunk payload_chunk(const CheckIn& in, const CheckChunk& c) {
+  PayloadChunk pc{};
+  pc.bytes = c.bytes;
+  if (!in.qb) return pc;
+  pc.q0 = (size_t)in.qb[c.p.b0];
+  pc.q1 = (size_t)in.qb[c.p.b1];
+  if (const size_t nq = pc.q1 - pc.q0) {
+    pc.o_qk = c.bytes;
+    pc.o_qp = pc.o_qk + 32 * nq;
+    pc.o_qb = pc.o_qp + 64 * nq;
+    pc.o_ql = pc.o_qb + 8 * (c.p.b1 - c.p.b0 + 1);
+    pc.bytes = al16(pc.o_ql + nq);
+  }
+  return pc;
+}
+// (a few rows at most: copied by the caller's thread)
+inline void payload_pack(const CheckIn& in, const CheckChunk& c, const PayloadChunk& pc, uint8_t* h) {
+  const size_t nq = pc.q1 - pc.q0, k = c.p.b1 - c.p.b0;
+  if (!nq) return;
+  std::memcpy(h + pc.o_qk, in.qkey + 32 * pc.q0, 32 * nq);
+  std::memcpy(h + pc.o_qp, in.qpay + 64 * pc.q0, 64 * nq);
+  std::memcpy(h + pc.o_ql, in.qlen + pc.q0, nq);
+  uint64_t* qb = (uint64_t*)(h + pc.o_qb);
+  for (size_t i = 0; i <= k; ++i) qb[i] = in.qb[c.p.b0 + i] - pc.q0;
+  std::memset(h + pc.o_ql + nq, 0, pc.bytes - (pc.o_ql + nq));
+}
 
 // The hinted image of exactly bodies [b0, b1): pair_plan's layout for a given run.
 inline PairChunk pair_chunk(const HintIn& in, size_t b0, size_t b1, size_t body_bytes) {
@@ -514,7 +556,7 @@ inline PairChunk pair_chunk(const HintIn& in, size_t b0, size_t b1, size_t body_
 
 // The chunks of bodies [B0, B1): pair_plan's runs of whole bodies, additionally
 // bounded by max_c checks and max_g signers (a body over a bound is a chunk
-// alone).
+// alone).  Payload candidates count towards max_k like keys.
 inline std::vector<CheckChunk> check_plan(const CheckIn& in, size_t B0, size_t B1, size_t max_s, size_t max_k,
                                           size_t max_b, size_t max_c, size_t max_g) {
   std::vector<CheckChunk> out;
@@ -522,11 +564,13 @@ inline std::vector<CheckChunk> check_plan(const CheckIn& in, size_t B0, size_t B
   size_t t = B0;
   while (t < B1) {
     const size_t b0 = t, s0 = (size_t)hi.sb[t], k0 = (size_t)hi.kb[t], c0 = (size_t)in.cb[t], g0 = (size_t)in.gb[c0];
+    const size_t q0 = in.qb ? (size_t)in.qb[t] : 0;
     size_t bytes = 0;
     do {
       bytes += al16(hi.len[t]);
       ++t;
-    } while (t < B1 && hi.sb[t + 1] - s0 <= max_s && hi.kb[t + 1] - k0 <= max_k && in.cb[t + 1] - c0 <= max_c &&
+    } while (t < B1 && hi.sb[t + 1] - s0 <= max_s &&
+             hi.kb[t + 1] - k0 + (in.qb ? in.qb[t + 1] - q0 : 0) <= max_k && in.cb[t + 1] - c0 <= max_c &&
              in.gb[in.cb[t + 1]] - g0 <= max_g && bytes + al16(hi.len[t]) <= max_b);
     CheckChunk c{};
     c.p = pair_chunk(hi, b0, t, bytes);
@@ -556,6 +600,7 @@ inline void check_pack(const CheckIn& in, const CheckChunk& c, uint8_t* h) {
   uint32_t* gk = (uint32_t*)(h + c.o_gk);
   cb[k] = in.cb[c.p.b1] - c.c0;
   gb[nc] = in.gb[c.c1] - c.g0;
+  const size_t q0 = in.qb ? (size_t)in.qb[c.p.b0] : 0;
   // the tables in parts of the pack pool: rebased CSR words and key indices, plain copies of the rest
   Pool& pp = pack_pool();
   const size_t parts = pack_parts(pp.size(), t_pack_parts, 8 * k + 12 * nc + 9 * ng + m, pack_part());
@@ -567,7 +612,9 @@ inline void check_pack(const CheckIn& in, const CheckChunk& c, uint8_t* h) {
     a = ng * p / parts, b = ng * (p + 1) / parts;
     if (b > a) {
       std::memcpy(h + c.o_gw + 4 * a, in.gweight + c.g0 + a, 4 * (b - a));
-      for (size_t i = a; i < b; ++i) gk[i] = in.gkey[c.g0 + i] - (uint32_t)c.p.k0;
+      for (size_t i = a; i < b; ++i)
+        gk[i] = in.gkey[c.g0 + i] -
+                (uint32_t)(in.qb && in.gtype[c.g0 + i] == 3 /* ED25519_SIGNED_PAYLOAD */ ? q0 : c.p.k0);
       std::memcpy(h + c.o_gt + a, in.gtype + c.g0 + a, b - a);
     }
     a = m * p / parts, b = m * (p + 1) / parts;

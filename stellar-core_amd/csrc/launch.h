@@ -35,6 +35,11 @@ int sv_txchecks_check(const uint8_t* network_id, const uint8_t* bodies, const ui
                       const uint8_t* key, size_t n_keys, const struct sv_txchecks* checks, const uint8_t* check_ok,
                       const uint32_t* check_weight, const uint64_t* check_used);
 
+// The payload tables of a check call (sv_cpu.cpp): `checks` as an sv_txchecks_payload when its struct_size covers
+// one and pkey_begin is set, else nullptr -- whatever lies behind a plain sv_txchecks is not read.
+struct sv_txchecks_payload;
+const struct sv_txchecks_payload* sv_txchecks_tables(const struct sv_txchecks* checks);
+
 }  // extern "C"
 
 // The launchers take HIP types: compiled only where the HIP runtime headers
@@ -80,6 +85,19 @@ hipError_t sv_launch_pair_fill(const uint64_t* sig_begin, const void* hint, cons
                                void* ws, uint64_t* pair_begin, uint64_t n_pairs, uint32_t* pair_sig,
                                uint32_t* pair_key, void* gkey, void* gsig, void* gmsg, const void* digests,
                                hipStream_t s);
+// payload pairing (sv_txpair.hip): a body's signed-payload candidates against its signatures, after
+// sv_launch_pair_count on the same `ws`; `pws` holds sv_ppair_ws_bytes(n_bodies), the count is
+// sv_pair_total(ws, n_bodies)[1]; the fill gathers the arrays of a variable-length verify launch
+size_t sv_ppair_ws_bytes(uint64_t n_bodies);
+hipError_t sv_launch_ppair_count(const uint64_t* sig_begin, const void* hint, uint64_t n_sigs,
+                                 const uint64_t* pkey_begin, const void* pkey, const void* payload,
+                                 const uint8_t* plen, uint64_t n_pkeys, uint64_t n_bodies, void* ws, void* pws,
+                                 uint64_t* ppair_begin, hipStream_t s);
+hipError_t sv_launch_ppair_fill(const uint64_t* sig_begin, const void* hint, const void* sig, uint64_t n_sigs,
+                                const uint64_t* pkey_begin, const void* pkey, const void* payload,
+                                const uint8_t* plen, uint64_t n_pkeys, uint64_t n_bodies, void* ws, void* pws,
+                                uint64_t* ppair_begin, uint64_t n_pairs, uint32_t* pair_sig, uint32_t* pair_key,
+                                void* gkey, void* gsig, void* gmsg, uint64_t* goff, uint32_t* glen, hipStream_t s);
 // one checkSignature decision per check (sv_txcheck.hip), after the pairing and the verify launch on the same
 // stream; sig_len may be nullptr (all 64)
 int sv_check_block(void);
@@ -92,6 +110,20 @@ hipError_t sv_launch_txcheck(const uint64_t* sig_begin, const void* hint, const 
                              const uint32_t* signer_weight, const uint32_t* signer_key, uint64_t n_signers,
                              int clamp, uint8_t* check_ok, uint32_t* check_weight, uint64_t* check_used,
                              hipStream_t s);
+// ... with the payload pairing's output (sv_launch_ppair_fill) and the candidates' CSR array for the
+// signed-payload pass; n_ppairs == 0: no payload pairs, the payload arguments are not read
+hipError_t sv_launch_txcheck_payload(const uint64_t* sig_begin, const void* hint, const void* sig,
+                                     const uint8_t* sig_len, uint64_t n_sigs, const uint64_t* key_begin,
+                                     const void* key, uint64_t n_keys, uint64_t n_bodies, const uint64_t* pair_begin,
+                                     const uint32_t* pair_sig, const uint32_t* pair_key, const void* pair_verdict,
+                                     uint64_t n_pairs, const void* digests, const uint64_t* check_begin,
+                                     const int32_t* check_needed, uint64_t n_checks, const uint64_t* signer_begin,
+                                     const uint8_t* signer_type, const uint32_t* signer_weight,
+                                     const uint32_t* signer_key, uint64_t n_signers, int clamp,
+                                     const uint64_t* ppair_begin, const uint32_t* ppair_sig,
+                                     const uint32_t* ppair_key, const void* ppair_verdict, uint64_t n_ppairs,
+                                     const uint64_t* pkey_begin, uint64_t n_pkeys, uint8_t* check_ok,
+                                     uint32_t* check_weight, uint64_t* check_used, hipStream_t s);
 // warm-key latency path (sv_comb.hip)
 size_t sv_comb_btab_bytes(void);
 size_t sv_key_slot_bytes(void);

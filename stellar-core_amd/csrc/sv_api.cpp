@@ -846,16 +846,25 @@ int sv_ed25519_check_txbodies(const uint8_t* network_id, const uint8_t* bodies, 
                         key_begin, key, n_keys, checks, check_ok, check_weight, check_used))
     return fail(SV_ERR_INVALID_ARG,
                 "tx checks: null pointer, body kind > 2, malformed CSR array, signer type > 3, key index outside its "
-                "body, sig_len > 64, more than 64 signatures or signers in a check, or protocol 7");
+                "body, sig_len > 64, more than 64 signatures or signers in a check, protocol 7, or a malformed payload "
+                "table (pkey_begin, pkey_len > 64, null table, 2^32 or more candidates)");
   if (n_bodies == 0) return SV_OK;
   if ((rc = debug_fail())) return rc;
   if ((rc = ensure_init())) return rc;
   std::vector<Device*> devs;
   if ((rc = select_devices(opts, n_sigs, devs))) return rc;
   const int path = path_from_flags(opts ? opts->flags : 0u);
-  const CheckIn in{{network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, key_begin, key},
-                   checks->sig_len,      checks->check_begin,   checks->check_needed, checks->signer_begin,
-                   checks->signer_type, checks->signer_weight, checks->signer_key};
+  CheckIn in{{network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, key_begin, key},
+             checks->sig_len,      checks->check_begin,   checks->check_needed, checks->signer_begin,
+             checks->signer_type, checks->signer_weight, checks->signer_key};
+  // (payload tables without a candidate: the call without them)
+  const sv_txchecks_payload* pt = sv_txchecks_tables(checks);
+  if (pt && pt->n_pkeys) {
+    in.qb = pt->pkey_begin;
+    in.qkey = pt->pkey;
+    in.qpay = pt->pkey_payload;
+    in.qlen = pt->pkey_len;
+  }
   const int clamp = checks->protocol_version >= 10;
   const CheckOut out{check_ok, check_weight, check_used, digests};
   const size_t G = devs.size();
@@ -888,6 +897,20 @@ int sv_ed25519_check_txbodies_device(int device, const uint8_t* network_id, cons
   if (ck->protocol_version == 7) return fail(SV_ERR_INVALID_ARG, "tx checks: protocol 7 needs no engine");
   if ((uint64_t)n_sigs >> 32 || (uint64_t)n_keys >> 32)
     return fail(SV_ERR_INVALID_ARG, "tx checks: 2^32 or more signatures or keys");
+  // the payload tables: with no candidate the call is the one without them
+  PayloadDev pl;
+  const sv_txchecks_payload* pt = sv_txchecks_tables(ck);
+  if (pt && pt->n_pkeys) {
+    pl.qb = pt->pkey_begin;
+    if ((uint64_t)pt->n_pkeys >> 32 || !pt->pkey || !pt->pkey_payload || !pt->pkey_len)
+      return fail(SV_ERR_INVALID_ARG, "tx checks: null payload table, or 2^32 or more payload candidates");
+    if (!aligned16(pt->pkey) || !aligned16(pt->pkey_payload) || ((uintptr_t)pl.qb & 7u))
+      return fail(SV_ERR_ALIGN, "pkey/pkey_payload must be 16-byte aligned, pkey_begin naturally aligned");
+    pl.key = pt->pkey;
+    pl.payload = pt->pkey_payload;
+    pl.len = pt->pkey_len;
+    pl.nq = pt->n_pkeys;
+  }
   if (!aligned16(d_sig) || !aligned16(d_key) || !aligned16(d_digests) || ((uintptr_t)d_hint & 3u) ||
       ((uintptr_t)ck->check_begin & 7u) || ((uintptr_t)ck->signer_begin & 7u) || ((uintptr_t)ck->check_needed & 3u) ||
       ((uintptr_t)ck->signer_weight & 3u) || ((uintptr_t)ck->signer_key & 3u) || ((uintptr_t)d_check_weight & 3u) ||
@@ -907,7 +930,8 @@ int sv_ed25519_check_txbodies_device(int device, const uint8_t* network_id, cons
   // none, and the pinned word the count comes back in (growing drains the
   // kernel stream)
   const size_t wsb = al16(sv_pair_ws_bytes(n_bodies)), pbb = al16(8 * (n_bodies + 1));
-  const size_t need = wsb + pbb + (d_digests ? 0 : 32 * n_bodies);
+  const size_t o_pws = wsb + pbb + (d_digests ? 0 : 32 * n_bodies), pwsb = al16(sv_ppair_ws_bytes(n_bodies));
+  const size_t need = o_pws + (pl.nq ? pwsb + pbb : 0);
   if (need > D.txpair.cap) {
     SV_HIP(hipStreamSynchronize(D.stream));
     if ((rc = D.txpair.ensure(need))) return rc;
@@ -921,13 +945,23 @@ int sv_ed25519_check_txbodies_device(int device, const uint8_t* network_id, cons
                           nullptr, dig, D.stream));
   SV_HIP(sv_launch_pair_count(d_sig_begin, d_hint, d_sig, n_sigs, d_key_begin, d_key, n_keys, n_bodies, D.txpair.p,
                               d_pb, D.stream));
-  SV_HIP(hipMemcpyAsync(D.h_txcnt.p, sv_pair_total(D.txpair.p, n_bodies), 8, hipMemcpyDeviceToHost, D.stream));
+  void* d_pws = (uint8_t*)D.txpair.p + o_pws;
+  uint64_t* d_ppb = (uint64_t*)((uint8_t*)D.txpair.p + o_pws + pwsb);
+  if (pl.nq)
+    SV_HIP(sv_launch_ppair_count(d_sig_begin, d_hint, n_sigs, pl.qb, pl.key, pl.payload, pl.len, pl.nq, n_bodies,
+                                 D.txpair.p, d_pws, d_ppb, D.stream));
+  // (both counts in the one copy: the payload pairing's total is the word behind the ed25519 pairing's)
+  SV_HIP(hipMemcpyAsync(D.h_txcnt.p, sv_pair_total(D.txpair.p, n_bodies), pl.nq ? 16 : 8, hipMemcpyDeviceToHost,
+                        D.stream));
   // the one wait: the number of pairs is only known on the device (the stream
   // is idle afterwards, so the pair arrays may grow here)
   SV_HIP(hipStreamSynchronize(D.stream));
   const size_t np = (size_t)*(const uint64_t*)D.h_txcnt.p;
+  const size_t npp = pl.nq ? (size_t)((const uint64_t*)D.h_txcnt.p)[1] : 0;
   const size_t o_idx = al16(np);
   if ((rc = ensure_txpairs(D, np)) || (rc = D.txchk.ensure(o_idx + 8 * np + 16))) return rc;
+  // (the workspace of both verify launches now, so the second never grows it under the first)
+  if (npp && ((rc = ensure_txpp(D, ppair_layout(npp).bytes)) || (rc = presize_ws(D, SV_PATH_AUTO, npp)))) return rc;
   uint8_t* dv = (uint8_t*)D.txchk.p;
   uint32_t* d_ps = (uint32_t*)(dv + o_idx);
   uint32_t* d_pk = d_ps + np;
@@ -936,10 +970,17 @@ int sv_ed25519_check_txbodies_device(int device, const uint8_t* network_id, cons
   if (np && (rc = launch_locked(D, 0, SV_PATH_AUTO, D.txpk.p, D.txsg.p, D.txmsg.p, nullptr, nullptr, 32, np, dv,
                                 nullptr, kt_mode() == 1)))
     return rc;
-  SV_HIP(sv_launch_txcheck(d_sig_begin, d_hint, d_sig, ck->sig_len, n_sigs, d_key_begin, d_key, n_keys, n_bodies, d_pb,
+  if (npp && (rc = ppair_run(D, pl, d_sig_begin, d_hint, d_sig, n_sigs, n_bodies, D.txpair.p, d_pws, d_ppb, npp,
+                             SV_PATH_AUTO)))
+    return rc;
+  const PPairBufs L = ppair_layout(npp);
+  const uint8_t* dpp = (const uint8_t*)D.txpp.p;
+  SV_HIP(sv_launch_txcheck_payload(d_sig_begin, d_hint, d_sig, ck->sig_len, n_sigs, d_key_begin, d_key, n_keys, n_bodies, d_pb,
                            d_ps, d_pk, dv, np, dig, ck->check_begin, ck->check_needed, ck->n_checks, ck->signer_begin,
                            ck->signer_type, ck->signer_weight, ck->signer_key, ck->n_signers,
-                           ck->protocol_version >= 10, (uint8_t*)d_check_ok, d_check_weight, d_check_used, D.stream));
+                           ck->protocol_version >= 10, d_ppb, (const uint32_t*)(dpp + L.o_idx),
+                           (const uint32_t*)(dpp + L.o_idx) + npp, dpp, npp, pl.qb, pl.nq, (uint8_t*)d_check_ok,
+                           d_check_weight, d_check_used, D.stream));
   SV_HIP(hipEventRecord(D.dep_out, D.stream));
   SV_HIP(hipStreamWaitEvent(user, D.dep_out, 0));
   return SV_OK;
@@ -1188,7 +1229,7 @@ int sv_workspace_bytes(int device, size_t* bytes) {
   // (lock order: the lane's mutex before the slot's)
   std::lock_guard<std::mutex> gl(Dp->lat.mu);
   std::lock_guard<std::mutex> g(Dp->mu);
-  size_t b = Dp->ws.cap + Dp->txmsg.cap + Dp->txpk.cap + Dp->txsg.cap + Dp->txpair.cap + Dp->txchk.cap;
+  size_t b = Dp->ws.cap + Dp->txmsg.cap + Dp->txpk.cap + Dp->txsg.cap + Dp->txpair.cap + Dp->txchk.cap + Dp->txpp.cap;
   for (const LatCtx& c : Dp->lat.ctx) b += c.ws.cap + c.d_in.cap + c.d_out.cap + c.d_keys.cap;
   *bytes = b;
   return SV_OK;

@@ -271,6 +271,12 @@ int sv_ed25519_verify_txbodies_hinted_cpu(const uint8_t* network_id, const uint8
                                      threads);
 }
 
+const sv_txchecks_payload* sv_txchecks_tables(const sv_txchecks* ck) {
+  if (ck->struct_size < sizeof(sv_txchecks_payload)) return nullptr;
+  const sv_txchecks_payload* pt = (const sv_txchecks_payload*)ck;
+  return pt->pkey_begin ? pt : nullptr;
+}
+
 // Argument check shared by the sv_ed25519_check_txbodies host-array entry
 // points (declared in launch.h): SV_OK or SV_ERR_INVALID_ARG.
 int sv_txchecks_check(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
@@ -292,6 +298,14 @@ int sv_txchecks_check(const uint8_t* network_id, const uint8_t* bodies, const ui
   if (ng && (!ck->signer_type || !ck->signer_weight || !ck->signer_key)) return SV_ERR_INVALID_ARG;
   if (ck->check_begin[0] != 0 || ck->check_begin[n_bodies] != nc) return SV_ERR_INVALID_ARG;
   if (ck->signer_begin[0] != 0 || ck->signer_begin[nc] != ng) return SV_ERR_INVALID_ARG;
+  // the payload tables, when the struct has them: type-3 signers then index the payload candidates
+  const sv_txchecks_payload* pt = sv_txchecks_tables(ck);
+  const uint64_t* qb = pt ? pt->pkey_begin : nullptr;
+  const size_t nq = pt ? pt->n_pkeys : 0;
+  if (qb) {
+    if ((uint64_t)nq >> 32 || (nq && (!pt->pkey || !pt->pkey_payload || !pt->pkey_len))) return SV_ERR_INVALID_ARG;
+    if (qb[0] != 0 || qb[n_bodies] != nq) return SV_ERR_INVALID_ARG;
+  }
   // per body: its CSR entries, signature lengths, limits, and per check of it
   // the signer range, signer types and key indices (every pass here is linear
   // in the batch, so large batches are threaded over bodies)
@@ -300,6 +314,11 @@ int sv_txchecks_check(const uint8_t* network_id, const uint8_t* bodies, const ui
       if (sig_begin[t + 1] < sig_begin[t] || key_begin[t + 1] < key_begin[t] || body_kind[t] > 2) return false;
       if (sig_begin[t + 1] > n_sigs || key_begin[t + 1] > n_keys) return false;
       if (body_len[t] && !bodies) return false;
+      if (qb) {
+        if (qb[t + 1] < qb[t] || qb[t + 1] > nq) return false;
+        for (uint64_t i = qb[t]; i < qb[t + 1]; ++i)
+          if (pt->pkey_len[i] > 64) return false;
+      }
       if (ck->sig_len)
         for (uint64_t i = sig_begin[t]; i < sig_begin[t + 1]; ++i)
           if (ck->sig_len[i] > 64) return false;
@@ -309,9 +328,12 @@ int sv_txchecks_check(const uint8_t* network_id, const uint8_t* bodies, const ui
       for (uint64_t c = c0; c < c1; ++c) {
         const uint64_t g0 = ck->signer_begin[c], g1 = ck->signer_begin[c + 1];
         if (g1 < g0 || g1 > ng || g1 - g0 > SV_TXCHECK_MAX) return false;
-        for (uint64_t g = g0; g < g1; ++g)
-          if (ck->signer_type[g] > 3 || ck->signer_key[g] < key_begin[t] || ck->signer_key[g] >= key_begin[t + 1])
-            return false;
+        for (uint64_t g = g0; g < g1; ++g) {
+          if (ck->signer_type[g] > 3) return false;
+          const bool pl = qb && ck->signer_type[g] == SV_SIGNER_SIGNED_PAYLOAD;
+          const uint64_t lo = pl ? qb[t] : key_begin[t], hi = pl ? qb[t + 1] : key_begin[t + 1];
+          if (ck->signer_key[g] < lo || ck->signer_key[g] >= hi) return false;
+        }
       }
     }
     return true;
@@ -354,6 +376,38 @@ int sv_ed25519_check_txbodies_cpu(const uint8_t* network_id, const uint8_t* bodi
                                              hint, sig, n_sigs, key_begin, key, n_keys, cap, pb.data(), ps.data(),
                                              pk.data(), pv.data(), &np, digests, threads);
   if (rc) return rc;
+  // the payload pairs: (body, signature, candidate) order, verified over the candidates' payloads
+  const sv_txchecks_payload* pt = sv_txchecks_tables(ck);
+  const uint64_t* qb = pt ? pt->pkey_begin : nullptr;
+  std::vector<uint64_t> ppb(n_bodies + 1, 0);
+  std::vector<uint32_t> pps, ppk;
+  std::vector<uint8_t> ppv;
+  if (qb && pt->n_pkeys) {
+    std::vector<uint8_t> gpk, gsig, gmsg;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> len;
+    for (size_t t = 0; t < n_bodies; ++t) {
+      ppb[t] = pps.size();
+      if (qb[t + 1] == qb[t]) continue;
+      for (uint64_t s = sig_begin[t]; s < sig_begin[t + 1]; ++s)
+        for (uint64_t c = qb[t]; c < qb[t + 1]; ++c) {
+          const uint32_t l = pt->pkey_len[c];
+          if (sv_payload_hint(pt->pkey + 32 * c, pt->pkey_payload + 64 * c, l) != sv_txc_ld32(hint + 4 * s)) continue;
+          pps.push_back((uint32_t)s);
+          ppk.push_back((uint32_t)c);
+          off.push_back(gmsg.size());
+          len.push_back(l);
+          gpk.insert(gpk.end(), pt->pkey + 32 * c, pt->pkey + 32 * c + 32);
+          gsig.insert(gsig.end(), sig + 64 * s, sig + 64 * s + 64);
+          gmsg.insert(gmsg.end(), pt->pkey_payload + 64 * c, pt->pkey_payload + 64 * c + 64);
+        }
+    }
+    ppb[n_bodies] = pps.size();
+    ppv.resize(pps.size() + 1);
+    if (!pps.empty() && (rc = sv_ed25519_verify_batch_cpu(gpk.data(), gsig.data(), gmsg.data(), off.data(), len.data(),
+                                                          pps.size(), ppv.data(), threads)))
+      return rc;
+  }
   const bool clamp = ck->protocol_version >= 10;
   for (size_t t = 0; t < n_bodies; ++t) {
     sv_txcheck_body b;
@@ -371,6 +425,13 @@ int sv_ed25519_check_txbodies_cpu(const uint8_t* network_id, const uint8_t* bodi
     b.k1 = key_begin[t + 1];
     b.p0 = pb[t];
     b.p1 = pb[t + 1];
+    b.ppair_sig = pps.data();
+    b.ppair_key = ppk.data();
+    b.ppair_verdict = ppv.data();
+    b.q0 = qb ? qb[t] : 0;
+    b.q1 = qb ? qb[t + 1] : 0;
+    b.pp0 = ppb[t];
+    b.pp1 = ppb[t + 1];
     for (uint64_t c = ck->check_begin[t]; c < ck->check_begin[t + 1]; ++c) {
       const uint64_t g0 = ck->signer_begin[c];
       const sv_txcheck_result r = sv_txcheck<true>(b, ck->signer_type + g0, ck->signer_weight + g0, ck->signer_key + g0,

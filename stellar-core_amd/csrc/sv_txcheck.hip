@@ -19,7 +19,12 @@
 // registers, and called out of line it made the common path spill around a
 // call it never makes, so the kernel every check runs is
 // built without it and defers the rare check that needs it to a second kernel
-// behind it on the same stream.  Neither has scratch.
+// behind it on the same stream.  The signed-payload pass goes the same way: in
+// the kernel every check runs it cost 20 bytes of scratch at 8 waves/SIMD
+// (DESIGN.md 3.13), so that kernel gives up where the pass would have to run --
+// the first three stages did not succeed and a type-3 signer is live in a body
+// that has payload pairs -- and the second kernel decides the check from the
+// start.  Neither has scratch.
 #include <hip/hip_runtime.h>
 
 #include "launch.h"
@@ -45,6 +50,13 @@ struct sv_checkparams {
   const uint8_t* signer_type;    // n_signers
   const uint32_t* signer_weight;
   const uint32_t* signer_key;
+  // the payload pairing's output and the candidates' CSR array; ppair_begin == nullptr: no payload pairs in this call
+  const uint64_t* ppair_begin;   // n_bodies + 1
+  const uint64_t* pkey_begin;    // n_bodies + 1
+  const uint32_t* ppair_sig;     // n_ppairs
+  const uint32_t* ppair_key;
+  const uint8_t* ppair_verdict;
+  uint64_t n_ppairs, n_pkeys;
   uint64_t n_bodies, n_sigs, n_keys, n_pairs, n_checks, n_signers;
   uint32_t clamp;
   uint8_t* ok;                   // n_checks
@@ -55,11 +67,12 @@ struct sv_checkparams {
 __device__ __forceinline__ uint64_t sv_min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
 
 // One check.  SLOW = false is the kernel every check runs: the decision without
-// the SHA-256, 8 waves/SIMD; a check that meets a HASH_X signer whose hint
-// matches stores SV_TXCHECK_DEFER in check_ok.  SLOW = true, launched right
+// the SHA-256 and the signed-payload pass, 8 waves/SIMD; a check that meets a
+// HASH_X signer whose hint matches, or that needs the payload pass, stores
+// SV_TXCHECK_DEFER in check_ok.  SLOW = true, launched right
 // after it on the same stream, returns at once for every other check and
-// decides the deferred ones with the SHA-256 inlined, at whatever registers
-// that takes.
+// decides the deferred ones with the SHA-256 and the payload pass inlined, at
+// whatever registers that takes.
 template <bool SLOW>
 __device__ __forceinline__ void sv_txcheck_lane(const sv_checkparams& p) {
   const uint64_t c = (uint64_t)blockIdx.x * SV_CHECKBLOCK + threadIdx.x;
@@ -94,6 +107,18 @@ __device__ __forceinline__ void sv_txcheck_lane(const sv_checkparams& p) {
     b.k0 = sv_min64(p.key_begin[t], b.k1);
     b.p1 = sv_min64(p.pair_begin[t + 1], p.n_pairs);
     b.p0 = sv_min64(p.pair_begin[t], b.p1);
+    b.ppair_sig = p.ppair_sig;
+    b.ppair_key = p.ppair_key;
+    b.ppair_verdict = p.ppair_verdict;
+    b.q0 = b.q1 = b.pp0 = b.pp1 = 0;
+    if (p.ppair_begin) {
+      b.pp1 = sv_min64(p.ppair_begin[t + 1], p.n_ppairs);
+      b.pp0 = sv_min64(p.ppair_begin[t], b.pp1);
+      if (b.pp1 > b.pp0) {
+        b.q1 = sv_min64(p.pkey_begin[t + 1], p.n_pkeys);
+        b.q0 = sv_min64(p.pkey_begin[t], b.q1);
+      }
+    }
     const uint64_t g1 = sv_min64(p.signer_begin[c + 1], p.n_signers);
     const uint64_t g0 = sv_min64(p.signer_begin[c], g1);
     r = sv_txcheck<SLOW>(b, p.signer_type + g0, p.signer_weight + g0, p.signer_key + g0,
@@ -111,15 +136,18 @@ extern "C" {
 
 int sv_check_block(void) { return SV_CHECKBLOCK; }
 
-hipError_t sv_launch_txcheck(const uint64_t* sig_begin, const void* hint, const void* sig, const uint8_t* sig_len,
-                             uint64_t n_sigs, const uint64_t* key_begin, const void* key, uint64_t n_keys,
-                             uint64_t n_bodies, const uint64_t* pair_begin, const uint32_t* pair_sig,
-                             const uint32_t* pair_key, const void* pair_verdict, uint64_t n_pairs,
-                             const void* digests, const uint64_t* check_begin, const int32_t* check_needed,
-                             uint64_t n_checks, const uint64_t* signer_begin, const uint8_t* signer_type,
-                             const uint32_t* signer_weight, const uint32_t* signer_key, uint64_t n_signers,
-                             int clamp, uint8_t* check_ok, uint32_t* check_weight, uint64_t* check_used,
-                             hipStream_t s) {
+hipError_t sv_launch_txcheck_payload(const uint64_t* sig_begin, const void* hint, const void* sig,
+                                     const uint8_t* sig_len, uint64_t n_sigs, const uint64_t* key_begin,
+                                     const void* key, uint64_t n_keys, uint64_t n_bodies, const uint64_t* pair_begin,
+                                     const uint32_t* pair_sig, const uint32_t* pair_key, const void* pair_verdict,
+                                     uint64_t n_pairs, const void* digests, const uint64_t* check_begin,
+                                     const int32_t* check_needed, uint64_t n_checks, const uint64_t* signer_begin,
+                                     const uint8_t* signer_type, const uint32_t* signer_weight,
+                                     const uint32_t* signer_key, uint64_t n_signers, int clamp,
+                                     const uint64_t* ppair_begin, const uint32_t* ppair_sig,
+                                     const uint32_t* ppair_key, const void* ppair_verdict, uint64_t n_ppairs,
+                                     const uint64_t* pkey_begin, uint64_t n_pkeys, uint8_t* check_ok,
+                                     uint32_t* check_weight, uint64_t* check_used, hipStream_t s) {
   if (n_checks == 0) return hipSuccess;
   sv_checkparams p;
   p.sig_begin = sig_begin;
@@ -146,6 +174,13 @@ hipError_t sv_launch_txcheck(const uint64_t* sig_begin, const void* hint, const 
   p.n_checks = n_checks;
   p.n_signers = n_signers;
   p.clamp = clamp ? 1u : 0u;
+  p.ppair_begin = n_ppairs ? ppair_begin : nullptr;
+  p.pkey_begin = pkey_begin;
+  p.ppair_sig = ppair_sig;
+  p.ppair_key = ppair_key;
+  p.ppair_verdict = (const uint8_t*)ppair_verdict;
+  p.n_ppairs = n_ppairs;
+  p.n_pkeys = n_pkeys;
   p.ok = check_ok;
   p.weight = check_weight;
   p.used = check_used;
@@ -155,6 +190,22 @@ hipError_t sv_launch_txcheck(const uint64_t* sig_begin, const void* hint, const 
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(sv_txcheck_hashx_kernel, dim3(blocks), dim3(SV_CHECKBLOCK), 0, s, p);
   return hipGetLastError();
+}
+
+hipError_t sv_launch_txcheck(const uint64_t* sig_begin, const void* hint, const void* sig, const uint8_t* sig_len,
+                             uint64_t n_sigs, const uint64_t* key_begin, const void* key, uint64_t n_keys,
+                             uint64_t n_bodies, const uint64_t* pair_begin, const uint32_t* pair_sig,
+                             const uint32_t* pair_key, const void* pair_verdict, uint64_t n_pairs,
+                             const void* digests, const uint64_t* check_begin, const int32_t* check_needed,
+                             uint64_t n_checks, const uint64_t* signer_begin, const uint8_t* signer_type,
+                             const uint32_t* signer_weight, const uint32_t* signer_key, uint64_t n_signers,
+                             int clamp, uint8_t* check_ok, uint32_t* check_weight, uint64_t* check_used,
+                             hipStream_t s) {
+  return sv_launch_txcheck_payload(sig_begin, hint, sig, sig_len, n_sigs, key_begin, key, n_keys, n_bodies, pair_begin,
+                                   pair_sig, pair_key, pair_verdict, n_pairs, digests, check_begin, check_needed,
+                                   n_checks, signer_begin, signer_type, signer_weight, signer_key, n_signers, clamp,
+                                   nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, check_ok, check_weight,
+                                   check_used, s);
 }
 
 }  // extern "C"

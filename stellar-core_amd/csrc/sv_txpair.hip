@@ -20,10 +20,22 @@
 // run of the second level (above it each lane of the scan block sums more than
 // one block).  Device-resident CSR arrays are not validated by the host: every
 // range is clamped to its array, and the fill never writes at or past n_pairs.
+//
+// The payload pairing (sv_ppair_*) is the same scheme over a body's
+// signed-payload candidates (key, payload row, payload length): a pair exists
+// iff the signature's hint equals hint(key) XOR hint(payload)
+// (txcheck.h sv_payload_hint), the order is (body, signature, candidate), and
+// the fill gathers key, signature, the 64-byte payload row as the pair's
+// message slot and the slot's offset and length for a variable-length verify
+// launch.  Its count kernel writes its own cnt / bsum, the scan kernel above
+// runs on them unchanged, and its total lands in the word behind the ed25519
+// total, so one 16-byte copy brings both counts back.  Most bodies have no
+// payload candidate: such a lane reads its two CSR words and nothing else.
 #include <hip/hip_runtime.h>
 
 #include "launch.h"
 #include "sv_common.h"
+#include "txcheck.h"
 
 #define SV_PAIRBLOCK 256
 
@@ -161,6 +173,109 @@ __global__ __launch_bounds__(SV_PAIRBLOCK) void sv_pair_fill_kernel(sv_fillparam
   }
 }
 
+// ---- payload pairing
+struct sv_ppairparams {
+  sv_pairparams q;            // sig_begin, hint, sig, n_bodies, n_sigs; cnt / bsum / total / pair_begin: this pairing's
+  const uint64_t* pkey_begin; // n_bodies + 1
+  const uint8_t* pkey;        // n_pkeys x 32 B
+  const uint8_t* payload;     // n_pkeys x 64 B
+  const uint8_t* plen;        // n_pkeys
+  uint64_t n_pkeys;
+};
+
+struct sv_pfillparams {
+  sv_ppairparams pp;
+  uint64_t n_pairs;           // slots of the pair arrays (the scan's total)
+  uint32_t* pair_sig;
+  uint32_t* pair_key;         // the candidate's global index
+  uint4* gkey;                // n_pairs x 32 B
+  uint4* gsig;                // n_pairs x 64 B
+  uint4* gmsg;                // n_pairs x 64 B: the payload rows
+  uint64_t* goff;             // n_pairs: 64 i
+  uint32_t* glen;             // n_pairs: the payload lengths
+};
+
+// Body t's payload candidates [c0, c1) and signatures [s0, s1), clamped; the
+// signature words are only read for a body that has candidates.
+__device__ __forceinline__ sv_range sv_ppair_range(const sv_ppairparams& pp, uint64_t t) {
+  sv_range r;
+  r.k1 = pp.pkey_begin[t + 1] < pp.n_pkeys ? pp.pkey_begin[t + 1] : pp.n_pkeys;
+  r.k0 = pp.pkey_begin[t] < r.k1 ? pp.pkey_begin[t] : r.k1;
+  r.s0 = r.s1 = 0;
+  if (r.k1 > r.k0) {
+    r.s1 = pp.q.sig_begin[t + 1] < pp.q.n_sigs ? pp.q.sig_begin[t + 1] : pp.q.n_sigs;
+    r.s0 = pp.q.sig_begin[t] < r.s1 ? pp.q.sig_begin[t] : r.s1;
+  }
+  return r;
+}
+
+__device__ __forceinline__ uint32_t sv_ppair_len(const sv_ppairparams& pp, uint64_t c) {
+  const uint32_t l = pp.plen[c];
+  return l > 64u ? 64u : l;
+}
+
+__device__ __forceinline__ uint32_t sv_ppair_hint(const sv_ppairparams& pp, uint64_t c) {
+  return sv_payload_hint(pp.pkey + 32 * c, pp.payload + 64 * c, sv_ppair_len(pp, c));
+}
+
+__global__ __launch_bounds__(SV_PAIRBLOCK) void sv_ppair_count_kernel(sv_ppairparams pp) {
+  const sv_pairparams& q = pp.q;
+  const uint64_t t = (uint64_t)blockIdx.x * SV_PAIRBLOCK + threadIdx.x;
+  uint64_t c = 0;
+  if (t < q.n_bodies) {
+    const sv_range r = sv_ppair_range(pp, t);
+    SV_NOUNROLL for (uint64_t k = r.k0; k < r.k1; ++k) {
+      const uint32_t h = sv_ppair_hint(pp, k);
+      SV_NOUNROLL for (uint64_t s = r.s0; s < r.s1; ++s) c += q.hint[s] == h ? 1u : 0u;
+    }
+    q.cnt[t] = c;
+  }
+  uint64_t sum;
+  (void)sv_block_exscan(c, &sum);
+  if (threadIdx.x == 0) q.bsum[blockIdx.x] = sum;
+}
+
+__global__ __launch_bounds__(SV_PAIRBLOCK) void sv_ppair_fill_kernel(sv_pfillparams p) {
+  const sv_ppairparams& pp = p.pp;
+  const sv_pairparams& q = pp.q;
+  const uint64_t t = (uint64_t)blockIdx.x * SV_PAIRBLOCK + threadIdx.x;
+  const bool live = t < q.n_bodies;
+  const uint64_t c = live ? q.cnt[t] : 0;
+  uint64_t sum;
+  uint64_t i = q.bsum[blockIdx.x] + sv_block_exscan(c, &sum);
+  if (!live) return;
+  q.pair_begin[t] = i;
+  if (c == 0) return;
+  const sv_range r = sv_ppair_range(pp, t);
+  SV_NOUNROLL for (uint64_t s = r.s0; s < r.s1; ++s) {
+    const uint32_t h = q.hint[s];
+    SV_NOUNROLL for (uint64_t k = r.k0; k < r.k1; ++k) {
+      if (sv_ppair_hint(pp, k) != h) continue;
+      if (i >= p.n_pairs) return;  // (the arrays changed under us: never write past them)
+      p.pair_sig[i] = (uint32_t)s;
+      p.pair_key[i] = (uint32_t)k;
+      const uint4* key = (const uint4*)pp.pkey;
+      const uint4* pay = (const uint4*)pp.payload;
+      const uint4 k0 = key[2 * k], k1 = key[2 * k + 1];
+      const uint4 s0 = q.sig[4 * s], s1 = q.sig[4 * s + 1], s2 = q.sig[4 * s + 2], s3 = q.sig[4 * s + 3];
+      const uint4 m0 = pay[4 * k], m1 = pay[4 * k + 1], m2 = pay[4 * k + 2], m3 = pay[4 * k + 3];
+      p.gkey[2 * i] = k0;
+      p.gkey[2 * i + 1] = k1;
+      p.gsig[4 * i] = s0;
+      p.gsig[4 * i + 1] = s1;
+      p.gsig[4 * i + 2] = s2;
+      p.gsig[4 * i + 3] = s3;
+      p.gmsg[4 * i] = m0;
+      p.gmsg[4 * i + 1] = m1;
+      p.gmsg[4 * i + 2] = m2;
+      p.gmsg[4 * i + 3] = m3;
+      p.goff[i] = 64 * i;
+      p.glen[i] = sv_ppair_len(pp, k);
+      ++i;
+    }
+  }
+}
+
 static unsigned sv_pair_blocks(uint64_t n_bodies) { return (unsigned)((n_bodies + SV_PAIRBLOCK - 1) / SV_PAIRBLOCK); }
 
 extern "C" {
@@ -233,6 +348,62 @@ hipError_t sv_launch_pair_fill(const uint64_t* sig_begin, const void* hint, cons
   p.digests = (const uint4*)digests;
   const unsigned blocks = sv_pair_blocks(n_bodies);
   hipLaunchKernelGGL(sv_pair_fill_kernel, dim3(blocks), dim3(SV_PAIRBLOCK), 0, s, p);
+  return hipGetLastError();
+}
+
+// ---- payload pairing: its workspace is cnt (8 n_bodies) | bsum (8 blocks), each 16-byte aligned; its total is the
+// second word of the ed25519 pairing's total slot in `ws` (sv_pair_total(ws, n_bodies)[1])
+size_t sv_ppair_ws_bytes(uint64_t n_bodies) { return sv_pair_ws_bytes(n_bodies) - 16; }
+
+static sv_ppairparams sv_ppair_params(const uint64_t* sig_begin, const void* hint, const void* sig, uint64_t n_sigs,
+                                      const uint64_t* pkey_begin, const void* pkey, const void* payload,
+                                      const uint8_t* plen, uint64_t n_pkeys, uint64_t n_bodies, void* ws, void* pws,
+                                      uint64_t* ppair_begin) {
+  sv_ppairparams pp;
+  pp.q = sv_pair_params(sig_begin, hint, sig, n_sigs, nullptr, nullptr, 0, n_bodies, pws, ppair_begin);
+  pp.q.total = (uint64_t*)sv_pair_total(ws, n_bodies) + 1;
+  pp.pkey_begin = pkey_begin;
+  pp.pkey = (const uint8_t*)pkey;
+  pp.payload = (const uint8_t*)payload;
+  pp.plen = plen;
+  pp.n_pkeys = n_pkeys;
+  return pp;
+}
+
+// Count and scan, after sv_launch_pair_count on the same `ws` and stream: afterwards sv_pair_total(ws, n_bodies)[1]
+// and ppair_begin[n_bodies] hold the number of payload pairs.  n_bodies >= 1.
+hipError_t sv_launch_ppair_count(const uint64_t* sig_begin, const void* hint, uint64_t n_sigs,
+                                 const uint64_t* pkey_begin, const void* pkey, const void* payload,
+                                 const uint8_t* plen, uint64_t n_pkeys, uint64_t n_bodies, void* ws, void* pws,
+                                 uint64_t* ppair_begin, hipStream_t s) {
+  const sv_ppairparams pp = sv_ppair_params(sig_begin, hint, nullptr, n_sigs, pkey_begin, pkey, payload, plen, n_pkeys,
+                                            n_bodies, ws, pws, ppair_begin);
+  const unsigned blocks = sv_pair_blocks(n_bodies);
+  hipLaunchKernelGGL(sv_ppair_count_kernel, dim3(blocks), dim3(SV_PAIRBLOCK), 0, s, pp);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(sv_pair_scan_kernel, dim3(1), dim3(SV_PAIRBLOCK), 0, s, pp.q, (uint64_t)blocks);
+  return hipGetLastError();
+}
+
+// Fill, after sv_launch_ppair_count on the same arguments and stream.
+hipError_t sv_launch_ppair_fill(const uint64_t* sig_begin, const void* hint, const void* sig, uint64_t n_sigs,
+                                const uint64_t* pkey_begin, const void* pkey, const void* payload,
+                                const uint8_t* plen, uint64_t n_pkeys, uint64_t n_bodies, void* ws, void* pws,
+                                uint64_t* ppair_begin, uint64_t n_pairs, uint32_t* pair_sig, uint32_t* pair_key,
+                                void* gkey, void* gsig, void* gmsg, uint64_t* goff, uint32_t* glen, hipStream_t s) {
+  sv_pfillparams p;
+  p.pp = sv_ppair_params(sig_begin, hint, sig, n_sigs, pkey_begin, pkey, payload, plen, n_pkeys, n_bodies, ws, pws,
+                         ppair_begin);
+  p.n_pairs = n_pairs;
+  p.pair_sig = pair_sig;
+  p.pair_key = pair_key;
+  p.gkey = (uint4*)gkey;
+  p.gsig = (uint4*)gsig;
+  p.gmsg = (uint4*)gmsg;
+  p.goff = goff;
+  p.glen = glen;
+  hipLaunchKernelGGL(sv_ppair_fill_kernel, dim3(sv_pair_blocks(n_bodies)), dim3(SV_PAIRBLOCK), 0, s, p);
   return hipGetLastError();
 }
 
