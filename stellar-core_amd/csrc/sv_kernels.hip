@@ -149,16 +149,24 @@ __global__ __launch_bounds__(SV_BLOCK) void sv_keyslot_kernel(sv_cparams c) {
     unsigned long long w = __hip_atomic_load(&t.index[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (w == 0ull) {
       if (__hip_atomic_load(&t.count[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= t.limit) break;
+      // A claim takes its place under the limit BEFORE it takes the slot: lanes
+      // that read the same count would otherwise all claim, and the claims
+      // would pass the limit by as many lanes as were in flight.  A lane that
+      // then loses the slot gives its place back.
+      if (atomicAdd(&t.count[1], 1u) >= t.limit) {
+        atomicSub(&t.count[1], 1u);
+        break;
+      }
       w = atomicCAS(&t.index[s], 0ull, fp);
       if (w == 0ull) {  // claimed: sv_keybuild_kernel decodes this key into slot s
         sv_u4* e = t.store + s * SV_KT_QUADS + SV_KT_TQUADS;
         e[0] = sv_u4{A[0], A[1], A[2], A[3]};
         e[1] = sv_u4{A[4], A[5], A[6], A[7]};
         t.builders[atomicAdd(&t.count[0], 1u)] = (uint32_t)s;
-        atomicAdd(&t.count[1], 1u);
         ks = (uint32_t)s;
         break;
       }
+      atomicSub(&t.count[1], 1u);  // (another lane took the slot first)
     }
     if (w == fp) {  // (the prep kernel compares the entry's 32 bytes)
       ks = (uint32_t)s;

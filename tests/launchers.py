@@ -11,32 +11,27 @@ test input fails as a Python assertion, never as a GPU fault.  Each wrapper
 synchronises before it returns, so its tensors outlive the kernels.
 """
 import ctypes
-import os
-import re
 
 import numpy as np
 import torch
 
-_CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "stellar-core_amd", "csrc")
+from kernel_defs import (REC_FLAGS, SV_ATAB_ENTRIES, SV_COMB_CHAIN_WAVES, SV_DBG_MAX_WINDOWS,  # noqa: F401
+                         SV_DBG_PREP_ONLY, SV_DBG_TRIVIAL_PAIR, SV_KEY_BAD, SV_KEY_OK, SV_KP_IN_PLACE, SV_KP_OCT_HI,
+                         SV_KP_OCT_HI_WIDE, SV_KT_NONE, SV_KT_TQUADS, SV_LAT_MIN_WINDOWS, SV_LTAB_QUADS, SV_OSIGS,
+                         SV_QENT, SV_QSIGS, SV_QSLOT_QUADS, SV_REC_OK, SV_REC_RNEG, SV_REC_TOP8A, SV_REC_TOP8R,
+                         SV_SLOT_QUADS_L, _define)
 
-
-def _define(header, name):
-    """The integer value of `#define name <literal>` in csrc/header, read from the source the kernels are built from."""
-    with open(os.path.join(_CSRC, header)) as fh:
-        m = re.search(r"^#define\s+%s\s+(0[xX][0-9a-fA-F]+|\d+)[uU]?\b" % re.escape(name), fh.read(), re.M)
-    assert m, "%s: no #define %s" % (header, name)
-    return int(m.group(1), 0)
-
-
-SV_KP_OCT_HI, SV_KP_OCT_HI_WIDE, SV_KP_IN_PLACE = (_define("keytab.h", n) for n in
-                                                   ("SV_KP_OCT_HI", "SV_KP_OCT_HI_WIDE", "SV_KP_IN_PLACE"))
-SV_KEY_BAD, SV_KEY_OK = _define("comb.h", "SV_KEY_BAD"), _define("comb.h", "SV_KEY_OK")
-SV_COMB_CHAIN_WAVES = _define("comb.h", "SV_COMB_CHAIN_WAVES")  # chain waves per comb workgroup
-SV_OSIGS = _define("sv_kernels.hip", "SV_OSIGS")                # signatures per octet workgroup
 PATH_ONE_LANE, PATH_OCTET, PATH_QUAD = 1, 2, 3
+GUARD_BYTES, FILL = 4096, 0xA5
 MSG_PAD = 32  # bytes after the last message: the latency loaders read whole aligned 16-byte blocks
 
 _vp, _sz, _u32, _u64, _int = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
+
+
+class sv_ktparams(ctypes.Structure):
+    """keytab.h struct sv_ktparams"""
+    _fields_ = [("index", _vp), ("store", _vp), ("kslot", _vp), ("builders", _vp), ("count", _vp), ("mask", _u64),
+                ("limit", _u32), ("salt", _u64)]
 
 
 def prototypes(lib):
@@ -63,7 +58,11 @@ def prototypes(lib):
     lib.sv_occupancy_blocks_per_cu.argtypes = []
     lib.sv_launch_verify.restype = _int
     lib.sv_launch_verify.argtypes = [_int, _int, ctypes.c_uint, _vp, _vp, _vp, _vp, _vp, _u32, _u64, _vp, _vp, _vp, _vp,
-                                     _u32, _int, _vp, _vp, _vp]
+                                     _u32, _int, ctypes.POINTER(sv_ktparams), _vp, _vp]
+    lib.sv_key_table_entry_bytes.restype = _sz
+    lib.sv_key_table_entry_bytes.argtypes = []
+    lib.sv_plan_chunk_max.restype = _u64
+    lib.sv_plan_chunk_max.argtypes = [_u64]
     return lib
 
 
@@ -139,6 +138,64 @@ class Batch:
         return Batch(dev, self.h_pk[sel], self.h_sig[sel], [self.h_msgs[i] for i in sel], self.mode, self.want[sel])
 
 
+class Guarded:
+    """A device buffer of nbytes, every byte preset to `fill`, with GUARD_BYTES
+    of 0xA5 behind it that no kernel may touch.  t: the declared part."""
+
+    def __init__(self, dev, nbytes, fill=FILL):
+        self.nbytes = max(16, int(nbytes))
+        self.full = torch.full((self.nbytes + GUARD_BYTES,), FILL, dtype=torch.uint8, device=dev)
+        self.t = self.full[:self.nbytes]
+        if fill != FILL:
+            self.t.fill_(fill)
+        assert self.t.data_ptr() % 16 == 0 and self.t.data_ptr() == self.full.data_ptr()
+
+    def check(self, what=""):
+        assert bool((self.full[self.nbytes:] == FILL).all()), (what, "bytes behind the buffer were written")
+
+    def words(self):
+        """the declared part on the host, as uint32"""
+        return self.t.cpu().numpy().view(np.uint32)
+
+    def data_ptr(self):
+        return self.t.data_ptr()
+
+
+class KeyStore:
+    """The arrays of one sv_ktparams (keytab.h) for launches of up to n
+    signatures: 2^k = mask + 1 slots, claims stop at `limit`.  index and count
+    start at 0 (0 is their empty state); store, kslot and builders hold 0xA5."""
+
+    def __init__(self, L, n, mask, limit, salt):
+        assert mask + 1 > 0 and (mask + 1) & mask == 0 and 0 < limit <= mask + 1
+        self.n, self.mask, self.limit, self.salt = n, mask, limit, salt
+        self.entry_bytes = L.lib.sv_key_table_entry_bytes()
+        self.chunk = L.lib.sv_plan_chunk_max(n)
+        self.index = Guarded(L.dev, 8 * (mask + 1), 0)
+        self.store = Guarded(L.dev, (mask + 1) * self.entry_bytes)
+        self.kslot = Guarded(L.dev, 4 * self.chunk)
+        self.builders = Guarded(L.dev, 4 * self.chunk)
+        self.count = Guarded(L.dev, 16, 0)
+        self.count.nbytes = 8  # (two words; the buffer cannot be shorter than a quad)
+
+    def params(self, n):
+        assert n <= self.n and self.kslot.nbytes >= 4 * self.chunk and self.builders.nbytes >= 4 * self.chunk
+        assert self.count.nbytes == 8 and self.index.nbytes == 8 * (self.mask + 1)
+        assert self.store.nbytes == (self.mask + 1) * self.entry_bytes and self.store.data_ptr() % 16 == 0
+        return sv_ktparams(self.index.data_ptr(), self.store.data_ptr(), self.kslot.data_ptr(),
+                           self.builders.data_ptr(), self.count.data_ptr(), self.mask, self.limit, self.salt)
+
+    def check(self):
+        for g in (self.index, self.store, self.kslot, self.builders):
+            g.check("sv_ktparams")
+        assert bool((self.count.full[8:16] == 0).all()) and bool((self.count.full[16:] == FILL).all()), "count[2..]"
+
+
+class Verdicts(tuple):
+    """(verdicts, bitmap words + 1 guard word, status word) of a verify launch; .ws: its workspace (Guarded)."""
+    ws = None
+
+
 class Launchers:
     def __init__(self, lib, dev):
         self.lib, self.dev = prototypes(lib), dev
@@ -156,23 +213,59 @@ class Launchers:
         torch.cuda.synchronize(self.dev)
 
     # ---- throughput / cold latency tables and launches (sv_kernels.hip)
-    def btab(self):
-        t = self._alloc(self.lib.sv_btab_bytes())
-        assert _bytes_of(t) >= self.lib.sv_btab_bytes()
-        self._done(self.lib.sv_launch_btab_init(t.data_ptr(), self.stream), "sv_launch_btab_init")
-        return t
+    def guarded(self, nbytes, fill=FILL):
+        return Guarded(self.dev, nbytes, fill)
 
-    def verify(self, b, n, path, btab, dbg=0, bitmap=True):
-        """sv_launch_verify of the first n rows of b -> (verdicts, bitmap words + 1 guard word, status word)."""
+    def btab(self):
+        """Both base-point tables, built into a buffer preset to 0xA5 with a guard behind it."""
+        g = self.guarded(self.lib.sv_btab_bytes())
+        assert g.nbytes >= self.lib.sv_btab_bytes()
+        self._done(self.lib.sv_launch_btab_init(g.data_ptr(), self.stream), "sv_launch_btab_init")
+        g.check("sv_launch_btab_init")
+        return g.t
+
+    def workspace(self, path, n):
+        """A caller-owned workspace for verify(ws=...) of up to n signatures on `path`."""
+        need = self.lib.sv_verify_ws_bytes(path, self._grid(n), n)
+        assert need > 0
+        return self.guarded(need)
+
+    def keystore(self, n, mask=1023, limit=None, salt=0x5eed5eed5eed5eed):
+        return KeyStore(self, n, mask, mask + 1 if limit is None else limit, salt)
+
+    def _grid(self, n):
+        bt = self.lib.sv_block_threads()
+        return max(1, min(self.cus * self.lib.sv_occupancy_blocks_per_cu(), (n + bt - 1) // bt))
+
+    def ws_layout(self, n):
+        """Of a one-lane-path workspace for n signatures: (cap, dword offset of the records, dwords per record,
+        dword offset of the wave window counts); the tables of signature li start at dword li * 4 * SV_SLOT_QUADS_L."""
+        cap = self.lib.sv_plan_chunk_max(n)
+        need = self.lib.sv_verify_ws_bytes(PATH_ONE_LANE, 1, n)
+        rec_bytes = (need - cap // 64 * 4) // cap - 16 * SV_SLOT_QUADS_L
+        assert rec_bytes % 16 == 0 and cap * (16 * SV_SLOT_QUADS_L + rec_bytes) + cap // 64 * 4 == need
+        rec0 = cap * 4 * SV_SLOT_QUADS_L
+        return cap, rec0, rec_bytes // 4, rec0 + cap * rec_bytes // 4
+
+    def verify(self, b, n, path, btab, dbg=0, bitmap=True, ws=None, kt=None):
+        """sv_launch_verify of the first n rows of b -> Verdicts (verdicts, bitmap words + 1 guard word, status
+        word), its .ws the workspace: ws (a Guarded of workspace()) or one allocated here.  kt: a KeyStore."""
         b.check(n)
         assert path in (PATH_ONE_LANE, PATH_OCTET, PATH_QUAD)
-        assert dbg & ~(SV_KP_OCT_HI | SV_KP_OCT_HI_WIDE | SV_KP_IN_PLACE) == 0
-        bt = self.lib.sv_block_threads()
-        grid = max(1, min(self.cus * self.lib.sv_occupancy_blocks_per_cu(), (n + bt - 1) // bt))
+        knobs = SV_DBG_TRIVIAL_PAIR | SV_DBG_MAX_WINDOWS | SV_DBG_PREP_ONLY
+        assert dbg & ~(SV_KP_OCT_HI | SV_KP_OCT_HI_WIDE | SV_KP_IN_PLACE | knobs) == 0
+        assert not (dbg & SV_DBG_PREP_ONLY) or path == PATH_ONE_LANE
+        assert kt is None or (path == PATH_ONE_LANE and not dbg & SV_KP_IN_PLACE)
+        grid = self._grid(n)
         need = self.lib.sv_verify_ws_bytes(path, grid, n)
-        ws = self._alloc(need) if need else None
-        assert ws is None or _bytes_of(ws) >= need
+        if ws is None:
+            ws = self.guarded(need) if need else None
+        else:
+            # the whole launch is one chunk, so the workspace holds every signature's state afterwards
+            assert need > 0 and (path != PATH_ONE_LANE or self.lib.sv_plan_chunk_max(n) >= n)
+        assert ws is None or (ws.nbytes >= need and ws.data_ptr() % 16 == 0)
         assert _bytes_of(btab) >= self.lib.sv_btab_bytes()
+        ktp = kt.params(n) if kt is not None else None
         out = torch.full((n + 64,), 7, dtype=torch.uint8, device=self.dev)
         words = (n + 63) // 64
         bm = torch.full((words + 1,), -1, dtype=torch.int64, device=self.dev)
@@ -180,17 +273,25 @@ class Launchers:
         rc = self.lib.sv_launch_verify(b.mode, path, grid, _ptr(b.pk), _ptr(b.sig), _ptr(b.msg),
                                        _ptr(b.off) if b.mode == 1 else None, _ptr(b.len) if b.mode == 1 else None,
                                        b.fixed_len, n, _ptr(out), _ptr(bm) if bitmap else None, _ptr(ws), _ptr(btab),
-                                       dbg, 0, None, _ptr(status), self.stream)
+                                       dbg, 0, ctypes.byref(ktp) if ktp is not None else None, _ptr(status),
+                                       self.stream)
         self._done(rc, "sv_launch_verify")
         got = out.cpu().numpy()
         assert (got[n:] == 7).all(), "bytes after verdict[n] were written"
-        return got[:n], bm.cpu().numpy(), int(status[0].item())
+        if ws is not None:
+            ws.check("sv_launch_verify workspace")
+        if kt is not None:
+            kt.check()
+        res = Verdicts((got[:n], bm.cpu().numpy(), int(status[0].item())))
+        res.ws = ws
+        return res
 
     # ---- warm latency path (sv_comb.hip)
     def comb_btab(self):
-        t = self._alloc(self.lib.sv_comb_btab_bytes())
-        self._done(self.lib.sv_launch_comb_btab(t.data_ptr(), self.stream), "sv_launch_comb_btab")
-        return t
+        g = self.guarded(self.lib.sv_comb_btab_bytes())
+        self._done(self.lib.sv_launch_comb_btab(g.data_ptr(), self.stream), "sv_launch_comb_btab")
+        g.check("sv_launch_comb_btab")
+        return g.t
 
     def keytab(self, keys, slots, nslots, guard=0xA5):
         """Builds the tables of `keys` (k x 32 host bytes) into `slots` (k distinct
@@ -202,7 +303,8 @@ class Launchers:
         assert keys.shape == (k, 32) and slots.shape == (k,) and k > 0
         assert len(set(slots.tolist())) == k and int(slots.max()) < nslots
         sb = self.lib.sv_key_slot_bytes()
-        ktab = self._alloc(nslots * sb, guard)
+        gk = self.guarded(nslots * sb, guard)
+        ktab = gk.t
         kstat = torch.full((nslots,), 0x5A5A5A5A, dtype=torch.int32, device=self.dev)
         assert _bytes_of(ktab) >= nslots * sb and kstat.numel() >= nslots
         d_keys = torch.from_numpy(keys).to(self.dev)
@@ -211,6 +313,7 @@ class Launchers:
         rc = self.lib.sv_launch_keytab(d_keys.data_ptr(), d_slots.data_ptr(), k, ktab.data_ptr(), kstat.data_ptr(),
                                        self.stream)
         self._done(rc, "sv_launch_keytab")
+        gk.check("sv_launch_keytab")
         return ktab, kstat
 
     def comb(self, b, n, spw, kslot, ktab, kstat, ctab):

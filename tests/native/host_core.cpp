@@ -259,6 +259,55 @@ extern "C" int hc_lattice_reduce(const uint8_t h[32], uint8_t c0[32], uint8_t c1
   return lat.bits;
 }
 
+// Table and record twins (tests/test_tables_cpu.py): what the kernels leave in
+// memory for one another, built by the same functions on the host.
+// Base-point table entry e of the table shifted by `shift` bits (36 dwords).
+extern "C" void hc_btab_entry_shift(uint32_t out[SV_BTAB_STRIDE], int e, int shift) {
+  sv_btab_entry_shift(out, e, shift);
+}
+// sv_build_ltab of a decoded encoding (negated as the kernels decode -A and
+// -R): 9 entries x 40 dwords; returns whether the encoding decodes.
+extern "C" int hc_build_ltab(uint32_t out[SV_ATAB_ENTRIES * SV_LTAB_QUADS * 4], const uint8_t enc[32], int negate) {
+  uint32_t w[8];
+  load_words(w, enc);
+  ge_p3 P;
+  const bool ok = ge_frombytes(P, w, negate != 0);
+  std::vector<sv_u4> tab(SV_ATAB_ENTRIES * SV_LTAB_QUADS);
+  sv_build_ltab(tab.data(), P);
+  memcpy(out, tab.data(), tab.size() * sizeof(sv_u4));
+  return ok ? 1 : 0;
+}
+// sv_lat_pre + sv_lat_prepare of one signature at W windows (W <= 0: the
+// lane's own count): rec = dA[8] dR[8] dB0[] dB1[] as the prep kernel's record
+// holds them; info = rneg, top8A, top8R, ok (sv_lat_pre's verdict of (1)-(5)
+// and R's decode), the lane's own window count, the W used; tabs (optional):
+// the tables of -A and -R, 2 x 9 x 40 dwords.
+extern "C" void hc_lat_record(const uint8_t pk[32], const uint8_t sig[64], const uint8_t* msg, uint32_t len, int W,
+                              int trivial, uint32_t* rec, int32_t info[6], uint32_t* tabs) {
+  uint32_t A[8], R[8], S[8], hram[16];
+  load_words(A, pk);
+  load_words(R, sig);
+  load_words(S, sig + 32);
+  sha512_ram_var(hram, R, A, msg, len);
+  std::vector<sv_u4> slot(SV_SLOT_QUADS_L);
+  sv_lat lat;
+  const bool ok = sv_lat_pre(lat, A, R, S, hram, slot.data(), slot.data() + SV_ATAB_ENTRIES * SV_LTAB_QUADS,
+                             trivial != 0);
+  const int wl = sv_lat_windows(lat.bits);
+  if (W <= 0) W = wl;
+  sv_lat_digits D;
+  sv_lat_prepare(D, lat, S, W);
+  memcpy(rec, D.dA, 32);
+  memcpy(rec + 8, D.dR, 32);
+  for (int j = 0; j < SV_LB_DIGITS; ++j) {
+    rec[16 + j] = (uint32_t)D.dB0[j];
+    rec[16 + SV_LB_DIGITS + j] = (uint32_t)D.dB1[j];
+  }
+  const int32_t v[6] = {D.rneg, D.top8A, D.top8R, ok, wl, W};
+  memcpy(info, v, sizeof(v));
+  if (tabs) memcpy(tabs, slot.data(), slot.size() * sizeof(sv_u4));
+}
+
 // Engine stubs for timing the host mirror's own bookkeeping (no crypto):
 // every row valid; keyed stub returns sig[0..32) as the "key" (unique rows).
 extern "C" int hc_stub_verify(const uint8_t*, const uint8_t*, const uint8_t*, const uint64_t*, const uint32_t*,
@@ -300,6 +349,12 @@ static void init_cb() {
         sv_comb_bentry(&g_cb[(size_t)id * SV_CE_DW], id / SV_CB_ENT, id % SV_CB_ENT);
     });
   for (auto& x : th) x.join();
+}
+
+// the comb base table (SV_CB_DW dwords) as init_cb builds it
+extern "C" void hc_comb_btab(uint32_t* out) {
+  std::call_once(g_cb_once, init_cb);
+  memcpy(out, g_cb.data(), (size_t)SV_CB_DW * 4);
 }
 
 // tables of -A (layout of one key-cache slot); returns the key status

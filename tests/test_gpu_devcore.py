@@ -31,14 +31,12 @@ import pytest
 
 import fe_bounds as fb
 from conftest import REPO
+from edwards_ref import (BASE, D, L, N8, SQRTM1, T8, aff_add, aff_enc, aff_from_y, aff_mul, aff_neg,  # noqa: F401
+                         assert_projective, coords, limbs)
 from fe_bounds import OFF, P, value
 
 pytestmark = pytest.mark.gpu
 
-L = 2**252 + 27742317777372353535851937790883648493
-N8 = 8 * L
-D = -121665 * pow(121666, P - 2, P) % P
-SQRTM1 = pow(2, (P - 1) // 4, P)
 GUARD = 0xA5A5A5A5
 
 # probe -> dwords per output row (tests/native/dev_core.hip); the CPU suite
@@ -112,11 +110,6 @@ def u32(rows, width):
 
 def fes(rows):
     return u32(rows, 10)
-
-
-def limbs(v):
-    """canonical-width limbs of v < 2^255"""
-    return [(v >> OFF[i]) & ((1 << fb.WIDTH[i]) - 1) for i in range(10)]
 
 
 def limbs_wide(v):
@@ -474,48 +467,7 @@ def test_lattice_reduce_pinned_set_equals_host(dc, hostcore):
 
 
 # ========================================================== the affine reference
-def aff_add(p, q):
-    """Edwards addition law on affine points (a = -1), plain."""
-    (x1, y1), (x2, y2) = p, q
-    t = D * x1 * x2 * y1 * y2 % P
-    return ((x1 * y2 + x2 * y1) * pow(1 + t, P - 2, P) % P, (y1 * y2 + x1 * x2) * pow(1 - t, P - 2, P) % P)
-
-
-def aff_neg(p):
-    return (-p[0] % P, p[1])
-
-
-def aff_mul(k, p):
-    q = (0, 1)
-    while k:
-        if k & 1:
-            q = aff_add(q, p)
-        p = aff_add(p, p)
-        k >>= 1
-    return q
-
-
-def aff_from_y(y, sign):
-    u, v = (y * y - 1) % P, (D * y * y + 1) % P
-    x = u * pow(v, 3, P) * pow(u * pow(v, 7, P), (P - 5) // 8, P) % P
-    if (v * x * x - u) % P:
-        if (v * x * x + u) % P:
-            return None
-        x = x * SQRTM1 % P
-    if x & 1 != sign:
-        x = -x % P
-    return (x, y)
-
-
-def aff_enc(p):
-    return p[1] | ((p[0] & 1) << 255)
-
-
-BASE = aff_from_y(4 * pow(5, P - 2, P) % P, 0)
-
-
-# one of the order-8 encodings on libsodium's small-order list
-T8 = aff_from_y(int.from_bytes(bytes.fromhex("26e8958fc2b227b045c3f489f2ef98f0d5dfac05d3c63339b13802886d53fc05"), "little"), 0)
+# (the plain Edwards law, BASE, T8 and assert_projective: tests/edwards_ref.py)
 TORSION = [aff_mul(k, T8) for k in range(8)]  # the eight small-order points
 assert len(set(TORSION)) == 8 and aff_mul(8, T8) == (0, 1)
 _POOL = []
@@ -559,19 +511,6 @@ def cached_of(rng, pt):
 
 def flat(rows):
     return [sum(r, []) for r in rows]
-
-
-def coords(row):
-    return [value(row[10 * k:10 * k + 10]) % P for k in range(len(row) // 10)]
-
-
-def assert_projective(row, pt, wantT=True, what=""):
-    X, Y, Z, T = coords(row)
-    assert Z != 0, (what, "Z = 0")
-    zi = pow(Z, P - 2, P)
-    assert (X * zi % P, Y * zi % P) == pt, (what, "not the reference point")
-    if wantT:
-        assert T * Z % P == X * Y % P, (what, "T Z != X Y")
 
 
 # ======================================================== D. points, per lane
