@@ -142,6 +142,10 @@ int svh_check_txset(const svh_tx* txs, size_t ntx, const svh_decorated_sig* sigs
  * enumeration, [2] the overlapped middle (engine on half 0 beside half 1's enumeration, then engine on
  * half 1 beside half 0's checkers), [3] half 1's checkers. */
 void svh_txset_last_phases(double out[4]);
+/* std::vector<Signer> copies of signer lists the mirror's transaction checks have
+ * built since the process started (one per check on every path but the
+ * reference lists of prefetch 7). */
+uint64_t svh_signer_lists_built(void);
 
 /* ---- transaction-level checks (a13) ---- */
 typedef struct svh_account {
@@ -238,7 +242,20 @@ int svh_check_envelopes(const svh_envelope* env, size_t n, const svh_decorated_s
  *               pairs them by their XORed hint, verifies the pairs over the
  *               payloads and runs the fourth stage, so every decision is final
  *               and no check continues on the host.  Fallback, limits and
- *               results as prefetch 5. */
+ *               results as prefetch 5.
+ *   prefetch 7  the checks go to the engine as REFERENCES to the accounts: every
+ *               account a check names is put into one account table once (found
+ *               again by its account ID; a missing operation source's key and
+ *               the extra signers are pseudo-accounts), each check is (account,
+ *               threshold level), and ONE sv_ed25519_check_txbodies_accounts call
+ *               decides them all.  No signer list is copied per check, neither
+ *               for the engine nor when the decisions are consumed
+ *               (svh_signer_lists_built does not move).  Every decision is
+ *               final.  An engine error re-runs on
+ *               sv_ed25519_check_txbodies_accounts_cpu (counted in
+ *               svh_engine_stats.fallbacks).  Limits (64 signatures, 64 signers
+ *               in an account's list with its master key, 64-byte payloads),
+ *               protocol 7 and results as prefetch 5. */
 typedef struct svh_envelope_body {
   uint64_t off;
   uint32_t len;

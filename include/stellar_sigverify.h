@@ -506,6 +506,123 @@ int sv_ed25519_check_txbodies_cpu(const uint8_t* network_id, const uint8_t* bodi
                                   const sv_txchecks* checks, uint8_t* check_ok, uint32_t* check_weight,
                                   uint64_t* check_used, uint8_t* digests /* optional */, int threads);
 
+/* ---- Signature checks against a device-side account table ----------------
+ * The calls above take every check spelled out: each body brings its own copy
+ * of its candidate key rows and each check its own copy of its account's signer
+ * list.  A ledger holds an account once, and a transaction's source check and
+ * its operations' checks usually name the same account
+ * (TransactionFrame::checkSignature builds the signer list from the account
+ * entry: the master key with weight thresholds[0] if that is non-zero, then
+ * acc.signers; the needed weight is a threshold level of the same entry).
+ * These entry points take each account once, per body the accounts its checks
+ * refer to, and per check WHICH account and WHICH threshold level; the engine
+ * derives the explicit tables (csrc/txacct.h, on the device csrc/sv_txacct.hip)
+ * and runs the pipeline above on them unchanged.
+ *
+ *   accounts         acct_key (n_accounts x 32, the account ID's ed25519 key),
+ *                    acct_thresholds (n_accounts x 4: master weight, LOW, MED,
+ *                    HIGH, as AccountEntry.thresholds); account a's signers are
+ *                    asigner_begin[a] .. asigner_begin[a+1]-1: asigner_type
+ *                    (SV_SIGNER_*), asigner_weight, asigner_key (x 32; for type
+ *                    3 signedPayload.ed25519) and, read for type 3 only,
+ *                    asigner_payload, an index into apayload (n_apayloads x 64,
+ *                    rows zero-padded) / apayload_len (<= 64)
+ *   per body         bacct[bacct_begin[t] .. bacct_begin[t+1]-1]: the accounts
+ *                    body t's checks refer to, in any order; a duplicate only
+ *                    repeats candidate rows and changes no result
+ *   per check        check_acct: the position of its account inside its body's
+ *                    bacct range; check_level 1, 2, 3: needed =
+ *                    acct_thresholds[a][level]; 0: needed = check_needed[c]
+ *                    (check_needed is read only there)
+ *
+ * Level 0 makes the checks without a ledger account pseudo-accounts of the
+ * table: checkSignatureNoAccount is (master weight 1, no signers, needed 0),
+ * checkExtraSigners is (master weight 0, the extra signers with weight 1,
+ * needed = their count).
+ *
+ * The expansion is the definition.  Body t's candidate key list is, for each
+ * of its accounts in bacct order, acct_key iff the master weight is > 0, then
+ * the asigner_key of the account's signers of types 0-2 in list order; its
+ * payload candidates are its accounts' type-3 signers in the same order, as
+ * (key, payload, length).  Check c's signer list is (ED25519, master weight,
+ * the master's row) iff the master weight is > 0, then the account's signers
+ * in list order, a type-3 signer's signer_key being its index among the body's
+ * payload candidates.  check_ok, check_weight, check_used and digests are by
+ * definition those of sv_ed25519_check_txbodies* with an sv_txchecks_payload
+ * over that expansion; the limits stay 64 signers per check and 64 signatures
+ * per body.
+ *
+ * The host forms validate before any device work (SV_ERR_INVALID_ARG): a null
+ * required pointer, a malformed CSR array, a bacct entry >= n_accounts, a
+ * check_acct outside its body's range, a level > 3, a type > 3, a type-3
+ * asigner_payload >= n_apayloads, an apayload_len > 64, an account whose
+ * expanded list exceeds 64 signers, a body with checks and more than 64
+ * signatures, a sig_len > 64, protocol 7, 2^32 or more rows of any table and a
+ * struct_size that is too small.  The passes over the account table run once
+ * per account, not once per use.
+ * Host buffers: the account table goes up once per slot per call, ahead of the
+ * first chunk; chunks are whole bodies with their signatures, bacct entries and
+ * the three per-check arrays, bounded as in sv_ed25519_check_txbodies with the
+ * EXPANDED key, payload-candidate and signer counts standing in for the
+ * explicit ones.  opts->device == -1 slices the bodies as there. */
+typedef struct sv_txaccounts {
+  uint32_t struct_size;            /* sizeof(sv_txaccounts) */
+  uint32_t protocol_version;       /* as sv_txchecks */
+  const uint8_t* sig_len;          /* optional, n_sigs, as sv_txchecks */
+  const uint8_t* acct_key;         /* n_accounts x 32 */
+  const uint8_t* acct_thresholds;  /* n_accounts x 4 */
+  const uint64_t* asigner_begin;   /* n_accounts + 1 */
+  const uint8_t* asigner_type;     /* n_asigners */
+  const uint32_t* asigner_weight;  /* n_asigners */
+  const uint8_t* asigner_key;      /* n_asigners x 32 */
+  const uint32_t* asigner_payload; /* n_asigners (may be NULL when no signer has type 3) */
+  const uint8_t* apayload;         /* n_apayloads x 64 */
+  const uint8_t* apayload_len;     /* n_apayloads */
+  const uint64_t* bacct_begin;     /* n_bodies + 1 */
+  const uint32_t* bacct;           /* n_bacct */
+  const uint64_t* check_begin;     /* n_bodies + 1 */
+  const uint32_t* check_acct;      /* n_checks */
+  const uint8_t* check_level;      /* n_checks */
+  const int32_t* check_needed;     /* n_checks (may be NULL when no check has level 0) */
+  size_t n_accounts, n_asigners, n_apayloads, n_bacct, n_checks;
+} sv_txaccounts;
+int sv_ed25519_check_txbodies_accounts(const uint8_t* network_id /* 32 B */, const uint8_t* bodies,
+                                       const uint64_t* body_off, const uint32_t* body_len, const uint8_t* body_kind,
+                                       size_t n_bodies, const uint64_t* sig_begin, const uint8_t* hint,
+                                       const uint8_t* sig, size_t n_sigs, const sv_txaccounts* accts,
+                                       uint8_t* check_ok, uint32_t* check_weight, uint64_t* check_used,
+                                       uint8_t* digests /* optional, n_bodies x 32 */, const sv_opts* opts);
+/* Device-resident form: every array, those `accts` points to included, is
+ * device memory on `device` (d_sig, acct_key, asigner_key, apayload and the
+ * optional d_digests 16-byte aligned, the others naturally); network_id and
+ * the struct itself are host memory.  Nothing is validated: every range and
+ * index is clamped to its array -- a bacct entry >= n_accounts contributes
+ * nothing, a check whose check_acct lies outside its body's range or names such
+ * an entry has no signer and is 0, a level above 3 reads as 3, a payload index
+ * >= n_apayloads reads as the empty payload, a check considers its first 64
+ * signers -- and nothing is written outside the three outputs (and d_digests).
+ * With asigner_payload or check_needed NULL, type-3 signers read the empty
+ * payload and level-0 checks need 0.  The expanded tables live in the slot's
+ * workspace.  Their three row counts are only known on the device, so this form
+ * WAITS on `stream` once more than sv_ed25519_check_txbodies_device does: once
+ * for the three totals (before it sizes the row arrays), then once for the pair
+ * counts. */
+int sv_ed25519_check_txbodies_accounts_device(int device, const uint8_t* network_id /* host, 32 B */,
+                                              const void* d_bodies, const uint64_t* d_body_off,
+                                              const uint32_t* d_body_len, const uint8_t* d_body_kind, size_t n_bodies,
+                                              const uint64_t* d_sig_begin, const void* d_hint, const void* d_sig,
+                                              size_t n_sigs, const sv_txaccounts* accts /* host struct, device arrays */,
+                                              void* d_check_ok, uint32_t* d_check_weight, uint64_t* d_check_used,
+                                              void* d_digests, void* stream);
+/* The same contract on the engine's CPU path: the expansion on the host, then
+ * sv_ed25519_check_txbodies_cpu over it. */
+int sv_ed25519_check_txbodies_accounts_cpu(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                           const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                           const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig,
+                                           size_t n_sigs, const sv_txaccounts* accts, uint8_t* check_ok,
+                                           uint32_t* check_weight, uint64_t* check_used,
+                                           uint8_t* digests /* optional */, int threads);
+
 /* ---- Warm-key latency path (csrc/comb.h, csrc/sv_comb.hip) ---------------
  * Each device slot keeps a bounded cache of per-public-key tables
  * ({0..8} * 16^j * (-A), 108 KiB per key) in HBM.  A latency-path host batch

@@ -73,6 +73,8 @@ EXPORTED_SYMBOLS = (
     "sv_ed25519_verify_txbodies_hinted", "sv_ed25519_verify_txbodies_hinted_device",
     "sv_ed25519_verify_txbodies_hinted_cpu", "sv_txbodies_pair_bound",
     "sv_ed25519_check_txbodies", "sv_ed25519_check_txbodies_device", "sv_ed25519_check_txbodies_cpu",
+    "sv_ed25519_check_txbodies_accounts", "sv_ed25519_check_txbodies_accounts_device",
+    "sv_ed25519_check_txbodies_accounts_cpu",
 )
 
 # signer key types of the check entry points (include/stellar_sigverify.h)
@@ -115,6 +117,15 @@ class sv_txchecks(ctypes.Structure):
                 # covers them and pkey_begin is set)
                 ("pkey_begin", ctypes.c_void_p), ("pkey", ctypes.c_void_p), ("pkey_payload", ctypes.c_void_p),
                 ("pkey_len", ctypes.c_void_p), ("n_pkeys", ctypes.c_size_t)]
+
+
+class sv_txaccounts(ctypes.Structure):
+    _fields_ = ([("struct_size", ctypes.c_uint32), ("protocol_version", ctypes.c_uint32)]
+                + [(f, ctypes.c_void_p) for f in (
+                    "sig_len", "acct_key", "acct_thresholds", "asigner_begin", "asigner_type", "asigner_weight",
+                    "asigner_key", "asigner_payload", "apayload", "apayload_len", "bacct_begin", "bacct",
+                    "check_begin", "check_acct", "check_level", "check_needed")]
+                + [(f, ctypes.c_size_t) for f in ("n_accounts", "n_asigners", "n_apayloads", "n_bacct", "n_checks")])
 
 
 class FeedStats(ctypes.Structure):
@@ -202,6 +213,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.sv_ed25519_check_txbodies_cpu.argtypes = checked + [ctypes.c_int]
     lib.sv_ed25519_check_txbodies_device.argtypes = [ctypes.c_int] + checked + [vp]
     lib.sv_txbodies_pair_bound.restype = sz
+    by_acct = [vp, vp, vp, vp, vp, sz, vp, vp, vp, sz, ctypes.POINTER(sv_txaccounts), vp, vp, vp, vp]
+    lib.sv_ed25519_check_txbodies_accounts.argtypes = by_acct + [vp]
+    lib.sv_ed25519_check_txbodies_accounts_cpu.argtypes = by_acct + [ctypes.c_int]
+    lib.sv_ed25519_check_txbodies_accounts_device.argtypes = [ctypes.c_int] + by_acct + [vp]
     _lib = lib
     return lib
 
@@ -661,6 +676,144 @@ def check_txbodies_device(device: int, network_id, d_bodies: int, d_body_off: in
         d_sig_begin or None, d_hint or None, d_sig or None, n_sigs, d_key_begin or None, d_key or None, n_keys,
         ctypes.byref(ck), d_check_ok or None, d_check_weight or None, d_check_used or None, d_digests or None,
         stream or None))
+
+
+def _accounts_desc(protocol_version, sig_len, acct_key, acct_thresholds, asigner_begin, asigner_type, asigner_weight,
+                   asigner_key, asigner_payload, apayload, apayload_len, bacct_begin, bacct, check_begin, check_acct,
+                   check_level, check_needed, n_accounts, n_asigners, n_apayloads, n_bacct, n_checks):
+    """sv_txaccounts over raw addresses (host arrays' or device pointers; 0: NULL)."""
+    ac = sv_txaccounts()
+    ac.struct_size = ctypes.sizeof(sv_txaccounts)
+    ac.protocol_version = int(protocol_version)
+    for name, v in (("sig_len", sig_len), ("acct_key", acct_key), ("acct_thresholds", acct_thresholds),
+                    ("asigner_begin", asigner_begin), ("asigner_type", asigner_type),
+                    ("asigner_weight", asigner_weight), ("asigner_key", asigner_key),
+                    ("asigner_payload", asigner_payload), ("apayload", apayload), ("apayload_len", apayload_len),
+                    ("bacct_begin", bacct_begin), ("bacct", bacct), ("check_begin", check_begin),
+                    ("check_acct", check_acct), ("check_level", check_level), ("check_needed", check_needed)):
+        setattr(ac, name, v or None)
+    ac.n_accounts, ac.n_asigners, ac.n_apayloads = int(n_accounts), int(n_asigners), int(n_apayloads)
+    ac.n_bacct, ac.n_checks = int(n_bacct), int(n_checks)
+    return ac
+
+
+def _accounts_host(fn, last, network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, acct_key,
+                   acct_thresholds, asigner_begin, asigner_type, asigner_weight, asigner_key, asigner_payload,
+                   apayload, apayload_len, bacct_begin, bacct, check_begin, check_acct, check_level, check_needed,
+                   sig_len, protocol_version):
+    nid = np.ascontiguousarray(np.frombuffer(bytes(network_id), np.uint8))
+    if nid.size != 32:
+        raise ValueError("network_id must be 32 bytes")
+    hint, sig = _u8(hint, 4), _u8(sig, 64)
+    ns = sig.shape[0]
+    if hint.shape[0] != ns:
+        raise ValueError("hint/sig row mismatch")
+    kind = np.ascontiguousarray(np.asarray(body_kind, dtype=np.uint8).reshape(-1))
+    nb = kind.shape[0]
+    bodies, off, ln = _var_msgs(bodies, body_off, body_len, nb)
+    sb, eb, cb = _csr(sig_begin, nb, "sig_begin"), _csr(bacct_begin, nb, "bacct_begin"), _csr(check_begin, nb,
+                                                                                             "check_begin")
+
+    def arr(x, dt):
+        return np.ascontiguousarray(np.asarray(x if x is not None else [], dtype=dt).reshape(-1))
+    ak, th = _u8(acct_key, 32), _u8(acct_thresholds, 4)
+    na = ak.shape[0]
+    if th.shape[0] != na:
+        raise ValueError("acct_key / acct_thresholds row mismatch")
+    gb = np.ascontiguousarray(np.asarray(asigner_begin, dtype=np.uint64).reshape(-1))
+    if gb.shape[0] != na + 1:
+        raise ValueError("asigner_begin must hold n_accounts + 1 entries")
+    gt, gw, gk = arr(asigner_type, np.uint8), arr(asigner_weight, np.uint32), _u8(asigner_key, 32)
+    ng = gt.shape[0]
+    gp = arr(asigner_payload, np.uint32) if asigner_payload is not None else None
+    if gw.shape[0] != ng or gk.shape[0] != ng or (gp is not None and gp.shape[0] != ng):
+        raise ValueError("asigner_type / asigner_weight / asigner_key / asigner_payload row mismatch")
+    pay, pl = _u8(apayload if apayload is not None else [], 64), arr(apayload_len, np.uint8)
+    npay = pay.shape[0]
+    if pl.shape[0] != npay:
+        raise ValueError("apayload / apayload_len row mismatch")
+    ea, ca, lv = arr(bacct, np.uint32), arr(check_acct, np.uint32), arr(check_level, np.uint8)
+    nc = ca.shape[0]
+    need = arr(check_needed, np.int32) if check_needed is not None else None
+    if lv.shape[0] != nc or (need is not None and need.shape[0] != nc):
+        raise ValueError("check_acct / check_level / check_needed row mismatch")
+    sl = None
+    if sig_len is not None:
+        sl = arr(sig_len, np.uint8)
+        if sl.shape[0] != ns:
+            raise ValueError("sig_len must hold one byte per signature")
+    a = lambda x: x.__array_interface__["data"][0] if x is not None and x.size else 0  # noqa: E731
+    ac = _accounts_desc(protocol_version, a(sl), a(ak), a(th), gb.__array_interface__["data"][0], a(gt), a(gw), a(gk),
+                        a(gp), a(pay), a(pl), a(eb), a(ea), a(cb), a(ca), a(lv), a(need), na, ng, npay, ea.shape[0],
+                        nc)
+    ok, weight, used = np.zeros(nc, np.uint8), np.zeros(nc, np.uint32), np.zeros(nc, np.uint64)
+    dig = np.zeros((nb, 32), np.uint8)
+    _check(fn(_ptr(nid), _ptr(bodies), _ptr(off), _ptr(ln), _ptr(kind), nb, _ptr(sb), _ptr(hint), _ptr(sig), ns,
+              ctypes.byref(ac), _ptr(ok), _ptr(weight), _ptr(used), _ptr(dig), last))
+    return ok, weight, used, dig
+
+
+def check_txbodies_accounts(network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, acct_key,
+                            acct_thresholds, asigner_begin, asigner_type, asigner_weight, asigner_key,
+                            asigner_payload, apayload, apayload_len, bacct_begin, bacct, check_begin, check_acct,
+                            check_level, check_needed=None, sig_len=None, protocol_version: int = 21,
+                            device: int = -1, max_devices: int = 0, path=None):
+    """Signature checks against an account table (sv_ed25519_check_txbodies_accounts):
+    every account once (key, thresholds [master, low, med, high], its signers in
+    CSR form; a type-3 signer's asigner_payload indexes apayload / apayload_len),
+    per body the accounts its checks refer to (bacct_begin / bacct) and per check
+    the position of its account in that list and a threshold level (0: the
+    needed weight is check_needed[c]).  Returns (check_ok, check_weight,
+    check_used, digests), by definition those of check_txbodies over the
+    expansion (include/stellar_sigverify.h)."""
+    lib = load_library()
+    return _accounts_host(lib.sv_ed25519_check_txbodies_accounts, _opts(device, max_devices, path), network_id, bodies,
+                          body_off, body_len, body_kind, sig_begin, hint, sig, acct_key, acct_thresholds,
+                          asigner_begin, asigner_type, asigner_weight, asigner_key, asigner_payload, apayload,
+                          apayload_len, bacct_begin, bacct, check_begin, check_acct, check_level, check_needed,
+                          sig_len, protocol_version)
+
+
+def check_txbodies_accounts_cpu(network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, acct_key,
+                                acct_thresholds, asigner_begin, asigner_type, asigner_weight, asigner_key,
+                                asigner_payload, apayload, apayload_len, bacct_begin, bacct, check_begin, check_acct,
+                                check_level, check_needed=None, sig_len=None, protocol_version: int = 21,
+                                threads: int = 0):
+    """The same on the engine's CPU path (what a caller runs on an engine error)."""
+    lib = load_library()
+    return _accounts_host(lib.sv_ed25519_check_txbodies_accounts_cpu, int(threads), network_id, bodies, body_off,
+                          body_len, body_kind, sig_begin, hint, sig, acct_key, acct_thresholds, asigner_begin,
+                          asigner_type, asigner_weight, asigner_key, asigner_payload, apayload, apayload_len,
+                          bacct_begin, bacct, check_begin, check_acct, check_level, check_needed, sig_len,
+                          protocol_version)
+
+
+def check_txbodies_accounts_device(device: int, network_id, d_bodies: int, d_body_off: int, d_body_len: int,
+                                   d_body_kind: int, n_bodies: int, d_sig_begin: int, d_hint: int, d_sig: int,
+                                   n_sigs: int, d_acct_key: int, d_acct_thresholds: int, d_asigner_begin: int,
+                                   d_asigner_type: int, d_asigner_weight: int, d_asigner_key: int,
+                                   d_asigner_payload: int, d_apayload: int, d_apayload_len: int, n_accounts: int,
+                                   n_asigners: int, n_apayloads: int, d_bacct_begin: int, d_bacct: int, n_bacct: int,
+                                   d_check_begin: int, d_check_acct: int, d_check_level: int, d_check_needed: int,
+                                   n_checks: int, d_check_ok: int, d_check_weight: int, d_check_used: int,
+                                   d_sig_len: int = 0, protocol_version: int = 21, d_digests: int = 0,
+                                   stream: int = 0) -> None:
+    """Device-resident form (raw device pointers; network_id is 32 host bytes).
+    Waits on `stream` for the expansion's row counts and for the pair counts,
+    enqueues the verification and the check kernel and returns; the decisions
+    land in the d_check_* arrays."""
+    lib = load_library()
+    nid = np.ascontiguousarray(np.frombuffer(bytes(network_id), np.uint8))
+    if nid.size != 32:
+        raise ValueError("network_id must be 32 bytes")
+    ac = _accounts_desc(protocol_version, d_sig_len, d_acct_key, d_acct_thresholds, d_asigner_begin, d_asigner_type,
+                        d_asigner_weight, d_asigner_key, d_asigner_payload, d_apayload, d_apayload_len, d_bacct_begin,
+                        d_bacct, d_check_begin, d_check_acct, d_check_level, d_check_needed, n_accounts, n_asigners,
+                        n_apayloads, n_bacct, n_checks)
+    _check(lib.sv_ed25519_check_txbodies_accounts_device(
+        device, _ptr(nid), d_bodies or None, d_body_off or None, d_body_len or None, d_body_kind or None, n_bodies,
+        d_sig_begin or None, d_hint or None, d_sig or None, n_sigs, ctypes.byref(ac), d_check_ok or None,
+        d_check_weight or None, d_check_used or None, d_digests or None, stream or None))
 
 
 def verify_gather(items, keys: bool = False, device: int = -1, max_devices: int = 0):

@@ -13,6 +13,7 @@
 
 #include "engine_state.h"
 #include "host_image.h"
+#include "txacct.h"
 
 namespace sv {
 namespace {
@@ -975,6 +976,231 @@ inline int check_slice_locked(Device& D, const CheckIn& in, size_t B0, size_t B1
 
 inline int check_slice(Device& D, const CheckIn& in, size_t B0, size_t B1, int clamp, const CheckOut& out, int path) {
   return with_slot(D, [&] { return check_slice_locked(D, in, B0, B1, clamp, out, path); });
+}
+
+// ------------------------------------------------- checks by account
+// The explicit tables of a by-account check call on the device, in one buffer
+// (sv_txacct.hip fills them): the expansion's workspace (ws bytes) | key_begin |
+// pkey_begin (8 (k + 1) each) | signer_begin (8 (nc + 1)) | check_needed (4 nc) and, with the row counts known,
+// key (32 nk) | pkey (32 nq) | payload rows (64 nq) | signer_weight | signer_key (4 ng each) | pkey_len (nq) |
+// signer_type (ng); every section 16-byte aligned.  own_rows: the row sections are a buffer of their own, from
+// offset 0 (the device-resident form sizes them after its wait); else they follow the CSR part.
+struct AcctBufs {
+  size_t o_kb, o_qb, o_gb, o_need, head;                            // the CSR part: [0, head)
+  size_t o_key, o_qkey, o_qpay, o_gw, o_gk, o_qlen, o_gt, bytes;  // the rows: [o_key, bytes)
+};
+inline AcctBufs acct_layout(size_t ws, size_t k, size_t nc, bool own_rows, size_t nk, size_t nq, size_t ng) {
+  AcctBufs b;
+  b.o_kb = al16(ws);
+  b.o_qb = b.o_kb + al16(8 * (k + 1));
+  b.o_gb = b.o_qb + al16(8 * (k + 1));
+  b.o_need = b.o_gb + al16(8 * (nc + 1));
+  b.head = b.o_need + al16(4 * nc) + 16;
+  b.o_key = own_rows ? 0 : b.head;
+  b.o_qkey = b.o_key + 32 * nk;
+  b.o_qpay = b.o_qkey + 32 * nq;
+  b.o_gw = b.o_qpay + 64 * nq;
+  b.o_gk = b.o_gw + al16(4 * ng);
+  b.o_qlen = b.o_gk + al16(4 * ng);
+  b.o_gt = b.o_qlen + al16(nq);
+  b.bytes = b.o_gt + al16(ng) + 16;
+  return b;
+}
+inline sv_acct_out acct_out(const AcctBufs& L, uint8_t* head, uint8_t* rows, size_t nk, size_t nq, size_t ng) {
+  sv_acct_out O;
+  O.key_begin = (uint64_t*)(head + L.o_kb);
+  O.pkey_begin = (uint64_t*)(head + L.o_qb);
+  O.signer_begin = (uint64_t*)(head + L.o_gb);
+  O.check_needed = (int32_t*)(head + L.o_need);
+  O.key = rows + L.o_key;
+  O.pkey = rows + L.o_qkey;
+  O.ppay = rows + L.o_qpay;
+  O.gweight = (uint32_t*)(rows + L.o_gw);
+  O.gkey = (uint32_t*)(rows + L.o_gk);
+  O.plen = rows + L.o_qlen;
+  O.gtype = rows + L.o_gt;
+  O.nk = nk;
+  O.nq = nq;
+  O.ng = ng;
+  return O;
+}
+
+// The account table of a host call in D.txatab: key (32 na) | signer keys (32 ns) | payload rows (64 np) |
+// asigner_begin (8 (na + 1)) | weights | payload indices (4 ns each) | thresholds (4 na) | types (ns) | payload
+// lengths (np) | the per-account counts and ranks (sv_acct_tab_ws_bytes), every section 16-byte aligned.
+struct AcctTabBufs {
+  size_t o_skey, o_pay, o_sbeg, o_sw, o_sp, o_thr, o_st, o_pl, o_ws, bytes;
+};
+inline AcctTabBufs acct_tab_layout(size_t na, size_t ns, size_t np) {
+  AcctTabBufs b;
+  b.o_skey = 32 * na;
+  b.o_pay = b.o_skey + 32 * ns;
+  b.o_sbeg = b.o_pay + 64 * np;
+  b.o_sw = b.o_sbeg + al16(8 * (na + 1));
+  b.o_sp = b.o_sw + al16(4 * ns);
+  b.o_thr = b.o_sp + al16(4 * ns);
+  b.o_st = b.o_thr + al16(4 * na);
+  b.o_pl = b.o_st + al16(ns);
+  b.o_ws = b.o_pl + al16(np);
+  b.bytes = b.o_ws + al16(sv_acct_tab_ws_bytes(na, ns)) + 16;
+  return b;
+}
+
+// The account table up, once per slot per call, ahead of the first chunk: straight from the caller's arrays (they
+// stay valid for the whole call) on D.stream, then the per-account kernel.  *T: the table on the device.  Grown
+// like ensure_txpairs: the streams that may still read the old one are drained first.
+inline int acct_table_upload(Device& D, const sv_txaccounts& A, sv_acct_tab* T, const void** tab_ws) {
+  const size_t na = A.n_accounts, ns = A.n_asigners, np = A.n_apayloads;
+  const AcctTabBufs L = acct_tab_layout(na, ns, np);
+  if (L.bytes > D.txatab.cap) {
+    SV_HIP(hipStreamSynchronize(D.h2d));
+    SV_HIP(hipStreamSynchronize(D.stream));
+    int rc;
+    if ((rc = D.txatab.ensure(L.bytes))) return rc;
+  }
+  uint8_t* d = (uint8_t*)D.txatab.p;
+  auto up = [&](size_t o, const void* src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(d + o, src, bytes, hipMemcpyHostToDevice, D.stream) : hipSuccess;
+  };
+  SV_HIP(up(0, A.acct_key, 32 * na));
+  SV_HIP(up(L.o_skey, A.asigner_key, 32 * ns));
+  SV_HIP(up(L.o_pay, A.apayload, 64 * np));
+  SV_HIP(up(L.o_sbeg, A.asigner_begin, 8 * (na + 1)));
+  SV_HIP(up(L.o_sw, A.asigner_weight, 4 * ns));
+  if (A.asigner_payload) SV_HIP(up(L.o_sp, A.asigner_payload, 4 * ns));
+  SV_HIP(up(L.o_thr, A.acct_thresholds, 4 * na));
+  SV_HIP(up(L.o_st, A.asigner_type, ns));
+  SV_HIP(up(L.o_pl, A.apayload_len, np));
+  T->key = d;
+  T->skey = d + L.o_skey;
+  T->pay = d + L.o_pay;
+  T->sbeg = (const uint64_t*)(d + L.o_sbeg);
+  T->sweight = (const uint32_t*)(d + L.o_sw);
+  T->spay = A.asigner_payload ? (const uint32_t*)(d + L.o_sp) : nullptr;
+  T->thr = d + L.o_thr;
+  T->stype = d + L.o_st;
+  T->plen = d + L.o_pl;
+  T->na = na;
+  T->ns = ns;
+  T->np = np;
+  *tab_ws = d + L.o_ws;
+  SV_HIP(sv_launch_acct_table(T, d + L.o_ws, D.stream));
+  return SV_OK;
+}
+
+// Bodies [B0, B1) with their signatures, account entries and checks on one slot (caller holds D.mu, device set):
+// the account table up once, then check_slice_locked's sequence per chunk with the expansion kernels between the
+// upload and the pairing -- pack -> H2D -> contents hashes -> count, scan, begin, rows, signers (the row counts
+// are the planner's: no wait) -> pair count and scan -> the pair count back (the one wait) -> fill -> verify
+// launch -> check kernel.  A chunk's explicit tables live in the stage's d_acct.
+inline int acct_slice_locked(Device& D, const AcctIn& in, const sv_txaccounts& A, size_t B0, size_t B1, int clamp,
+                             const CheckOut& out, int path) {
+  int rc;
+  const std::vector<AcctChunk> plan = acct_plan(in, B0, B1, stage_chunk(), stage_chunk(), txbody_chunk_bytes(),
+                                                stage_chunk(), 8 * stage_chunk());
+  if (plan.empty()) return SV_OK;
+  const bool single = plan.size() == 1;
+  hipStream_t up_s = single ? D.stream : D.h2d, down_s = single ? D.stream : D.d2h;
+  sv_acct_tab T;
+  const void* tab_ws = nullptr;
+  if ((rc = acct_table_upload(D, A, &T, &tab_ws))) return rc;
+  if (!single) {
+    SV_HIP(hipEventRecord(D.dep_in, D.stream));
+    SV_HIP(hipStreamWaitEvent(D.h2d, D.dep_in, 0));
+  }
+  CheckPending pend[2];
+  for (size_t ci = 0; ci < plan.size(); ++ci) {
+    const AcctChunk& c = plan[ci];
+    Stage& s = D.st[ci & 1];
+    if ((rc = check_drain(s, pend[ci & 1], out))) return rc;
+    const size_t m = c.p.s1 - c.p.s0, k = c.p.b1 - c.p.b0, ne = c.e1 - c.e0, nc = c.c1 - c.c0;
+    const size_t q = c.nk, nq = c.nq, ng = c.ng;
+    const size_t wsb = al16(sv_pair_ws_bytes(k)), pbb = al16(8 * (k + 1)), pwsb = al16(sv_ppair_ws_bytes(k));
+    const AcctBufs L = acct_layout(sv_acct_ws_bytes(k, ne, nc), k, nc, false, q, nq, ng);
+    if ((rc = s.h_in.ensure(c.bytes)) || (rc = s.d_in.ensure(c.bytes)) || (rc = s.d_acct.ensure(L.bytes)) ||
+        (rc = s.d_pair.ensure(wsb + pbb + (nq ? pwsb + pbb : 0))) || (rc = s.d_keys.ensure(32 * k)) ||
+        (rc = s.h_cnt.ensure(64)))
+      return rc;
+    uint8_t* hp = (uint8_t*)s.h_in.p;
+    uint8_t* d = (uint8_t*)s.d_in.p;
+    uint8_t* da = (uint8_t*)s.d_acct.p;
+    acct_pack(in, c, hp);
+    if ((rc = upload_image(D, d, hp, c.bytes, up_s))) return rc;
+    const uint64_t* d_sb = (const uint64_t*)(d + c.p.o_sb);
+    uint64_t* d_pb = (uint64_t*)((uint8_t*)s.d_pair.p + wsb);
+    SV_HIP(sv_launch_txhash(D.grid * 8, in.h.nid, d + c.p.o_body, (const uint64_t*)(d + c.p.o_off),
+                            (const uint32_t*)(d + c.p.o_len), d + c.p.o_kind, k, nullptr, 0, nullptr, s.d_keys.p,
+                            up_s));
+    // the chunk's explicit tables from the table and the chunk's references
+    const sv_acct_use U{(const uint64_t*)(d + c.o_eb), (const uint32_t*)(d + c.o_ea), (const uint64_t*)(d + c.o_cb),
+                        (const uint32_t*)(d + c.o_ca), d + c.o_lvl, (const int32_t*)(d + c.o_need), k, ne, nc};
+    const sv_acct_out O = acct_out(L, da, da, q, nq, ng);
+    SV_HIP(sv_launch_acct_count(&T, tab_ws, &U, &O, da, up_s));
+    SV_HIP(sv_launch_acct_fill(&T, tab_ws, &U, &O, da, up_s));
+    const uint64_t* d_kb = O.key_begin;
+    SV_HIP(sv_launch_pair_count(d_sb, d + c.p.o_hint, d + c.p.o_sig, m, d_kb, O.key, q, k, s.d_pair.p, d_pb, up_s));
+    PayloadDev pl;
+    void* d_pws = (uint8_t*)s.d_pair.p + wsb + pbb;
+    uint64_t* d_ppb = (uint64_t*)((uint8_t*)s.d_pair.p + wsb + pbb + pwsb);
+    if (nq) {
+      pl.qb = O.pkey_begin;
+      pl.key = O.pkey;
+      pl.payload = O.ppay;
+      pl.len = O.plen;
+      pl.nq = nq;
+      SV_HIP(sv_launch_ppair_count(d_sb, d + c.p.o_hint, m, pl.qb, pl.key, pl.payload, pl.len, nq, k, s.d_pair.p, d_pws,
+                                   d_ppb, up_s));
+    }
+    SV_HIP(hipMemcpyAsync(s.h_cnt.p, sv_pair_total(s.d_pair.p, k), nq ? 16 : 8, hipMemcpyDeviceToHost, up_s));
+    SV_HIP(hipEventRecord(s.up, up_s));
+    SV_HIP(hipEventSynchronize(s.up));
+    const size_t np = (size_t)*(const uint64_t*)s.h_cnt.p;
+    const size_t npp = nq ? (size_t)((const uint64_t*)s.h_cnt.p)[1] : 0;
+    if (!single) SV_HIP(hipStreamWaitEvent(D.stream, s.up, 0));
+    if (npp && (rc = ensure_txpp(D, ppair_layout(npp).bytes))) return rc;
+    // verdicts (np, padded) | pair_sig, pair_key (4 np each, padded) | used | weight | ok
+    const size_t o_idx = al16(np), o_res = o_idx + al16(8 * np), o_dig = al16(13 * nc);
+    if ((rc = ensure_txpairs(D, np)) || (rc = s.d_verdict.ensure(o_res + 13 * nc + 16)) ||
+        (rc = s.h_out.ensure(o_dig + 32 * k)))
+      return rc;
+    uint8_t* dv = (uint8_t*)s.d_verdict.p;
+    uint32_t* d_ps = (uint32_t*)(dv + o_idx);
+    uint32_t* d_pk = d_ps + np;
+    SV_HIP(sv_launch_pair_fill(d_sb, d + c.p.o_hint, d + c.p.o_sig, m, d_kb, O.key, q, k, s.d_pair.p, d_pb, np, d_ps,
+                               d_pk, D.txpk.p, D.txsg.p, D.txmsg.p, s.d_keys.p, D.stream));
+    if (np && (rc = launch_locked(D, 0, path, D.txpk.p, D.txsg.p, D.txmsg.p, nullptr, nullptr, 32, np, dv, nullptr,
+                                  kt_mode() == 1)))
+      return rc;
+    if (npp && (rc = ppair_run(D, pl, d_sb, d + c.p.o_hint, d + c.p.o_sig, m, k, s.d_pair.p, d_pws, d_ppb, npp, path)))
+      return rc;
+    const PPairBufs PL = ppair_layout(npp);
+    const uint8_t* dpp = (const uint8_t*)D.txpp.p;
+    SV_HIP(sv_launch_txcheck_payload(
+        d_sb, d + c.p.o_hint, d + c.p.o_sig, in.sig_len ? d + c.o_sl : nullptr, m, d_kb, O.key, q, k, d_pb, d_ps, d_pk,
+        dv, np, s.d_keys.p, (const uint64_t*)(d + c.o_cb), O.check_needed, nc, O.signer_begin, O.gtype, O.gweight,
+        O.gkey, ng, clamp, d_ppb, (const uint32_t*)(dpp + PL.o_idx), (const uint32_t*)(dpp + PL.o_idx) + npp, dpp, npp,
+        pl.qb, nq, dv + o_res + 12 * nc, (uint32_t*)(dv + o_res + 8 * nc), (uint64_t*)(dv + o_res), D.stream));
+    if (!single) {
+      SV_HIP(hipEventRecord(s.done, D.stream));
+      SV_HIP(hipStreamWaitEvent(D.d2h, s.done, 0));
+    }
+    uint8_t* ho = (uint8_t*)s.h_out.p;
+    if (nc) SV_HIP(hipMemcpyAsync(ho, dv + o_res, 13 * nc, hipMemcpyDeviceToHost, down_s));
+    if (out.digests) SV_HIP(hipMemcpyAsync(ho + o_dig, s.d_keys.p, 32 * k, hipMemcpyDeviceToHost, down_s));
+    SV_HIP(hipEventRecord(s.down, down_s));
+    pend[ci & 1].busy = true;
+    pend[ci & 1].c.p = c.p;
+    pend[ci & 1].c.c0 = c.c0;
+    pend[ci & 1].c.c1 = c.c1;
+  }
+  for (int i = 0; i < 2; ++i)
+    if ((rc = check_drain(D.st[i], pend[i], out))) return rc;
+  return SV_OK;
+}
+
+inline int acct_slice(Device& D, const AcctIn& in, const sv_txaccounts& A, size_t B0, size_t B1, int clamp,
+                      const CheckOut& out, int path) {
+  return with_slot(D, [&] { return acct_slice_locked(D, in, A, B0, B1, clamp, out, path); });
 }
 
 }  // namespace

@@ -192,6 +192,7 @@ struct Stage {
   DevBuf d_in, d_verdict, d_keys;
   DevBuf d_pair;  // hinted tx-body chunks: the pairing workspace, then pair_begin / pair_sig / pair_key
   HostBuf h_cnt;  // ... and the chunk's pair count, read back before its verify launch
+  DevBuf d_acct;  // by-account check chunks: the expansion's workspace and the tables it fills (sv_txacct.hip)
   hipEvent_t up = nullptr, done = nullptr, down = nullptr, keys_down = nullptr;
   std::vector<hipEvent_t> pev;  // keys of piece k are down (one-chunk keyed batches)
   bool busy = false;  // a chunk's D2H is pending on `down`
@@ -293,6 +294,9 @@ struct Device {
   HostBuf h_txcnt;
   DevBuf txchk;  // device-resident check calls: the pairs' indices and verdicts, which stay inside the engine
   DevBuf txpp;   // check calls with payload candidates: the payload pairs' verdicts, indices and gathered arrays
+  // by-account check calls: the account table (host form: its image; both forms: the per-account counts and
+  // ranks), and the device-resident form's expansion -- workspace and CSR arrays, then the rows sized from its totals
+  DevBuf txatab, txaws, txarows;
   KernelTimer timer;  // the bulk launches (launch_locked)
   LatLane lat;
   KeyTabs kt;  // (under mu)
@@ -398,7 +402,7 @@ inline void release_device(Device& D) {
   for (Stage& s : D.st) {
     s.h_in.release(); s.h_out.release();
     s.d_in.release(); s.d_verdict.release(); s.d_keys.release();
-    s.d_pair.release(); s.h_cnt.release();
+    s.d_pair.release(); s.h_cnt.release(); s.d_acct.release();
     if (s.up) (void)hipEventDestroy(s.up);
     if (s.done) (void)hipEventDestroy(s.done);
     if (s.down) (void)hipEventDestroy(s.down);
@@ -410,6 +414,7 @@ inline void release_device(Device& D) {
   D.msg.release(); D.off.release(); D.len.release(); D.keys.release(); D.h_sha.release();
   D.txmsg.release();
   D.txpk.release(); D.txsg.release(); D.txpair.release(); D.h_txcnt.release(); D.txchk.release(); D.txpp.release();
+  D.txatab.release(); D.txaws.release(); D.txarows.release();
   D.ws.release();
   D.kt.index.release(); D.kt.store.release(); D.kt.kslot.release(); D.kt.builders.release();
   D.kt.count.release(); D.kt.h_count.release();

@@ -1096,6 +1096,32 @@ void checkTxBodiesUncached(const uint8_t* networkID, const uint8_t* bodies, cons
   gCpuSigs += nSigs;
 }
 
+void checkTxBodiesAccountsUncached(const uint8_t* networkID, const uint8_t* bodies, const uint64_t* bodyOff,
+                                   const uint32_t* bodyLen, const uint8_t* bodyKind, size_t nBodies,
+                                   const uint64_t* sigBegin, const uint8_t* hint, const uint8_t* sig, size_t nSigs,
+                                   const ::sv_txaccounts& accounts, uint8_t* checkOk, uint32_t* checkWeight,
+                                   uint64_t* checkUsed, uint8_t* digests) {
+  if (nBodies == 0) return;
+  const size_t work = std::max<size_t>(nSigs, 1);
+  int rc = timedBatch(true, work, [&] {
+    return sv_ed25519_check_txbodies_accounts(networkID, bodies, bodyOff, bodyLen, bodyKind, nBodies, sigBegin, hint,
+                                              sig, nSigs, &accounts, checkOk, checkWeight, checkUsed, digests, nullptr);
+  });
+  if (rc == SV_OK) {
+    gGpuSigs += nSigs;
+    gGpuBatches += 1;
+    return;
+  }
+  ++gFallbacks;
+  rc = timedBatch(false, work, [&] {
+    return sv_ed25519_check_txbodies_accounts_cpu(networkID, bodies, bodyOff, bodyLen, bodyKind, nBodies, sigBegin,
+                                                  hint, sig, nSigs, &accounts, checkOk, checkWeight, checkUsed,
+                                                  digests, 0);
+  });
+  if (rc != SV_OK) throw std::invalid_argument("checkTxBodiesAccountsUncached: malformed batch");
+  gCpuSigs += nSigs;
+}
+
 bool verifySig(PublicKey const& key, Signature const& signature, ByteSlice const& bin) {
   // the hit path as the reference runs it (SecretKey.cpp:446-456): key, one
   // lock, lookup, touch -- no batch bookkeeping; anything else (a miss, or an

@@ -37,6 +37,7 @@
 #include <vector>
 
 struct sv_txchecks;  // include/stellar_sigverify.h
+struct sv_txaccounts;
 
 namespace stellar {
 
@@ -182,6 +183,14 @@ void checkTxBodiesUncached(const uint8_t* networkID, const uint8_t* bodies, cons
                            const uint8_t* hint, const uint8_t* sig, size_t nSigs, const uint64_t* keyBegin,
                            const uint8_t* key, size_t nKeys, const ::sv_txchecks& checks, uint8_t* checkOk,
                            uint32_t* checkWeight, uint64_t* checkUsed, uint8_t* digests);
+
+// ... and one sv_ed25519_check_txbodies_accounts call (the by-account tables of sv_txaccounts): an engine error
+// re-runs the batch on sv_ed25519_check_txbodies_accounts_cpu and counts a fallback; a malformed batch throws.
+void checkTxBodiesAccountsUncached(const uint8_t* networkID, const uint8_t* bodies, const uint64_t* bodyOff,
+                                   const uint32_t* bodyLen, const uint8_t* bodyKind, size_t nBodies,
+                                   const uint64_t* sigBegin, const uint8_t* hint, const uint8_t* sig, size_t nSigs,
+                                   const ::sv_txaccounts& accounts, uint8_t* checkOk, uint32_t* checkWeight,
+                                   uint64_t* checkUsed, uint8_t* digests);
 
 void clearVerifySigCache();
 void maybeSeedVerifySigCache(unsigned int seed);

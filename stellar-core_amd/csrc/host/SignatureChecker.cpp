@@ -539,6 +539,141 @@ void SignatureBatchPrefetch::runDecided(const uint8_t* networkID, const uint8_t*
     if (bodies_[b].body.hashOut) std::memcpy(bodies_[b].body.hashOut->data(), &digests[32 * b], 32);
 }
 
+uint32_t SignatureBatchPrefetch::appendAccount(uint256 const* id, uint8_t const* thresholds,
+                                               std::vector<Signer> const* signers,
+                                               std::vector<SignerKey> const* extra) {
+  Accounts& a = acct_;
+  const uint32_t index = (uint32_t)(a.thr.size() / 4);
+  static const uint8_t kNoAccount[4] = {1, 0, 0, 0}, kExtra[4] = {0, 0, 0, 0};
+  const uint8_t* thr = extra ? kExtra : thresholds ? thresholds : kNoAccount;
+  a.key.resize(a.key.size() + 32, 0);
+  if (id) std::memcpy(&a.key[a.key.size() - 32], id->data(), 32);
+  a.thr.insert(a.thr.end(), thr, thr + 4);
+  auto add = [&](SignerKey const& k, uint32_t weight) {
+    a.stype.push_back((uint8_t)k.type);
+    a.sweight.push_back(weight);
+    a.skey.insert(a.skey.end(), k.key.begin(), k.key.end());
+    uint32_t row = 0;
+    if (k.type == SIGNER_KEY_TYPE_ED25519_SIGNED_PAYLOAD) {
+      row = (uint32_t)a.plen.size();
+      a.pay.resize(a.pay.size() + 64, 0);
+      if (!k.payload.empty()) std::memcpy(&a.pay[64 * (size_t)row], k.payload.data(), k.payload.size());
+      a.plen.push_back((uint8_t)k.payload.size());
+    }
+    a.spay.push_back(row);
+  };
+  if (extra)
+    for (auto const& k : *extra) add(k, 1);
+  else if (signers)
+    for (auto const& g : *signers) add(g.key, g.weight);
+  a.sbeg.push_back(a.stype.size());
+  return index;
+}
+
+bool SignatureBatchPrefetch::addDecidedRefs(TxBody const& body, std::vector<DecoratedSignature> const& signatures,
+                                            std::vector<SignatureCheckRef> const& checks) {
+  if (signatures.size() > 64) return false;
+  for (auto const& sig : signatures)
+    if (sig.signature.size() > 64) return false;
+  for (auto const& c : checks) {
+    if (c.extra) {
+      if (c.extra->size() > 64) return false;
+      for (auto const& k : *c.extra)
+        if (k.type == SIGNER_KEY_TYPE_ED25519_SIGNED_PAYLOAD && k.payload.size() > 64) return false;
+    } else if (c.thresholds) {
+      if ((c.thresholds[0] ? 1 : 0) + c.signers->size() > 64) return false;
+      for (auto const& g : *c.signers)
+        if (g.key.type == SIGNER_KEY_TYPE_ED25519_SIGNED_PAYLOAD && g.key.payload.size() > 64) return false;
+    }
+  }
+  Decided& d = dec_;
+  Accounts& a = acct_;
+  d.payload = true;  // (the table carries the payloads: every decision is final)
+  BodyEntry e;
+  e.body = body;
+  e.pair0 = e.pair1 = 0;
+  e.hashOff = ~0ull;
+  bodies_.push_back(e);
+  for (auto const& sig : signatures) {
+    const size_t i = d.sigLen.size();
+    d.hint.resize(4 * (i + 1));
+    d.sig.resize(64 * (i + 1), 0);
+    std::memcpy(&d.hint[4 * i], sig.hint.data(), 4);
+    if (!sig.signature.empty()) std::memcpy(&d.sig[64 * i], sig.signature.data(), sig.signature.size());
+    d.sigLen.push_back((uint8_t)sig.signature.size());
+  }
+  const size_t e0 = a.bacct.size();
+  for (auto const& c : checks) {
+    size_t pos;
+    if (c.thresholds && !c.extra) {
+      // a ledger account: once in the table, once in the body's list
+      auto it = a.byId.find(*c.id);
+      const uint32_t index =
+          it != a.byId.end() ? it->second : (a.byId[*c.id] = appendAccount(c.id, c.thresholds, c.signers, nullptr));
+      pos = e0;
+      while (pos < a.bacct.size() && a.bacct[pos] != index) ++pos;
+      if (pos == a.bacct.size()) a.bacct.push_back(index);
+    } else {
+      pos = a.bacct.size();
+      a.bacct.push_back(appendAccount(c.id, nullptr, nullptr, c.extra));
+    }
+    a.cacct.push_back((uint32_t)(pos - e0));
+    a.clevel.push_back(c.level);
+    d.needed.push_back(c.needed);
+  }
+  d.sigBegin.push_back(d.sigLen.size());
+  d.checkBegin.push_back(d.needed.size());
+  a.bacctBegin.push_back(a.bacct.size());
+  return true;
+}
+
+void SignatureBatchPrefetch::runDecidedRefs(const uint8_t* networkID, const uint8_t* blob, uint32_t protocolVersion) {
+  Decided& d = dec_;
+  Accounts& a = acct_;
+  const size_t nb = bodies_.size(), nc = d.needed.size();
+  d.ok.assign(nc, 0);
+  d.outWeight.assign(nc, 0);
+  d.used.assign(nc, 0);
+  if (nb == 0) return;
+  std::vector<uint64_t> off(nb);
+  std::vector<uint32_t> len(nb);
+  std::vector<uint8_t> kind(nb), digests(32 * nb);
+  for (size_t b = 0; b < nb; ++b) {
+    off[b] = bodies_[b].body.off;
+    len[b] = bodies_[b].body.len;
+    kind[b] = bodies_[b].body.kind;
+  }
+  sv_txaccounts A{};
+  A.struct_size = sizeof A;
+  A.protocol_version = protocolVersion;
+  A.sig_len = d.sigLen.data();
+  A.acct_key = a.key.data();
+  A.acct_thresholds = a.thr.data();
+  A.asigner_begin = a.sbeg.data();
+  A.asigner_type = a.stype.data();
+  A.asigner_weight = a.sweight.data();
+  A.asigner_key = a.skey.data();
+  A.asigner_payload = a.spay.data();
+  A.apayload = a.pay.data();
+  A.apayload_len = a.plen.data();
+  A.bacct_begin = a.bacctBegin.data();
+  A.bacct = a.bacct.data();
+  A.check_begin = d.checkBegin.data();
+  A.check_acct = a.cacct.data();
+  A.check_level = a.clevel.data();
+  A.check_needed = d.needed.data();
+  A.n_accounts = a.thr.size() / 4;
+  A.n_asigners = a.stype.size();
+  A.n_apayloads = a.plen.size();
+  A.n_bacct = a.bacct.size();
+  A.n_checks = nc;
+  PubKeyUtils::checkTxBodiesAccountsUncached(networkID, blob, off.data(), len.data(), kind.data(), nb,
+                                             d.sigBegin.data(), d.hint.data(), d.sig.data(), d.sigLen.size(), A,
+                                             d.ok.data(), d.outWeight.data(), d.used.data(), digests.data());
+  for (size_t b = 0; b < nb; ++b)
+    if (bodies_[b].body.hashOut) std::memcpy(bodies_[b].body.hashOut->data(), &digests[32 * b], 32);
+}
+
 SignatureBatchPrefetch::Decision SignatureBatchPrefetch::decision(size_t body, size_t check) const {
   const size_t c = (size_t)dec_.checkBegin.at(body) + check;
   if (c >= dec_.checkBegin.at(body + 1) || c >= dec_.ok.size())

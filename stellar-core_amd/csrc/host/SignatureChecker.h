@@ -26,6 +26,7 @@
 #include <cstdint>
 #include <functional>
 #include <memory>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
@@ -72,6 +73,19 @@ bool verifyEd25519SignedPayload(DecoratedSignature const& sig, SignerKey const& 
 struct SignatureCheck {
   std::vector<Signer> signers;
   int32_t needed = 0;
+};
+
+// One checkSignature call by reference -- nothing is copied.  A ledger account: `id` its account ID, `thresholds`
+// its four threshold bytes, `signers` its signer list, `level` 1..3 (needed = thresholds[level]).  The key of an
+// account that does not exist (checkSignatureNoAccount): `id` alone, level 0, needed 0.  The extra signers
+// (checkExtraSigners): `extra`, level 0, needed = their count.
+struct SignatureCheckRef {
+  uint256 const* id;
+  uint8_t const* thresholds;
+  std::vector<Signer> const* signers;
+  std::vector<SignerKey> const* extra;
+  uint8_t level;
+  int32_t needed;
 };
 
 // Verdicts computed ahead of the checkers.
@@ -172,6 +186,20 @@ class SignatureBatchPrefetch {
   bool decidedFinal() const { return dec_.payload; }
   void runDecided(const uint8_t* networkID, const uint8_t* blob, uint32_t protocolVersion);
   Decision decision(size_t body, size_t check) const;
+  // By-account form of the decided form (include/stellar_sigverify.h sv_txaccounts): the checks come as
+  // references.  addDecidedRefs puts every ledger account a check names into the prefetch's account table ONCE,
+  // found again by its account ID (a pseudo-account -- a missing source's key, the extra signers -- is a row of
+  // its own each time), lists the body's accounts and stores (account position, level, needed) per check; no
+  // signer list is copied per check or per body.  It returns false, adding nothing, beyond the engine's limits:
+  // more than 64 signatures, a signature or payload longer than 64 bytes, an account whose list (master included)
+  // exceeds 64 signers.  runDecidedRefs makes ONE sv_ed25519_check_txbodies_accounts call (an engine error re-runs
+  // it on the _cpu form and counts a fallback, never a reject); decision() then works as after runDecided, and
+  // every decision is final (decidedFinal()): signed-payload signers are in the table.  A prefetch takes one
+  // form only.
+  bool addDecidedRefs(TxBody const& body, std::vector<DecoratedSignature> const& signatures,
+                      std::vector<SignatureCheckRef> const& checks);
+  void runDecidedRefs(const uint8_t* networkID, const uint8_t* blob, uint32_t protocolVersion);
+  size_t decidedAccounts() const { return acct_.thr.size() / 4; }
   size_t decidedChecks() const { return dec_.needed.size(); }
   // verdict for (pk, sig, msg) if prefetched (tx: see addBatch)
   static constexpr size_t kNoTx = ~size_t(0);
@@ -240,6 +268,21 @@ class SignatureBatchPrefetch {
     std::vector<uint64_t> pkeyBegin{0};
     std::vector<uint8_t> pkey, pkeyPayload, pkeyLen;
   } dec_;
+  struct IdHash {
+    size_t operator()(uint256 const& k) const {
+      size_t v;
+      std::memcpy(&v, k.data(), sizeof v);
+      return v;
+    }
+  };
+  struct Accounts {  // the by-account form's tables (sv_txaccounts); signatures, needed and results live in dec_
+    std::vector<uint8_t> key, thr, stype, skey, pay, plen, clevel;
+    std::vector<uint64_t> sbeg{0}, bacctBegin{0};
+    std::vector<uint32_t> sweight, spay, bacct, cacct;
+    std::unordered_map<uint256, uint32_t, IdHash> byId;  // ledger accounts already in the table
+  } acct_;
+  uint32_t appendAccount(uint256 const* id, uint8_t const* thresholds, std::vector<Signer> const* signers,
+                         std::vector<SignerKey> const* extra);
   std::vector<uint64_t> hSigBegin_{0}, hKeyBegin_{0};  // hinted body form: CSR by body, in addHinted order
   static std::vector<Storage>& spares();
   static constexpr size_t kSpares = 4;

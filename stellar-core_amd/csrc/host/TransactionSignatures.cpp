@@ -5,12 +5,18 @@
 // OperationFrame.cpp:47-62,173-209 and FeeBumpTransactionFrame.cpp:138-197,267-287.
 #include "TransactionSignatures.h"
 
+#include <atomic>
+
 namespace stellar {
 namespace {
+
+// signer lists built as std::vector<Signer> copies (signerListsBuilt())
+std::atomic<uint64_t> gSignerListsBuilt{0};
 
 // TransactionFrame::checkSignature: master key (if its weight is non-zero)
 // then the account's signers
 std::vector<Signer> accountSigners(AccountSigState const& acc) {
+  gSignerListsBuilt.fetch_add(1, std::memory_order_relaxed);
   std::vector<Signer> signers;
   if (acc.thresholds[0]) {
     Signer m;
@@ -29,6 +35,7 @@ AccountSigState const* find(AccountSnapshot const& accounts, uint256 const& id) 
 }
 
 std::vector<Signer> extraSignerList(std::vector<SignerKey> const& keys) {
+  gSignerListsBuilt.fetch_add(1, std::memory_order_relaxed);
   std::vector<Signer> signers;
   for (auto const& k : keys) {
     Signer s;
@@ -47,7 +54,38 @@ Signer noAccountSigner(uint256 const& id) {
   return s;
 }
 
+// The three kinds of check as references (SignatureCheckRef): an account entry at a threshold level, the extra
+// signers, and the key of an account that does not exist.
+SignatureCheckRef accountRef(AccountSigState const& acc, int level) {
+  return SignatureCheckRef{&acc.accountID, acc.thresholds, &acc.signers, nullptr, (uint8_t)level,
+                           (int32_t)acc.thresholds[level]};
+}
+SignatureCheckRef extraRef(std::vector<SignerKey> const& keys) {
+  return SignatureCheckRef{nullptr, nullptr, nullptr, &keys, 0, (int32_t)keys.size()};
+}
+SignatureCheckRef noAccountRef(uint256 const& id) { return SignatureCheckRef{&id, nullptr, nullptr, nullptr, 0, 0}; }
+
+// ... and the list a reference stands for, as the copy the reference's checkSignature is handed
+SignatureCheck materialize(SignatureCheckRef const& r) {
+  if (r.extra) return SignatureCheck{extraSignerList(*r.extra), r.needed};
+  if (!r.thresholds) {
+    gSignerListsBuilt.fetch_add(1, std::memory_order_relaxed);
+    return SignatureCheck{std::vector<Signer>{noAccountSigner(*r.id)}, r.needed};
+  }
+  // (accountSigners' rule over the referenced parts)
+  gSignerListsBuilt.fetch_add(1, std::memory_order_relaxed);
+  std::vector<Signer> signers;
+  if (r.thresholds[0]) {
+    signers.push_back(noAccountSigner(*r.id));  // (the master: the account's key as an ed25519 signer)
+    signers.back().weight = r.thresholds[0];
+  }
+  signers.insert(signers.end(), r.signers->begin(), r.signers->end());
+  return SignatureCheck{std::move(signers), r.needed};
+}
+
 }  // namespace
+
+uint64_t signerListsBuilt() { return gSignerListsBuilt.load(std::memory_order_relaxed); }
 
 TxSigResult checkFeeBumpSignatures(FeeBumpSigInfo const& tx, AccountSnapshot const& accounts, uint32_t protocol,
                                    SignatureBatchPrefetch const* prefetched, bool forApply) {
@@ -81,9 +119,10 @@ TxSigResult checkFeeBumpSignatures(FeeBumpSigInfo const& tx, AccountSnapshot con
 namespace {
 
 // The sequence of checks of one transaction -- the one copy of it -- over any
-// checker: check(signers, needed) -> bool, allUsed() -> bool.  A SignatureChecker
-// (checkTransactionSignatures), a list (listTransactionChecks) and the engine's
-// decisions (checkTransactionSignaturesDecided) all walk it.
+// checker: check(SignatureCheckRef) -> bool, allUsed() -> bool.  A SignatureChecker
+// (checkTransactionSignatures), the lists (listTransactionChecks, listTransactionCheckRefs) and the engine's
+// decisions (checkTransactionSignaturesDecided, ...DecidedRefs) all walk it; byList adapts a checker that wants
+// the signer list as a copy.
 template <class Check, class AllUsed>
 TxSigResult walkTransaction(TransactionSigInfo const& tx, AccountSnapshot const& accounts, uint32_t protocol,
                             bool forApply, Check&& check, AllUsed&& allUsed) {
@@ -93,12 +132,11 @@ TxSigResult walkTransaction(TransactionSigInfo const& tx, AccountSnapshot const&
     r.code = txNO_ACCOUNT;
     return r;
   }
-  if (!check(accountSigners(*src), (int32_t)src->thresholds[THRESHOLD_LOW_LEVEL])) {
+  if (!check(accountRef(*src, THRESHOLD_LOW_LEVEL))) {
     r.code = txBAD_AUTH;
     return r;
   }
-  if (protocol >= 19 && !tx.extraSigners.empty() &&
-      !check(extraSignerList(tx.extraSigners), (int32_t)tx.extraSigners.size())) {
+  if (protocol >= 19 && !tx.extraSigners.empty() && !check(extraRef(tx.extraSigners))) {
     r.code = txBAD_AUTH;
     return r;
   }
@@ -110,7 +148,7 @@ TxSigResult walkTransaction(TransactionSigInfo const& tx, AccountSnapshot const&
     bool ok;
     int32_t opc = opINNER;
     if (acc) {
-      ok = check(accountSigners(*acc), (int32_t)acc->thresholds[op.level]);
+      ok = check(accountRef(*acc, op.level));
       if (!ok) opc = opBAD_AUTH;
     } else if (!op.sourceAccount) {
       // (processSignatures calls OperationFrame::checkSignature with
@@ -120,7 +158,7 @@ TxSigResult walkTransaction(TransactionSigInfo const& tx, AccountSnapshot const&
       ok = false;
       opc = opNO_ACCOUNT;
     } else {
-      ok = check(std::vector<Signer>{noAccountSigner(id)}, 0);
+      ok = check(noAccountRef(id));
       if (!ok) opc = opBAD_AUTH;
     }
     if (!ok && r.code != txFAILED) {
@@ -133,6 +171,14 @@ TxSigResult walkTransaction(TransactionSigInfo const& tx, AccountSnapshot const&
   if (r.code == txFAILED) return r;
   if (!allUsed()) r.code = txBAD_AUTH_EXTRA;
   return r;
+}
+
+template <class F>
+auto byList(F&& fn) {
+  return [&fn](SignatureCheckRef const& r) {
+    SignatureCheck c = materialize(r);
+    return fn(c.signers, c.needed);
+  };
 }
 
 // A checker that consumes the engine's decisions of one body in order.
@@ -164,6 +210,12 @@ class DecidedChecker {
         }
     return false;
   }
+  // a final decision (decidedFinal()): nothing but the decision is looked at
+  bool checkFinal() {
+    const SignatureBatchPrefetch::Decision d = mPre.decision(mBody, mNext++);
+    mUsed |= d.used;
+    return d.ok;
+  }
   bool allUsed() const {
     const size_t n = mSignatures.size();
     const uint64_t want = n >= 64 ? ~0ull : (1ull << n) - 1;
@@ -183,10 +235,11 @@ class DecidedChecker {
 TxSigResult checkTransactionSignatures(TransactionSigInfo const& tx, AccountSnapshot const& accounts,
                                        uint32_t protocol, SignatureBatchPrefetch const* prefetched, bool forApply) {
   SignatureChecker checker(protocol, tx.contentsHash, tx.signatures, prefetched);
-  return walkTransaction(
-      tx, accounts, protocol, forApply,
-      [&](std::vector<Signer> const& signers, int32_t needed) { return checker.checkSignature(signers, needed); },
-      [&] { return checker.checkAllSignaturesUsed(); });
+  auto check = [&](std::vector<Signer> const& signers, int32_t needed) {
+    return checker.checkSignature(signers, needed);
+  };
+  return walkTransaction(tx, accounts, protocol, forApply, byList(check),
+                         [&] { return checker.checkAllSignaturesUsed(); });
 }
 
 std::vector<SignatureCheck> listTransactionChecks(TransactionSigInfo const& tx, AccountSnapshot const& accounts,
@@ -194,11 +247,30 @@ std::vector<SignatureCheck> listTransactionChecks(TransactionSigInfo const& tx, 
   std::vector<SignatureCheck> out;
   (void)walkTransaction(
       tx, accounts, protocol, forApply,
-      [&](std::vector<Signer> signers, int32_t needed) {
-        out.push_back(SignatureCheck{std::move(signers), needed});
+      [&](SignatureCheckRef const& r) {
+        out.push_back(materialize(r));
         return true;
       },
       [] { return true; });
+  return out;
+}
+
+std::vector<SignatureCheckRef> listTransactionCheckRefs(TransactionSigInfo const& tx, AccountSnapshot const& accounts,
+                                                        uint32_t protocol, bool forApply) {
+  std::vector<SignatureCheckRef> out;
+  (void)walkTransaction(
+      tx, accounts, protocol, forApply,
+      [&](SignatureCheckRef const& r) {
+        out.push_back(r);
+        return true;
+      },
+      [] { return true; });
+  return out;
+}
+
+std::vector<SignatureCheckRef> listFeeBumpOuterCheckRefs(FeeBumpSigInfo const& tx, AccountSnapshot const& accounts) {
+  std::vector<SignatureCheckRef> out;
+  if (AccountSigState const* fee = find(accounts, tx.feeSource)) out.push_back(accountRef(*fee, THRESHOLD_LOW_LEVEL));
   return out;
 }
 
@@ -213,10 +285,46 @@ TxSigResult checkTransactionSignaturesDecided(TransactionSigInfo const& tx, Acco
                                               uint32_t protocol, SignatureBatchPrefetch const& pre, size_t body,
                                               bool forApply) {
   DecidedChecker checker(protocol, tx.signatures, pre, body);
+  auto check = [&](std::vector<Signer> const& signers, int32_t needed) { return checker.check(signers, needed); };
+  return walkTransaction(tx, accounts, protocol, forApply, byList(check), [&] { return checker.allUsed(); });
+}
+
+TxSigResult checkTransactionSignaturesDecidedRefs(TransactionSigInfo const& tx, AccountSnapshot const& accounts,
+                                                  uint32_t protocol, SignatureBatchPrefetch const& pre, size_t body,
+                                                  bool forApply) {
+  DecidedChecker checker(protocol, tx.signatures, pre, body);
   return walkTransaction(
-      tx, accounts, protocol, forApply,
-      [&](std::vector<Signer> const& signers, int32_t needed) { return checker.check(signers, needed); },
+      tx, accounts, protocol, forApply, [&](SignatureCheckRef const&) { return checker.checkFinal(); },
       [&] { return checker.allUsed(); });
+}
+
+TxSigResult checkFeeBumpSignaturesDecidedRefs(FeeBumpSigInfo const& tx, AccountSnapshot const& accounts,
+                                              uint32_t protocol, SignatureBatchPrefetch const& pre, size_t outerBody,
+                                              size_t innerBody, bool forApply) {
+  TxSigResult r;
+  if (protocol < 13) {
+    r.code = txNOT_SUPPORTED;
+    return r;
+  }
+  DecidedChecker checker(protocol, tx.signatures, pre, outerBody);
+  if (!find(accounts, tx.feeSource)) {
+    r.code = txNO_ACCOUNT;
+    return r;
+  }
+  if (!checker.checkFinal()) {
+    r.code = txBAD_AUTH;
+    return r;
+  }
+  if (!checker.allUsed()) {
+    r.code = txBAD_AUTH_EXTRA;
+    return r;
+  }
+  TxSigResult inner = checkTransactionSignaturesDecidedRefs(tx.inner, accounts, protocol, pre, innerBody, forApply);
+  r.code = inner.code == txSUCCESS ? txFEE_BUMP_INNER_SUCCESS : txFEE_BUMP_INNER_FAILED;
+  r.innerCode = inner.code;
+  r.failedOp = inner.failedOp;
+  r.opCode = inner.opCode;
+  return r;
 }
 
 TxSigResult checkFeeBumpSignaturesDecided(FeeBumpSigInfo const& tx, AccountSnapshot const& accounts,

@@ -123,6 +123,17 @@ std::vector<SignatureCheck> listTransactionChecks(TransactionSigInfo const& tx, 
 // (none without the account).
 std::vector<SignatureCheck> listFeeBumpOuterChecks(FeeBumpSigInfo const& tx, AccountSnapshot const& accounts);
 
+// The same two lists as references (SignatureChecker.h SignatureCheckRef): each entry points at the account
+// entry's own key, thresholds and signer list in `accounts` (or at the transaction's extra signers, or at the key
+// of a missing operation source) and names the threshold level.  No std::vector<Signer> is built
+// (signerListsBuilt() does not move); `accounts` and `tx` must outlive the list.
+std::vector<SignatureCheckRef> listTransactionCheckRefs(TransactionSigInfo const& tx, AccountSnapshot const& accounts,
+                                                        uint32_t protocol, bool forApply = false);
+std::vector<SignatureCheckRef> listFeeBumpOuterCheckRefs(FeeBumpSigInfo const& tx, AccountSnapshot const& accounts);
+// std::vector<Signer> copies of signer lists this module has built since the process started (the lists above
+// build none; every other path builds one per check)
+uint64_t signerListsBuilt();
+
 // The two check functions over decisions instead of a SignatureChecker: `pre`
 // is a prefetch whose runDecided has run, `body` / `outerBody` / `innerBody`
 // the addDecided indices of the transaction's bodies, added with the lists
@@ -139,6 +150,15 @@ TxSigResult checkTransactionSignaturesDecided(TransactionSigInfo const& tx, Acco
 TxSigResult checkFeeBumpSignaturesDecided(FeeBumpSigInfo const& tx, AccountSnapshot const& accounts,
                                           uint32_t protocol, SignatureBatchPrefetch const& pre, size_t outerBody,
                                           size_t innerBody, bool forApply = false);
+
+// ... and over the decisions of a prefetch filled with addDecidedRefs (runDecidedRefs has run): every decision is
+// final, so only the decisions are read -- no signer list is rebuilt.
+TxSigResult checkTransactionSignaturesDecidedRefs(TransactionSigInfo const& tx, AccountSnapshot const& accounts,
+                                                  uint32_t protocol, SignatureBatchPrefetch const& pre, size_t body,
+                                                  bool forApply = false);
+TxSigResult checkFeeBumpSignaturesDecidedRefs(FeeBumpSigInfo const& tx, AccountSnapshot const& accounts,
+                                              uint32_t protocol, SignatureBatchPrefetch const& pre, size_t outerBody,
+                                              size_t innerBody, bool forApply = false);
 
 // Adds every (signature, signer) pair the checks of `tx` can reach.  With a
 // body (SignatureBatchPrefetch's body form) the contents hash is not read: it

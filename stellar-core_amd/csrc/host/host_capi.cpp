@@ -443,6 +443,8 @@ int svh_check_txset(const svh_tx* txs, size_t ntx, const svh_decorated_sig* sigs
   }
 }
 
+uint64_t svh_signer_lists_built(void) { return stellar::signerListsBuilt(); }
+
 void svh_txset_last_phases(double out[4]) { std::memcpy(out, t_txset_phases, sizeof t_txset_phases); }
 
 }  // extern "C"
@@ -478,9 +480,9 @@ int checkEnvelopes(const svh_envelope* env, size_t n, const svh_decorated_sig* s
                    const EnvelopeBodies* eb) {
   try {
     if (eb) {
-      if (prefetch != 0 && prefetch != 1 && prefetch != 3 && prefetch != 5 && prefetch != 6)
+      if (prefetch != 0 && prefetch != 1 && prefetch != 3 && prefetch != 5 && prefetch != 6 && prefetch != 7)
         throw std::invalid_argument(
-            "svh_check_envelopes_bodies: prefetch must be 0, 1, 3, 5 or 6 (no keyed, cache-seeding form)");
+            "svh_check_envelopes_bodies: prefetch must be 0, 1, 3, 5, 6 or 7 (no keyed, cache-seeding form)");
       if (!eb->networkID || !eb->contentsHashOut || !eb->feeBumpHashOut || (n && !eb->body))
         throw std::invalid_argument("svh_check_envelopes_bodies: null argument");
       for (size_t t = 0; t < n; ++t) {
@@ -539,7 +541,42 @@ int checkEnvelopes(const svh_envelope* env, size_t n, const svh_decorated_sig* s
     constexpr size_t kPlain = ~size_t(0);
     std::vector<size_t> innerBody, outerBody;
     bool decidedRun = false;
-    if ((prefetch == 5 || prefetch == 6) && eb) {
+    bool decidedRefs = false;
+    if (prefetch == 7 && eb) {
+      // prefetch 7: the checks go to the engine as references to the snapshot's accounts (addDecidedRefs: every
+      // account once in the prefetch's table, no signer list copied), ONE sv_ed25519_check_txbodies_accounts call,
+      // every decision final; an envelope beyond the limits is checked by a plain SignatureChecker as in prefetch 5
+      auto at = [&](uint64_t off) { return eb->blob ? eb->blob + off : nullptr; };
+      innerBody.assign(n, kPlain);
+      outerBody.assign(n, kPlain);
+      size_t nbodies = 0;
+      const std::vector<SignatureCheckRef> none;
+      for (size_t t = 0; t < n; ++t) {
+        svh_envelope_body const& b = eb->body[t];
+        const bool bump = env[t].fee_bump != 0;
+        bool taken = protocol != 7;
+        if (taken && bump) {
+          const SignatureBatchPrefetch::TxBody outer{b.outer_off, b.outer_len, 2, &txs[t].contentsHash};
+          taken = pre.addDecidedRefs(outer, txs[t].signatures,
+                                     protocol >= 13 ? listFeeBumpOuterCheckRefs(txs[t], snap) : none);
+          if (taken) outerBody[t] = nbodies++;
+        }
+        if (taken) {
+          const SignatureBatchPrefetch::TxBody inner{b.off, b.len, (uint8_t)b.kind, &txs[t].inner.contentsHash};
+          taken = pre.addDecidedRefs(
+              inner, txs[t].inner.signatures,
+              !bump || protocol >= 13 ? listTransactionCheckRefs(txs[t].inner, snap, protocol, for_apply != 0) : none);
+          if (taken) innerBody[t] = nbodies++;
+        }
+        if (!taken) {
+          innerBody[t] = kPlain;
+          txs[t].inner.contentsHash = hostContentsHash(eb->networkID, b.kind, at(b.off), b.len);
+          if (bump) txs[t].contentsHash = hostContentsHash(eb->networkID, 2, at(b.outer_off), b.outer_len);
+        }
+      }
+      pre.runDecidedRefs(eb->networkID, eb->blob, protocol);
+      decidedRun = decidedRefs = true;
+    } else if ((prefetch == 5 || prefetch == 6) && eb) {
       auto at = [&](uint64_t off) { return eb->blob ? eb->blob + off : nullptr; };
       innerBody.assign(n, kPlain);
       outerBody.assign(n, kPlain);
@@ -605,7 +642,13 @@ int checkEnvelopes(const svh_envelope* env, size_t n, const svh_decorated_sig* s
     auto check = [&](size_t a, size_t b) {
       for (size_t t = a; t < b; ++t) {
         TxSigResult r;
-        if (decidedRun && innerBody[t] != kPlain)
+        if (decidedRefs && innerBody[t] != kPlain)
+          r = env[t].fee_bump
+                  ? checkFeeBumpSignaturesDecidedRefs(txs[t], snap, protocol, pre, outerBody[t], innerBody[t],
+                                                      for_apply != 0)
+                  : checkTransactionSignaturesDecidedRefs(txs[t].inner, snap, protocol, pre, innerBody[t],
+                                                          for_apply != 0);
+        else if (decidedRun && innerBody[t] != kPlain)
           r = env[t].fee_bump ? checkFeeBumpSignaturesDecided(txs[t], snap, protocol, pre, outerBody[t], innerBody[t],
                                                               for_apply != 0)
                               : checkTransactionSignaturesDecided(txs[t].inner, snap, protocol, pre, innerBody[t],

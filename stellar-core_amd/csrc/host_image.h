@@ -442,7 +442,7 @@ inline void pair_pack(const HintIn& in, const PairChunk& c, uint8_t* h) {
   }
   for (size_t i = 0; i <= k; ++i) {
     sb[i] = in.sb[c.b0 + i] - c.s0;
-    kb[i] = in.kb[c.b0 + i] - c.k0;
+    kb[i] = in.kb ? in.kb[c.b0 + i] - c.k0 : 0;  // (no key CSR array: a by-account chunk, its keys made on the device)
   }
   std::memcpy(h + c.o_len, in.len + c.b0, 4 * k);
   std::memcpy(h + c.o_kind, in.kind + c.b0, k);
@@ -538,8 +538,8 @@ inline PairChunk pair_chunk(const HintIn& in, size_t b0, size_t b1, size_t body_
   c.b1 = b1;
   c.s0 = (size_t)in.sb[b0];
   c.s1 = (size_t)in.sb[b1];
-  c.k0 = (size_t)in.kb[b0];
-  c.k1 = (size_t)in.kb[b1];
+  c.k0 = in.kb ? (size_t)in.kb[b0] : 0;
+  c.k1 = in.kb ? (size_t)in.kb[b1] : 0;
   c.body_bytes = body_bytes;
   const size_t m = c.s1 - c.s0, q = c.k1 - c.k0, k = b1 - b0;
   c.o_sig = 32 * q;
@@ -616,6 +616,126 @@ inline void check_pack(const CheckIn& in, const CheckChunk& c, uint8_t* h) {
         gk[i] = in.gkey[c.g0 + i] -
                 (uint32_t)(in.qb && in.gtype[c.g0 + i] == 3 /* ED25519_SIGNED_PAYLOAD */ ? q0 : c.p.k0);
       std::memcpy(h + c.o_gt + a, in.gtype + c.g0 + a, b - a);
+    }
+    a = m * p / parts, b = m * (p + 1) / parts;
+    if (in.sig_len && b > a) std::memcpy(h + c.o_sl + a, in.sig_len + c.p.s0 + a, b - a);
+  });
+}
+
+// sv_ed25519_check_txbodies_accounts: bodies and signatures as in the hinted
+// call, the keys and signer lists derived on the device from an account table
+// that goes up once (sv_txaccounts).  h.kb and h.key are null: a chunk's
+// hinted image has no key section (pair_chunk, pair_pack).
+struct AcctIn {
+  HintIn h;
+  const uint8_t* sig_len;  // per signature, or nullptr: all 64
+  const uint64_t* eb;      // account entries of body t: [eb[t], eb[t + 1])
+  const uint32_t* eacct;   // per entry
+  const uint64_t* cb;      // checks of body t
+  const uint32_t* cacct;   // per check: position inside the body's entries
+  const uint8_t* clevel;
+  const int32_t* cneed;    // may be null (no level-0 check)
+  const uint32_t* acnt;    // per account, made once: rows it adds to a key list [2a], payload candidates [2a + 1]
+};
+
+// The rows body t expands to: key rows, payload candidates, signers of its checks.
+inline void acct_body_rows(const AcctIn& in, size_t t, size_t* nk, size_t* nq, size_t* ng) {
+  size_t k = 0, q = 0, g = 0;
+  const uint64_t e0 = in.eb[t];
+  for (uint64_t e = e0; e < in.eb[t + 1]; ++e) {
+    k += in.acnt[2 * (size_t)in.eacct[e]];
+    q += in.acnt[2 * (size_t)in.eacct[e] + 1];
+  }
+  for (uint64_t c = in.cb[t]; c < in.cb[t + 1]; ++c) {
+    const size_t a = in.eacct[e0 + in.cacct[c]];
+    g += in.acnt[2 * a] + in.acnt[2 * a + 1];
+  }
+  *nk = k;
+  *nq = q;
+  *ng = g;
+}
+
+// One staging chunk of it: the hinted image of bodies [b0, b1) without keys
+// (PairChunk p), followed, 16-byte aligned, by the chunk's references (ne
+// account entries [e0, e1), nc checks [c0, c1), m signatures):
+//   bacct_begin (8 (k + 1)) | check_begin (8 (k + 1)) | bacct (4 ne) | check_acct (4 nc) | check_needed (4 nc) |
+//   check_level (nc) | sig_len (m, only with AcctIn::sig_len)
+// both CSR arrays relative to e0 / c0; bacct holds global account indices (the
+// table is on the device whole).  nk / nq / ng: the rows the chunk expands to.
+struct AcctChunk {
+  PairChunk p;
+  size_t e0, e1, c0, c1, nk, nq, ng;
+  size_t o_eb, o_cb, o_ea, o_ca, o_need, o_lvl, o_sl, bytes;
+};
+
+// The chunks of bodies [B0, B1): check_plan's bounds with the EXPANDED key,
+// payload-candidate and signer counts standing in for the explicit ones (a
+// body over a bound is a chunk alone).
+inline std::vector<AcctChunk> acct_plan(const AcctIn& in, size_t B0, size_t B1, size_t max_s, size_t max_k,
+                                        size_t max_b, size_t max_c, size_t max_g) {
+  std::vector<AcctChunk> out;
+  const HintIn& hi = in.h;
+  size_t t = B0;
+  size_t k1 = 0, q1 = 0, g1 = 0;  // body t's rows
+  if (t < B1) acct_body_rows(in, t, &k1, &q1, &g1);
+  while (t < B1) {
+    const size_t b0 = t, s0 = (size_t)hi.sb[t], c0 = (size_t)in.cb[t];
+    size_t bytes = 0, nk = 0, nq = 0, ng = 0;
+    do {
+      bytes += al16(hi.len[t]);
+      nk += k1;
+      nq += q1;
+      ng += g1;
+      ++t;
+      if (t < B1) acct_body_rows(in, t, &k1, &q1, &g1);
+    } while (t < B1 && hi.sb[t + 1] - s0 <= max_s && nk + k1 + nq + q1 <= max_k && in.cb[t + 1] - c0 <= max_c &&
+             ng + g1 <= max_g && bytes + al16(hi.len[t]) <= max_b);
+    AcctChunk c{};
+    c.p = pair_chunk(hi, b0, t, bytes);
+    c.e0 = (size_t)in.eb[b0];
+    c.e1 = (size_t)in.eb[t];
+    c.c0 = c0;
+    c.c1 = (size_t)in.cb[t];
+    c.nk = nk;
+    c.nq = nq;
+    c.ng = ng;
+    const size_t k = t - b0, ne = c.e1 - c.e0, nc = c.c1 - c.c0, m = c.p.s1 - c.p.s0;
+    c.o_eb = al16(c.p.bytes);
+    c.o_cb = c.o_eb + 8 * (k + 1);
+    c.o_ea = c.o_cb + 8 * (k + 1);
+    c.o_ca = c.o_ea + 4 * ne;
+    c.o_need = c.o_ca + 4 * nc;
+    c.o_lvl = c.o_need + 4 * nc;
+    c.o_sl = c.o_lvl + nc;
+    c.bytes = al16(c.o_sl + (in.sig_len ? m : 0) + 1);
+    out.push_back(c);
+  }
+  return out;
+}
+
+inline void acct_pack(const AcctIn& in, const AcctChunk& c, uint8_t* h) {
+  pair_pack(in.h, c.p, h);
+  const size_t k = c.p.b1 - c.p.b0, ne = c.e1 - c.e0, nc = c.c1 - c.c0, m = c.p.s1 - c.p.s0;
+  uint64_t* eb = (uint64_t*)(h + c.o_eb);
+  uint64_t* cb = (uint64_t*)(h + c.o_cb);
+  eb[k] = in.eb[c.p.b1] - c.e0;
+  cb[k] = in.cb[c.p.b1] - c.c0;
+  // the references in parts of the pack pool: rebased CSR words, plain copies of the rest
+  Pool& pp = pack_pool();
+  const size_t parts = pack_parts(pp.size(), t_pack_parts, 16 * k + 4 * ne + 9 * nc + m, pack_part());
+  pp.run(parts, [&](size_t p) {
+    for (size_t i = k * p / parts; i < k * (p + 1) / parts; ++i) {
+      eb[i] = in.eb[c.p.b0 + i] - c.e0;
+      cb[i] = in.cb[c.p.b0 + i] - c.c0;
+    }
+    size_t a = ne * p / parts, b = ne * (p + 1) / parts;
+    if (b > a) std::memcpy(h + c.o_ea + 4 * a, in.eacct + c.e0 + a, 4 * (b - a));
+    a = nc * p / parts, b = nc * (p + 1) / parts;
+    if (b > a) {
+      std::memcpy(h + c.o_ca + 4 * a, in.cacct + c.c0 + a, 4 * (b - a));
+      if (in.cneed) std::memcpy(h + c.o_need + 4 * a, in.cneed + c.c0 + a, 4 * (b - a));
+      else std::memset(h + c.o_need + 4 * a, 0, 4 * (b - a));
+      std::memcpy(h + c.o_lvl + a, in.clevel + c.c0 + a, b - a);
     }
     a = m * p / parts, b = m * (p + 1) / parts;
     if (in.sig_len && b > a) std::memcpy(h + c.o_sl + a, in.sig_len + c.p.s0 + a, b - a);

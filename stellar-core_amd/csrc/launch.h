@@ -40,6 +40,18 @@ int sv_txchecks_check(const uint8_t* network_id, const uint8_t* bodies, const ui
 struct sv_txchecks_payload;
 const struct sv_txchecks_payload* sv_txchecks_tables(const struct sv_txchecks* checks);
 
+// Argument check of the by-account check entry points (sv_cpu.cpp): the bodies and signatures as above, the
+// account table, the per-body account lists and the per-check references of `accts`, the limits on the EXPANDED
+// lists (64 signers per account, 2^32 rows) and the three outputs.  The per-account passes run once per account.
+// acnt (optional out): 2 x n_accounts words, the rows account a adds to a body's key list and to its payload
+// candidates (txacct.h sv_acct_count).
+struct sv_txaccounts;
+int sv_txaccounts_check(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                        const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                        const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig, size_t n_sigs,
+                        const struct sv_txaccounts* accts, const uint8_t* check_ok, const uint32_t* check_weight,
+                        const uint64_t* check_used, uint32_t* acnt);
+
 }  // extern "C"
 
 // The launchers take HIP types: compiled only where the HIP runtime headers
@@ -124,6 +136,23 @@ hipError_t sv_launch_txcheck_payload(const uint64_t* sig_begin, const void* hint
                                      const uint32_t* ppair_key, const void* ppair_verdict, uint64_t n_ppairs,
                                      const uint64_t* pkey_begin, uint64_t n_pkeys, uint8_t* check_ok,
                                      uint32_t* check_weight, uint64_t* check_used, hipStream_t s);
+// checks by account (sv_txacct.hip, txacct.h): the per-account counts and ranks into `tab_ws`
+// (sv_acct_tab_ws_bytes), once per table; then per call or chunk, on the same stream, count + scan + begin
+// (key_begin, pkey_begin, signer_begin, check_needed and the three totals at sv_acct_totals(ws, ...)) and the fill
+// of the rows O's nk / nq / ng say its arrays hold; `ws` holds sv_acct_ws_bytes(nb, ne, nc).  The structs are
+// host memory, their arrays device memory (key / skey / pay and O's key / pkey / ppay 16-byte aligned).
+struct sv_acct_tab;
+struct sv_acct_use;
+struct sv_acct_out;
+int sv_acct_block(void);
+size_t sv_acct_tab_ws_bytes(uint64_t na, uint64_t ns);
+size_t sv_acct_ws_bytes(uint64_t nb, uint64_t ne, uint64_t nc);
+const uint64_t* sv_acct_totals(const void* ws, uint64_t nb, uint64_t ne, uint64_t nc);
+hipError_t sv_launch_acct_table(const struct sv_acct_tab* T, void* tab_ws, hipStream_t s);
+hipError_t sv_launch_acct_count(const struct sv_acct_tab* T, const void* tab_ws, const struct sv_acct_use* U,
+                                const struct sv_acct_out* O, void* ws, hipStream_t s);
+hipError_t sv_launch_acct_fill(const struct sv_acct_tab* T, const void* tab_ws, const struct sv_acct_use* U,
+                               const struct sv_acct_out* O, void* ws, hipStream_t s);
 // warm-key latency path (sv_comb.hip)
 size_t sv_comb_btab_bytes(void);
 size_t sv_key_slot_bytes(void);

@@ -878,54 +878,20 @@ int sv_ed25519_check_txbodies(const uint8_t* network_id, const uint8_t* bodies, 
   });
 }
 
-int sv_ed25519_check_txbodies_device(int device, const uint8_t* network_id, const void* d_bodies,
-                                     const uint64_t* d_body_off, const uint32_t* d_body_len,
-                                     const uint8_t* d_body_kind, size_t n_bodies, const uint64_t* d_sig_begin,
-                                     const void* d_hint, const void* d_sig, size_t n_sigs,
-                                     const uint64_t* d_key_begin, const void* d_key, size_t n_keys,
-                                     const sv_txchecks* ck, void* d_check_ok, uint32_t* d_check_weight,
-                                     uint64_t* d_check_used, void* d_digests, void* stream) {
-  LifeGuard life_;
-  if (!network_id || !ck || ck->struct_size < sizeof(sv_txchecks) ||
-      (n_bodies && (!d_bodies || !d_body_off || !d_body_len || !d_body_kind || !d_sig_begin || !d_key_begin ||
-                    !ck->check_begin)) ||
-      (n_sigs && (!d_hint || !d_sig)) || (n_keys && !d_key) ||
-      (ck->n_checks && (n_bodies == 0 || !ck->check_needed || !ck->signer_begin || !d_check_ok || !d_check_weight ||
-                        !d_check_used)) ||
-      (ck->n_signers && (!ck->signer_type || !ck->signer_weight || !ck->signer_key)))
-    return fail(SV_ERR_INVALID_ARG, "tx checks: null pointer");
-  if (ck->protocol_version == 7) return fail(SV_ERR_INVALID_ARG, "tx checks: protocol 7 needs no engine");
-  if ((uint64_t)n_sigs >> 32 || (uint64_t)n_keys >> 32)
-    return fail(SV_ERR_INVALID_ARG, "tx checks: 2^32 or more signatures or keys");
-  // the payload tables: with no candidate the call is the one without them
-  PayloadDev pl;
-  const sv_txchecks_payload* pt = sv_txchecks_tables(ck);
-  if (pt && pt->n_pkeys) {
-    pl.qb = pt->pkey_begin;
-    if ((uint64_t)pt->n_pkeys >> 32 || !pt->pkey || !pt->pkey_payload || !pt->pkey_len)
-      return fail(SV_ERR_INVALID_ARG, "tx checks: null payload table, or 2^32 or more payload candidates");
-    if (!aligned16(pt->pkey) || !aligned16(pt->pkey_payload) || ((uintptr_t)pl.qb & 7u))
-      return fail(SV_ERR_ALIGN, "pkey/pkey_payload must be 16-byte aligned, pkey_begin naturally aligned");
-    pl.key = pt->pkey;
-    pl.payload = pt->pkey_payload;
-    pl.len = pt->pkey_len;
-    pl.nq = pt->n_pkeys;
-  }
-  if (!aligned16(d_sig) || !aligned16(d_key) || !aligned16(d_digests) || ((uintptr_t)d_hint & 3u) ||
-      ((uintptr_t)ck->check_begin & 7u) || ((uintptr_t)ck->signer_begin & 7u) || ((uintptr_t)ck->check_needed & 3u) ||
-      ((uintptr_t)ck->signer_weight & 3u) || ((uintptr_t)ck->signer_key & 3u) || ((uintptr_t)d_check_weight & 3u) ||
-      ((uintptr_t)d_check_used & 7u))
-    return fail(SV_ERR_ALIGN, "sig/key/digests must be 16-byte aligned, hint and the check arrays naturally aligned");
+}  // extern "C"
+
+namespace {
+// The device-resident check call on slot D (caller holds D.mu, device set, slot ready, arguments checked): `ck`'s
+// arrays and `pl` are device memory.  Shared by sv_ed25519_check_txbodies_device and the by-account form, which
+// runs it on the tables it expanded.
+int check_device_locked(Device& D, const uint8_t* network_id, const void* d_bodies, const uint64_t* d_body_off,
+                        const uint32_t* d_body_len, const uint8_t* d_body_kind, size_t n_bodies,
+                        const uint64_t* d_sig_begin, const void* d_hint, const void* d_sig, size_t n_sigs,
+                        const uint64_t* d_key_begin, const void* d_key, size_t n_keys, const sv_txchecks* ck,
+                        const PayloadDev& pl, void* d_check_ok, uint32_t* d_check_weight, uint64_t* d_check_used,
+                        void* d_digests, void* stream) {
   int rc;
-  if ((rc = debug_fail())) return rc;
-  Device* Dp;
-  if ((rc = slot_arg(device, Dp))) return rc;
-  Device& D = *Dp;
-  if (n_bodies == 0) return SV_OK;
   hipStream_t user = (hipStream_t)stream;
-  std::lock_guard<std::mutex> g(D.mu);
-  SV_HIP(hipSetDevice(D.phys));
-  if ((rc = ready_locked(D))) return rc;
   // the pairing workspace, pair_begin, a digest array when the caller wants
   // none, and the pinned word the count comes back in (growing drains the
   // kernel stream)
@@ -984,6 +950,204 @@ int sv_ed25519_check_txbodies_device(int device, const uint8_t* network_id, cons
   SV_HIP(hipEventRecord(D.dep_out, D.stream));
   SV_HIP(hipStreamWaitEvent(user, D.dep_out, 0));
   return SV_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sv_ed25519_check_txbodies_device(int device, const uint8_t* network_id, const void* d_bodies,
+                                     const uint64_t* d_body_off, const uint32_t* d_body_len,
+                                     const uint8_t* d_body_kind, size_t n_bodies, const uint64_t* d_sig_begin,
+                                     const void* d_hint, const void* d_sig, size_t n_sigs,
+                                     const uint64_t* d_key_begin, const void* d_key, size_t n_keys,
+                                     const sv_txchecks* ck, void* d_check_ok, uint32_t* d_check_weight,
+                                     uint64_t* d_check_used, void* d_digests, void* stream) {
+  LifeGuard life_;
+  if (!network_id || !ck || ck->struct_size < sizeof(sv_txchecks) ||
+      (n_bodies && (!d_bodies || !d_body_off || !d_body_len || !d_body_kind || !d_sig_begin || !d_key_begin ||
+                    !ck->check_begin)) ||
+      (n_sigs && (!d_hint || !d_sig)) || (n_keys && !d_key) ||
+      (ck->n_checks && (n_bodies == 0 || !ck->check_needed || !ck->signer_begin || !d_check_ok || !d_check_weight ||
+                        !d_check_used)) ||
+      (ck->n_signers && (!ck->signer_type || !ck->signer_weight || !ck->signer_key)))
+    return fail(SV_ERR_INVALID_ARG, "tx checks: null pointer");
+  if (ck->protocol_version == 7) return fail(SV_ERR_INVALID_ARG, "tx checks: protocol 7 needs no engine");
+  if ((uint64_t)n_sigs >> 32 || (uint64_t)n_keys >> 32)
+    return fail(SV_ERR_INVALID_ARG, "tx checks: 2^32 or more signatures or keys");
+  // the payload tables: with no candidate the call is the one without them
+  PayloadDev pl;
+  const sv_txchecks_payload* pt = sv_txchecks_tables(ck);
+  if (pt && pt->n_pkeys) {
+    pl.qb = pt->pkey_begin;
+    if ((uint64_t)pt->n_pkeys >> 32 || !pt->pkey || !pt->pkey_payload || !pt->pkey_len)
+      return fail(SV_ERR_INVALID_ARG, "tx checks: null payload table, or 2^32 or more payload candidates");
+    if (!aligned16(pt->pkey) || !aligned16(pt->pkey_payload) || ((uintptr_t)pl.qb & 7u))
+      return fail(SV_ERR_ALIGN, "pkey/pkey_payload must be 16-byte aligned, pkey_begin naturally aligned");
+    pl.key = pt->pkey;
+    pl.payload = pt->pkey_payload;
+    pl.len = pt->pkey_len;
+    pl.nq = pt->n_pkeys;
+  }
+  if (!aligned16(d_sig) || !aligned16(d_key) || !aligned16(d_digests) || ((uintptr_t)d_hint & 3u) ||
+      ((uintptr_t)ck->check_begin & 7u) || ((uintptr_t)ck->signer_begin & 7u) || ((uintptr_t)ck->check_needed & 3u) ||
+      ((uintptr_t)ck->signer_weight & 3u) || ((uintptr_t)ck->signer_key & 3u) || ((uintptr_t)d_check_weight & 3u) ||
+      ((uintptr_t)d_check_used & 7u))
+    return fail(SV_ERR_ALIGN, "sig/key/digests must be 16-byte aligned, hint and the check arrays naturally aligned");
+  int rc;
+  if ((rc = debug_fail())) return rc;
+  Device* Dp;
+  if ((rc = slot_arg(device, Dp))) return rc;
+  Device& D = *Dp;
+  if (n_bodies == 0) return SV_OK;
+  std::lock_guard<std::mutex> g(D.mu);
+  SV_HIP(hipSetDevice(D.phys));
+  if ((rc = ready_locked(D))) return rc;
+  return check_device_locked(D, network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin,
+                             d_hint, d_sig, n_sigs, d_key_begin, d_key, n_keys, ck, pl, d_check_ok, d_check_weight,
+                             d_check_used, d_digests, stream);
+}
+
+int sv_ed25519_check_txbodies_accounts(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                       const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                       const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig,
+                                       size_t n_sigs, const sv_txaccounts* A, uint8_t* check_ok,
+                                       uint32_t* check_weight, uint64_t* check_used, uint8_t* digests,
+                                       const sv_opts* opts) {
+  LifeGuard life_;
+  int rc = check_opts(opts);
+  if (rc) return rc;
+  // (the per-account row counts come out of the argument check: made once, used by every slot's planner)
+  std::vector<uint32_t> acnt(2);
+  if (A && A->struct_size >= sizeof(sv_txaccounts) && !((uint64_t)A->n_accounts >> 32)) {
+    try {
+      acnt.resize(2 * A->n_accounts + 2);
+    } catch (const std::bad_alloc&) {
+      return fail(SV_ERR_ALLOC, "tx checks by account: no memory for the per-account row counts");
+    }
+  }
+  if (sv_txaccounts_check(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, n_sigs, A,
+                          check_ok, check_weight, check_used, acnt.data()))
+    return fail(SV_ERR_INVALID_ARG,
+                "tx checks by account: null pointer, body kind > 2, malformed CSR array, bacct entry >= n_accounts, "
+                "check_acct outside its body, level > 3, signer type > 3, payload index >= n_apayloads, apayload_len "
+                "or sig_len > 64, more than 64 signatures in a body with checks or signers in an account's expanded "
+                "list, protocol 7, 2^32 or more rows, or a struct_size that is too small");
+  if (n_bodies == 0) return SV_OK;
+  if ((rc = debug_fail())) return rc;
+  if ((rc = ensure_init())) return rc;
+  std::vector<Device*> devs;
+  if ((rc = select_devices(opts, n_sigs, devs))) return rc;
+  const int path = path_from_flags(opts ? opts->flags : 0u);
+  const AcctIn in{{network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, nullptr, nullptr},
+                  A->sig_len,     A->bacct_begin,  A->bacct,   A->check_begin, A->check_acct,
+                  A->check_level, A->check_needed, acnt.data()};
+  const int clamp = A->protocol_version >= 10;
+  const CheckOut out{check_ok, check_weight, check_used, digests};
+  const size_t G = devs.size();
+  if (G == 1) return acct_slice(*devs[0], in, *A, 0, n_bodies, clamp, out, path);
+  // (slices of whole bodies as in sv_ed25519_check_txbodies; every slot takes the whole account table)
+  const std::vector<size_t> cut = pair_slices(sig_begin, n_bodies, G);
+  return shard(devs, G, [&](Device& D, size_t g, size_t) {
+    if (cut[g] == cut[g + 1]) return SV_OK;
+    return acct_slice(D, in, *A, cut[g], cut[g + 1], clamp, out, path);
+  });
+}
+
+int sv_ed25519_check_txbodies_accounts_device(int device, const uint8_t* network_id, const void* d_bodies,
+                                              const uint64_t* d_body_off, const uint32_t* d_body_len,
+                                              const uint8_t* d_body_kind, size_t n_bodies,
+                                              const uint64_t* d_sig_begin, const void* d_hint, const void* d_sig,
+                                              size_t n_sigs, const sv_txaccounts* A, void* d_check_ok,
+                                              uint32_t* d_check_weight, uint64_t* d_check_used, void* d_digests,
+                                              void* stream) {
+  LifeGuard life_;
+  if (!network_id || !A || A->struct_size < sizeof(sv_txaccounts))
+    return fail(SV_ERR_INVALID_ARG, "tx checks by account: null pointer or a struct_size that is too small");
+  const size_t na = A->n_accounts, ns = A->n_asigners, np = A->n_apayloads, ne = A->n_bacct, nc = A->n_checks;
+  if ((n_bodies && (!d_bodies || !d_body_off || !d_body_len || !d_body_kind || !d_sig_begin || !A->bacct_begin ||
+                    !A->check_begin)) ||
+      (n_sigs && (!d_hint || !d_sig)) || (na && (!A->acct_key || !A->acct_thresholds || !A->asigner_begin)) ||
+      (ns && (!A->asigner_type || !A->asigner_weight || !A->asigner_key)) ||
+      (np && (!A->apayload || !A->apayload_len)) || (ne && !A->bacct) ||
+      (nc && (n_bodies == 0 || !A->check_acct || !A->check_level || !d_check_ok || !d_check_weight || !d_check_used)))
+    return fail(SV_ERR_INVALID_ARG, "tx checks by account: null pointer");
+  if (A->protocol_version == 7) return fail(SV_ERR_INVALID_ARG, "tx checks by account: protocol 7 needs no engine");
+  if ((uint64_t)n_sigs >> 32 || (uint64_t)na >> 32 || (uint64_t)ns >> 32 || (uint64_t)np >> 32 ||
+      (uint64_t)ne >> 32 || (uint64_t)nc >> 32)
+    return fail(SV_ERR_INVALID_ARG, "tx checks by account: 2^32 or more rows");
+  if (!aligned16(d_sig) || !aligned16(d_digests) || !aligned16(A->acct_key) || !aligned16(A->asigner_key) ||
+      !aligned16(A->apayload) || ((uintptr_t)d_hint & 3u) || ((uintptr_t)A->asigner_begin & 7u) ||
+      ((uintptr_t)A->bacct_begin & 7u) || ((uintptr_t)A->check_begin & 7u) || ((uintptr_t)A->asigner_weight & 3u) ||
+      ((uintptr_t)A->asigner_payload & 3u) || ((uintptr_t)A->bacct & 3u) || ((uintptr_t)A->check_acct & 3u) ||
+      ((uintptr_t)A->check_needed & 3u) || ((uintptr_t)d_check_weight & 3u) || ((uintptr_t)d_check_used & 7u))
+    return fail(SV_ERR_ALIGN,
+                "sig/digests/acct_key/asigner_key/apayload must be 16-byte aligned, the other arrays naturally aligned");
+  int rc;
+  if ((rc = debug_fail())) return rc;
+  Device* Dp;
+  if ((rc = slot_arg(device, Dp))) return rc;
+  Device& D = *Dp;
+  if (n_bodies == 0) return SV_OK;
+  hipStream_t user = (hipStream_t)stream;
+  std::lock_guard<std::mutex> g(D.mu);
+  SV_HIP(hipSetDevice(D.phys));
+  if ((rc = ready_locked(D))) return rc;
+  const sv_acct_tab T{A->acct_key,       A->acct_thresholds, A->asigner_begin,   A->asigner_type,
+                      A->asigner_weight, A->asigner_key,     A->asigner_payload, A->apayload,
+                      A->apayload_len,   na,                 ns,                 np};
+  const sv_acct_use U{A->bacct_begin, A->bacct,        A->check_begin, A->check_acct,
+                      A->check_level, A->check_needed, n_bodies,       ne,           nc};
+  // the per-account counts and ranks, the expansion's workspace and its CSR arrays (growing drains the kernel
+  // stream), and the pinned words the totals come back in
+  const size_t tws = al16(sv_acct_tab_ws_bytes(na, ns));
+  const AcctBufs H = acct_layout(sv_acct_ws_bytes(n_bodies, ne, nc), n_bodies, nc, true, 0, 0, 0);
+  if (tws + H.head > D.txaws.cap) {
+    SV_HIP(hipStreamSynchronize(D.stream));
+    if ((rc = D.txaws.ensure(tws + H.head))) return rc;
+  }
+  if ((rc = D.h_txcnt.ensure(64))) return rc;
+  uint8_t* tab_ws = (uint8_t*)D.txaws.p;
+  uint8_t* head = tab_ws + tws;
+  SV_HIP(hipEventRecord(D.dep_in, user));
+  SV_HIP(hipStreamWaitEvent(D.stream, D.dep_in, 0));
+  sv_acct_out O = acct_out(H, head, nullptr, 0, 0, 0);
+  SV_HIP(sv_launch_acct_table(&T, tab_ws, D.stream));
+  SV_HIP(sv_launch_acct_count(&T, tab_ws, &U, &O, head, D.stream));
+  SV_HIP(hipMemcpyAsync(D.h_txcnt.p, sv_acct_totals(head, n_bodies, ne, nc), 24, hipMemcpyDeviceToHost, D.stream));
+  // the wait this form adds: the expansion's three row counts are only known on the device
+  SV_HIP(hipStreamSynchronize(D.stream));
+  const uint64_t* tot = (const uint64_t*)D.h_txcnt.p;
+  if (tot[0] >> 32 || tot[1] >> 32 || tot[2] >> 32)
+    return fail(SV_ERR_INVALID_ARG, "tx checks by account: the expansion has 2^32 or more rows");
+  const size_t nk = (size_t)tot[0], nq = (size_t)tot[1], ng = (size_t)tot[2];
+  const AcctBufs L = acct_layout(sv_acct_ws_bytes(n_bodies, ne, nc), n_bodies, nc, true, nk, nq, ng);
+  if ((rc = D.txarows.ensure(L.bytes))) return rc;  // (the stream is idle)
+  O = acct_out(L, head, (uint8_t*)D.txarows.p, nk, nq, ng);
+  SV_HIP(sv_launch_acct_fill(&T, tab_ws, &U, &O, head, D.stream));
+  // the explicit call over the expansion
+  sv_txchecks_payload P{};
+  P.checks.struct_size = sizeof(sv_txchecks_payload);
+  P.checks.protocol_version = A->protocol_version;
+  P.checks.sig_len = A->sig_len;
+  P.checks.check_begin = A->check_begin;
+  P.checks.check_needed = O.check_needed;
+  P.checks.signer_begin = O.signer_begin;
+  P.checks.signer_type = O.gtype;
+  P.checks.signer_weight = O.gweight;
+  P.checks.signer_key = O.gkey;
+  P.checks.n_checks = nc;
+  P.checks.n_signers = ng;
+  PayloadDev pl;
+  if (nq) {
+    pl.qb = O.pkey_begin;
+    pl.key = O.pkey;
+    pl.payload = O.ppay;
+    pl.len = O.plen;
+    pl.nq = nq;
+  }
+  return check_device_locked(D, network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin,
+                             d_hint, d_sig, n_sigs, O.key_begin, O.key, nk, &P.checks, pl, d_check_ok, d_check_weight,
+                             d_check_used, d_digests, stream);
 }
 
 int sv_ed25519_verify_device(int device, const void* d_pk, const void* d_sig, const void* d_msg,
@@ -1230,6 +1394,7 @@ int sv_workspace_bytes(int device, size_t* bytes) {
   std::lock_guard<std::mutex> gl(Dp->lat.mu);
   std::lock_guard<std::mutex> g(Dp->mu);
   size_t b = Dp->ws.cap + Dp->txmsg.cap + Dp->txpk.cap + Dp->txsg.cap + Dp->txpair.cap + Dp->txchk.cap + Dp->txpp.cap;
+  b += Dp->txatab.cap + Dp->txaws.cap + Dp->txarows.cap;
   for (const LatCtx& c : Dp->lat.ctx) b += c.ws.cap + c.d_in.cap + c.d_out.cap + c.d_keys.cap;
   *bytes = b;
   return SV_OK;

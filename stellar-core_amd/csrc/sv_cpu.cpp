@@ -27,6 +27,7 @@
 #pragma GCC diagnostic ignored "-Wunused-function"
 #include "txhash.h"
 #include "txcheck.h"
+#include "txacct.h"
 #pragma GCC diagnostic pop
 
 #include <algorithm>
@@ -442,6 +443,199 @@ int sv_ed25519_check_txbodies_cpu(const uint8_t* network_id, const uint8_t* bodi
     }
   }
   return SV_OK;
+}
+
+// Argument check shared by the sv_ed25519_check_txbodies_accounts host-array
+// entry points (declared in launch.h): SV_OK or SV_ERR_INVALID_ARG.  The
+// account table is walked once per account; the per-body and per-check passes
+// read two words per use.
+int sv_txaccounts_check(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                        const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                        const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig, size_t n_sigs,
+                        const sv_txaccounts* A, const uint8_t* check_ok, const uint32_t* check_weight,
+                        const uint64_t* check_used, uint32_t* acnt) {
+  if (!network_id || !sig_begin || !A || A->struct_size < sizeof(sv_txaccounts)) return SV_ERR_INVALID_ARG;
+  if (n_bodies && (!body_off || !body_len || !body_kind)) return SV_ERR_INVALID_ARG;
+  const size_t na = A->n_accounts, ns = A->n_asigners, np = A->n_apayloads, ne = A->n_bacct, nc = A->n_checks;
+  if ((uint64_t)n_sigs >> 32 || (uint64_t)na >> 32 || (uint64_t)ns >> 32 || (uint64_t)np >> 32 ||
+      (uint64_t)ne >> 32 || (uint64_t)nc >> 32)
+    return SV_ERR_INVALID_ARG;
+  if (n_sigs && (!hint || !sig)) return SV_ERR_INVALID_ARG;
+  if (A->protocol_version == 7) return SV_ERR_INVALID_ARG;
+  if (!A->asigner_begin || !A->bacct_begin || !A->check_begin) return SV_ERR_INVALID_ARG;
+  if (na && (!A->acct_key || !A->acct_thresholds)) return SV_ERR_INVALID_ARG;
+  if (ns && (!A->asigner_type || !A->asigner_weight || !A->asigner_key)) return SV_ERR_INVALID_ARG;
+  if (np && (!A->apayload || !A->apayload_len)) return SV_ERR_INVALID_ARG;
+  if (ne && !A->bacct) return SV_ERR_INVALID_ARG;
+  if (nc && (!A->check_acct || !A->check_level || !check_ok || !check_weight || !check_used))
+    return SV_ERR_INVALID_ARG;
+  if (sig_begin[0] != 0 || sig_begin[n_bodies] != n_sigs) return SV_ERR_INVALID_ARG;
+  if (A->asigner_begin[0] != 0 || A->asigner_begin[na] != ns) return SV_ERR_INVALID_ARG;
+  if (A->bacct_begin[0] != 0 || A->bacct_begin[n_bodies] != ne) return SV_ERR_INVALID_ARG;
+  if (A->check_begin[0] != 0 || A->check_begin[n_bodies] != nc) return SV_ERR_INVALID_ARG;
+  // once per payload and per account: lengths, types, payload indices, the expanded list's length
+  for (size_t i = 0; i < np; ++i)
+    if (A->apayload_len[i] > 64) return SV_ERR_INVALID_ARG;
+  std::vector<uint32_t> own;
+  if (!acnt) {
+    own.resize(2 * na + 2);
+    acnt = own.data();
+  }
+  for (size_t a = 0; a < na; ++a) {
+    const uint64_t s0 = A->asigner_begin[a], s1 = A->asigner_begin[a + 1];
+    if (s1 < s0 || s1 > ns) return SV_ERR_INVALID_ARG;
+    uint32_t nk = A->acct_thresholds[4 * a] ? 1u : 0u, nq = 0;
+    if (nk + (s1 - s0) > SV_TXCHECK_MAX) return SV_ERR_INVALID_ARG;
+    for (uint64_t s = s0; s < s1; ++s) {
+      const uint8_t ty = A->asigner_type[s];
+      if (ty > 3) return SV_ERR_INVALID_ARG;
+      if (ty != 3) {
+        ++nk;
+        continue;
+      }
+      if (!A->asigner_payload || A->asigner_payload[s] >= np) return SV_ERR_INVALID_ARG;
+      ++nq;
+    }
+    acnt[2 * a] = nk;
+    acnt[2 * a + 1] = nq;
+  }
+  // per body: its CSR words, signature lengths, account entries and checks (linear in the uses: threaded over
+  // bodies like sv_txchecks_check); sums: the expanded rows
+  auto bodies_ok = [&](size_t t0, size_t t1, uint64_t* rows) {
+    uint64_t nk = 0, nq = 0, ng = 0;
+    for (size_t t = t0; t < t1; ++t) {
+      if (sig_begin[t + 1] < sig_begin[t] || sig_begin[t + 1] > n_sigs || body_kind[t] > 2) return false;
+      if (body_len[t] && !bodies) return false;
+      if (A->sig_len)
+        for (uint64_t i = sig_begin[t]; i < sig_begin[t + 1]; ++i)
+          if (A->sig_len[i] > 64) return false;
+      const uint64_t e0 = A->bacct_begin[t], e1 = A->bacct_begin[t + 1];
+      if (e1 < e0 || e1 > ne) return false;
+      for (uint64_t e = e0; e < e1; ++e) {
+        const uint32_t a = A->bacct[e];
+        if (a >= na) return false;
+        nk += acnt[2 * a];
+        nq += acnt[2 * a + 1];
+      }
+      const uint64_t c0 = A->check_begin[t], c1 = A->check_begin[t + 1];
+      if (c1 < c0 || c1 > nc) return false;
+      if (c1 > c0 && sig_begin[t + 1] - sig_begin[t] > SV_TXCHECK_MAX) return false;
+      for (uint64_t c = c0; c < c1; ++c) {
+        if (A->check_acct[c] >= e1 - e0 || A->check_level[c] > 3) return false;
+        if (A->check_level[c] == 0 && !A->check_needed) return false;
+        const uint32_t a = A->bacct[e0 + A->check_acct[c]];
+        ng += acnt[2 * a] + acnt[2 * a + 1];
+      }
+    }
+    rows[0] = nk;
+    rows[1] = nq;
+    rows[2] = ng;
+    return true;
+  };
+  const size_t T = std::max<size_t>(1, std::min<size_t>({(size_t)8, n_bodies / 16384,
+                                                         (size_t)std::max(1u, std::thread::hardware_concurrency())}));
+  std::vector<uint64_t> rows(3 * T, 0);
+  std::vector<uint8_t> good(T, 0);
+  {
+    std::vector<std::thread> th;
+    for (size_t i = 1; i < T; ++i)
+      th.emplace_back(
+          [&, i] { good[i] = bodies_ok(n_bodies * i / T, n_bodies * (i + 1) / T, &rows[3 * i]) ? 1 : 0; });
+    good[0] = bodies_ok(0, n_bodies / T, &rows[0]) ? 1 : 0;
+    for (auto& x : th) x.join();
+  }
+  uint64_t tot[3] = {0, 0, 0};
+  for (size_t i = 0; i < T; ++i) {
+    if (!good[i]) return SV_ERR_INVALID_ARG;
+    for (int j = 0; j < 3; ++j) tot[j] += rows[3 * i + j];
+  }
+  if (tot[0] >> 32 || tot[1] >> 32 || tot[2] >> 32) return SV_ERR_INVALID_ARG;
+  return SV_OK;
+}
+
+int sv_ed25519_check_txbodies_accounts_cpu(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                           const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                           const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig,
+                                           size_t n_sigs, const sv_txaccounts* A, uint8_t* check_ok,
+                                           uint32_t* check_weight, uint64_t* check_used, uint8_t* digests,
+                                           int threads) {
+  int rc = sv_txaccounts_check(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig,
+                               n_sigs, A, check_ok, check_weight, check_used, nullptr);
+  if (rc) return rc;
+  if (n_bodies == 0) return SV_OK;
+  // the expansion with the functions the device kernels run (txacct.h), in their order: per account, count + scan
+  // per body and per check, rows, signers
+  const sv_acct_tab T{A->acct_key,        A->acct_thresholds, A->asigner_begin, A->asigner_type,
+                      A->asigner_weight,  A->asigner_key,     A->asigner_payload, A->apayload,
+                      A->apayload_len,    A->n_accounts,      A->n_asigners,    A->n_apayloads};
+  const sv_acct_use U{A->bacct_begin, A->bacct,     A->check_begin, A->check_acct, A->check_level,
+                      A->check_needed, n_bodies,    A->n_bacct,     A->n_checks};
+  const size_t nb = n_bodies, nc = A->n_checks;
+  std::vector<uint32_t> acnt(2 * T.na + 2), rank(T.ns + 1), erow(2 * U.ne + 2);
+  for (uint64_t a = 0; a < T.na; ++a) sv_acct_count(T, a, acnt.data(), rank.data());
+  std::vector<uint64_t> kb(nb + 1), qb(nb + 1), gb(nc + 1);
+  std::vector<int32_t> need(nc + 1);
+  uint64_t nk = 0, nq = 0, ng = 0;
+  for (size_t t = 0; t < nb; ++t) {
+    uint32_t k, q;
+    sv_acct_body_count(T, U, acnt.data(), t, &k, &q);
+    kb[t] = nk;
+    qb[t] = nq;
+    nk += k;
+    nq += q;
+    for (uint64_t c = U.cbeg[t]; c < U.cbeg[t + 1]; ++c) {
+      gb[c] = ng;
+      ng += sv_acct_check_count(T, U, acnt.data(), t, c, &need[c]);
+    }
+  }
+  kb[nb] = nk;
+  qb[nb] = nq;
+  gb[nc] = ng;
+  std::vector<uint8_t> key(32 * nk + 32), qkey(32 * nq + 32), qpay(64 * nq + 64), qlen(nq + 1), gt(ng + 1);
+  std::vector<uint32_t> gw(ng + 1), gk(ng + 1);
+  const sv_acct_out O{kb.data(),   qb.data(),   gb.data(), need.data(), key.data(), qkey.data(), qpay.data(),
+                      qlen.data(), gt.data(),   gw.data(), gk.data(),   nk,         nq,          ng};
+  for (size_t t = 0; t < nb; ++t) {
+    uint64_t e0, e1, krow = kb[t], qrow = qb[t];
+    sv_acct_entries(U, t, &e0, &e1);
+    for (uint64_t e = e0; e < e1; ++e) {
+      erow[2 * e] = (uint32_t)krow;
+      erow[2 * e + 1] = (uint32_t)qrow;
+      const uint64_t a = U.eacct[e];
+      if (a >= T.na) continue;
+      const uint64_t n = (uint64_t)acnt[2 * a] + acnt[2 * a + 1];
+      for (uint64_t j = 0; j < n; ++j) sv_acct_fill_row(T, rank.data(), a, j, krow, qrow, O);
+      krow += acnt[2 * a];
+      qrow += acnt[2 * a + 1];
+    }
+    for (uint64_t c = U.cbeg[t]; c < U.cbeg[t + 1]; ++c) {
+      uint64_t e;
+      const uint64_t a = sv_acct_check_account(T, U, t, c, &e);
+      if (a >= T.na) continue;
+      for (uint64_t j = 0; j < gb[c + 1] - gb[c]; ++j)
+        sv_acct_fill_signer(T, rank.data(), a, j, erow[2 * e], erow[2 * e + 1], gb[c] + j, O);
+    }
+  }
+  sv_txchecks_payload P{};
+  P.checks.struct_size = sizeof(sv_txchecks_payload);
+  P.checks.protocol_version = A->protocol_version;
+  P.checks.sig_len = A->sig_len;
+  P.checks.check_begin = A->check_begin;
+  P.checks.check_needed = need.data();
+  P.checks.signer_begin = gb.data();
+  P.checks.signer_type = gt.data();
+  P.checks.signer_weight = gw.data();
+  P.checks.signer_key = gk.data();
+  P.checks.n_checks = nc;
+  P.checks.n_signers = ng;
+  P.pkey_begin = qb.data();
+  P.pkey = qkey.data();
+  P.pkey_payload = qpay.data();
+  P.pkey_len = qlen.data();
+  P.n_pkeys = nq;
+  return sv_ed25519_check_txbodies_cpu(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint,
+                                       sig, n_sigs, kb.data(), key.data(), nk, &P.checks, check_ok, check_weight,
+                                       check_used, digests, threads);
 }
 
 int sv_ed25519_verify_cpu(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, size_t msg_len) {
