@@ -146,6 +146,10 @@ void svh_txset_last_phases(double out[4]);
  * built since the process started (one per check on every path but the
  * reference lists of prefetch 7). */
 uint64_t svh_signer_lists_built(void);
+/* Transactions prefetch 8 of svh_check_envelopes_bodies did not answer from
+ * their bodies' result codes alone since the process started: the failing
+ * ones, each walked once.  A valid set does not move it. */
+uint64_t svh_decided_walks(void);
 
 /* ---- transaction-level checks (a13) ---- */
 typedef struct svh_account {
@@ -255,7 +259,17 @@ int svh_check_envelopes(const svh_envelope* env, size_t n, const svh_decorated_s
  *               sv_ed25519_check_txbodies_accounts_cpu (counted in
  *               svh_engine_stats.fallbacks).  Limits (64 signatures, 64 signers
  *               in an account's list with its master key, 64-byte payloads),
- *               protocol 7 and results as prefetch 5. */
+ *               protocol 7 and results as prefetch 5.
+ *   prefetch 8  prefetch 7's tables, but the engine also folds each body's
+ *               checks (sv_ed25519_decide_txbodies_accounts: every check carries
+ *               its role, a body listed for_apply below protocol 10 the
+ *               SKIP_UNUSED flag) and returns ONE byte per body plus the index
+ *               of its first failing check; no per-check output comes back.  A
+ *               transaction whose bodies are OK and whose listing met no missing
+ *               account is a success without being walked again; any other is
+ *               walked once with that one check false (svh_decided_walks counts
+ *               them).  Fallback (sv_ed25519_decide_txbodies_accounts_cpu),
+ *               limits, protocol 7 and results as prefetch 7. */
 typedef struct svh_envelope_body {
   uint64_t off;
   uint32_t len;

@@ -623,6 +623,113 @@ int sv_ed25519_check_txbodies_accounts_cpu(const uint8_t* network_id, const uint
                                            uint32_t* check_weight, uint64_t* check_used,
                                            uint8_t* digests /* optional */, int threads);
 
+/* ---- One signature result per transaction body -----------------------------
+ * A caller of the check calls above folds every body's checks once more: the
+ * result code comes from the first failing check, the used marks are ORed over
+ * the body's checks (TransactionFrame::processSignatures, commonValid,
+ * checkAllSignaturesUsed).  The decide calls make that fold on the device
+ * (csrc/txresult.h, csrc/sv_txresult.hip) behind the check kernel and return
+ * one byte per body -- and, on request, the ascending list of the bodies that
+ * are not OK, which for a valid set is empty.
+ *
+ * Body t has the checks check_begin[t] .. check_begin[t+1]-1 and
+ * ns = min(sig_begin[t+1] - sig_begin[t], 64) signatures.  With
+ *   fail   the body-local index of its first check, in list order, whose
+ *          check_ok != 1 (anything but 1 fails), or SV_TXRESULT_NONE
+ *   used   the OR of check_used over all of its checks
+ *   want   ns >= 64 ? ~0 : (1 << ns) - 1
+ * body_code[t] is SV_TXRESULT_BAD_AUTH if a check failed and check_role[fail]
+ * is SV_TXROLE_TX (the source account at LOW, the extra signers, a fee bump's
+ * fee source); SV_TXRESULT_OP_BAD_AUTH if its role is SV_TXROLE_OP (an
+ * operation's check: txFAILED with opBAD_AUTH); otherwise
+ * SV_TXRESULT_BAD_AUTH_EXTRA if (used & want) != want and body_flags[t] has
+ * SV_TXBODY_SKIP_UNUSED clear; otherwise SV_TXRESULT_OK.  body_fail[t] is
+ * `fail`.  A body without checks but with signatures is BAD_AUTH_EXTRA.
+ * SKIP_UNUSED is processSignatures below protocol 10, which returns before
+ * checkAllSignaturesUsed.  All checks are evaluated where the reference stops
+ * at the first failing one: checks are independent and only the first failure
+ * and the OR are read, so no result changes.  A fee bump's outer and inner
+ * body are two bodies here; combining the two bytes stays with the caller.
+ *
+ * Each entry point has the argument list of its check twin with
+ * `const sv_txresults*` in place of the three check outputs, and its results
+ * are by definition the fold above of what the twin returns on the same input;
+ * requested check_* outputs and the digests are byte-equal to the twin's.
+ *
+ * Host forms: everything the twin refuses, and before any device work
+ * (SV_ERR_INVALID_ARG) a role > 1, a flag bit other than bit 0, a null
+ * body_code, a struct_size that is too small, bad_body == NULL with
+ * bad_cap > 0.  A chunk carries its roles and flags; the result kernel follows
+ * the check kernel on the same stream; only body_code and the outputs that
+ * were asked for come back (the 13 bytes per check stay on the device unless
+ * requested).  bad_body holds global body indices and is built on the host
+ * from body_code after the last chunk; *n_bad is exact even above bad_cap.
+ * Device forms: everything `res` points to is device memory, n_bad included;
+ * the struct is host memory.  The call waits no more often than its twin.
+ * Nothing is validated: a role > 1 reads as OP, unknown flag bits are ignored,
+ * ranges are clamped, entries at or past bad_cap are never written.  check_ok
+ * and check_used that are not requested live in the slot's workspace.
+ * CPU forms: the twin's CPU path, then csrc/txresult.h. */
+#define SV_TXRESULT_OK 0
+#define SV_TXRESULT_BAD_AUTH 1
+#define SV_TXRESULT_OP_BAD_AUTH 2
+#define SV_TXRESULT_BAD_AUTH_EXTRA 3
+#define SV_TXRESULT_NONE 0xFFFFFFFFu
+#define SV_TXROLE_TX 0
+#define SV_TXROLE_OP 1
+#define SV_TXBODY_SKIP_UNUSED 1
+typedef struct sv_txresults {
+  uint32_t struct_size;        /* sizeof(sv_txresults) */
+  const uint8_t* check_role;   /* n_checks, SV_TXROLE_*; NULL: every check SV_TXROLE_TX */
+  const uint8_t* body_flags;   /* n_bodies; NULL: 0 */
+  uint8_t* body_code;          /* out, n_bodies, required */
+  uint32_t* body_fail;         /* out, n_bodies, optional */
+  uint8_t* check_ok;           /* out, optional each: NULL = not returned */
+  uint32_t* check_weight;
+  uint64_t* check_used;
+  uint32_t* bad_body;          /* out, optional: ascending failing bodies */
+  size_t bad_cap;
+  uint64_t* n_bad;             /* out, optional */
+} sv_txresults;
+int sv_ed25519_decide_txbodies(const uint8_t* network_id /* 32 B */, const uint8_t* bodies, const uint64_t* body_off,
+                               const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                               const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig, size_t n_sigs,
+                               const uint64_t* key_begin, const uint8_t* key, size_t n_keys, const sv_txchecks* checks,
+                               const sv_txresults* res, uint8_t* digests /* optional, n_bodies x 32 */,
+                               const sv_opts* opts);
+int sv_ed25519_decide_txbodies_device(int device, const uint8_t* network_id /* host, 32 B */, const void* d_bodies,
+                                      const uint64_t* d_body_off, const uint32_t* d_body_len,
+                                      const uint8_t* d_body_kind, size_t n_bodies, const uint64_t* d_sig_begin,
+                                      const void* d_hint, const void* d_sig, size_t n_sigs,
+                                      const uint64_t* d_key_begin, const void* d_key, size_t n_keys,
+                                      const sv_txchecks* checks /* host struct, device arrays */,
+                                      const sv_txresults* res /* host struct, device arrays */, void* d_digests,
+                                      void* stream);
+int sv_ed25519_decide_txbodies_cpu(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                   const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                   const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig, size_t n_sigs,
+                                   const uint64_t* key_begin, const uint8_t* key, size_t n_keys,
+                                   const sv_txchecks* checks, const sv_txresults* res,
+                                   uint8_t* digests /* optional */, int threads);
+int sv_ed25519_decide_txbodies_accounts(const uint8_t* network_id /* 32 B */, const uint8_t* bodies,
+                                        const uint64_t* body_off, const uint32_t* body_len, const uint8_t* body_kind,
+                                        size_t n_bodies, const uint64_t* sig_begin, const uint8_t* hint,
+                                        const uint8_t* sig, size_t n_sigs, const sv_txaccounts* accts,
+                                        const sv_txresults* res, uint8_t* digests /* optional, n_bodies x 32 */,
+                                        const sv_opts* opts);
+int sv_ed25519_decide_txbodies_accounts_device(int device, const uint8_t* network_id /* host, 32 B */,
+                                               const void* d_bodies, const uint64_t* d_body_off,
+                                               const uint32_t* d_body_len, const uint8_t* d_body_kind, size_t n_bodies,
+                                               const uint64_t* d_sig_begin, const void* d_hint, const void* d_sig,
+                                               size_t n_sigs, const sv_txaccounts* accts /* host struct, device arrays */,
+                                               const sv_txresults* res /* host struct, device arrays */,
+                                               void* d_digests, void* stream);
+int sv_ed25519_decide_txbodies_accounts_cpu(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                            const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                            const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig,
+                                            size_t n_sigs, const sv_txaccounts* accts, const sv_txresults* res,
+                                            uint8_t* digests /* optional */, int threads);
+
 /* ---- Warm-key latency path (csrc/comb.h, csrc/sv_comb.hip) ---------------
  * Each device slot keeps a bounded cache of per-public-key tables
  * ({0..8} * 16^j * (-A), 108 KiB per key) in HBM.  A latency-path host batch

@@ -15,6 +15,7 @@ name follows the repository layout contract; it is not a valid identifier).
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 from typing import Optional, Sequence
@@ -75,7 +76,16 @@ EXPORTED_SYMBOLS = (
     "sv_ed25519_check_txbodies", "sv_ed25519_check_txbodies_device", "sv_ed25519_check_txbodies_cpu",
     "sv_ed25519_check_txbodies_accounts", "sv_ed25519_check_txbodies_accounts_device",
     "sv_ed25519_check_txbodies_accounts_cpu",
+    "sv_ed25519_decide_txbodies", "sv_ed25519_decide_txbodies_device", "sv_ed25519_decide_txbodies_cpu",
+    "sv_ed25519_decide_txbodies_accounts", "sv_ed25519_decide_txbodies_accounts_device",
+    "sv_ed25519_decide_txbodies_accounts_cpu",
 )
+
+# per-body result codes, check roles and body flags of the decide entry points (include/stellar_sigverify.h)
+TXRESULT_OK, TXRESULT_BAD_AUTH, TXRESULT_OP_BAD_AUTH, TXRESULT_BAD_AUTH_EXTRA = 0, 1, 2, 3
+TXRESULT_NONE = 0xFFFFFFFF
+TXROLE_TX, TXROLE_OP = 0, 1
+TXBODY_SKIP_UNUSED = 1
 
 # signer key types of the check entry points (include/stellar_sigverify.h)
 SIGNER_ED25519, SIGNER_PRE_AUTH_TX, SIGNER_HASH_X, SIGNER_SIGNED_PAYLOAD = 0, 1, 2, 3
@@ -126,6 +136,13 @@ class sv_txaccounts(ctypes.Structure):
                     "asigner_key", "asigner_payload", "apayload", "apayload_len", "bacct_begin", "bacct",
                     "check_begin", "check_acct", "check_level", "check_needed")]
                 + [(f, ctypes.c_size_t) for f in ("n_accounts", "n_asigners", "n_apayloads", "n_bacct", "n_checks")])
+
+
+class sv_txresults(ctypes.Structure):
+    _fields_ = ([("struct_size", ctypes.c_uint32)]
+                + [(f, ctypes.c_void_p) for f in ("check_role", "body_flags", "body_code", "body_fail", "check_ok",
+                                                  "check_weight", "check_used", "bad_body")]
+                + [("bad_cap", ctypes.c_size_t), ("n_bad", ctypes.c_void_p)])
 
 
 class FeedStats(ctypes.Structure):
@@ -217,6 +234,19 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.sv_ed25519_check_txbodies_accounts.argtypes = by_acct + [vp]
     lib.sv_ed25519_check_txbodies_accounts_cpu.argtypes = by_acct + [ctypes.c_int]
     lib.sv_ed25519_check_txbodies_accounts_device.argtypes = [ctypes.c_int] + by_acct + [vp]
+    # the decide forms: const sv_txresults* in place of the three check outputs
+    resp = ctypes.POINTER(sv_txresults)
+    decided = checked[:-4] + [resp, vp]
+    lib.sv_ed25519_decide_txbodies.argtypes = decided + [vp]
+    lib.sv_ed25519_decide_txbodies_cpu.argtypes = decided + [ctypes.c_int]
+    lib.sv_ed25519_decide_txbodies_device.argtypes = [ctypes.c_int] + decided + [vp]
+    decided_acct = by_acct[:-4] + [resp, vp]
+    lib.sv_ed25519_decide_txbodies_accounts.argtypes = decided_acct + [vp]
+    lib.sv_ed25519_decide_txbodies_accounts_cpu.argtypes = decided_acct + [ctypes.c_int]
+    lib.sv_ed25519_decide_txbodies_accounts_device.argtypes = [ctypes.c_int] + decided_acct + [vp]
+    lib.sv_txresult_block.restype = ctypes.c_int
+    lib.sv_txresult_ws_bytes.argtypes = [ctypes.c_uint64]
+    lib.sv_txresult_ws_bytes.restype = sz
     _lib = lib
     return lib
 
@@ -560,6 +590,62 @@ def verify_txbodies_hinted_device(device: int, network_id, d_bodies: int, d_body
     return int(n_pairs.value)
 
 
+TxResults = collections.namedtuple(
+    "TxResults", "body_code body_fail bad_body n_bad check_ok check_weight check_used digests")
+
+
+def results_desc(check_role=0, body_flags=0, body_code=0, body_fail=0, check_ok=0, check_weight=0, check_used=0,
+                 bad_body=0, bad_cap=0, n_bad=0, struct_size=None):
+    """sv_txresults over raw addresses (host arrays' or device pointers; 0: NULL)."""
+    r = sv_txresults()
+    r.struct_size = ctypes.sizeof(sv_txresults) if struct_size is None else int(struct_size)
+    for name, v in (("check_role", check_role), ("body_flags", body_flags), ("body_code", body_code),
+                    ("body_fail", body_fail), ("check_ok", check_ok), ("check_weight", check_weight),
+                    ("check_used", check_used), ("bad_body", bad_body), ("n_bad", n_bad)):
+        setattr(r, name, v or None)
+    r.bad_cap = int(bad_cap)
+    return r
+
+
+def _checked_call(fn, head, nb, nc, last, results):
+    """The tail of a host check or decide call: head are the arguments up to the
+    table struct.  results None: a check call, (check_ok, check_weight,
+    check_used, digests).  Else a decide call: an sv_txresults over the caller's
+    own arrays (passed as is; returns the digests), or a dict of check_role,
+    body_flags, want_checks, want_fail, bad_cap (None: no list) -> TxResults."""
+    dig = np.zeros((nb, 32), np.uint8)
+    if results is None:
+        ok, weight, used = np.zeros(nc, np.uint8), np.zeros(nc, np.uint32), np.zeros(nc, np.uint64)
+        _check(fn(*head, _ptr(ok), _ptr(weight), _ptr(used), _ptr(dig), last))
+        return ok, weight, used, dig
+    if isinstance(results, sv_txresults):
+        _check(fn(*head, ctypes.byref(results), _ptr(dig), last))
+        return dig
+    a = lambda x: x.__array_interface__["data"][0] if x is not None else 0  # noqa: E731
+    role, flags = results.get("check_role"), results.get("body_flags")
+    if role is not None:
+        role = np.ascontiguousarray(np.asarray(role, dtype=np.uint8).reshape(-1))
+        if role.shape[0] != nc:
+            raise ValueError("check_role must hold one byte per check")
+    if flags is not None:
+        flags = np.ascontiguousarray(np.asarray(flags, dtype=np.uint8).reshape(-1))
+        if flags.shape[0] != nb:
+            raise ValueError("body_flags must hold one byte per body")
+    code = np.zeros(nb, np.uint8)
+    fail = np.zeros(nb, np.uint32) if results.get("want_fail", True) else None
+    ok = weight = used = None
+    if results.get("want_checks", False):
+        ok, weight, used = np.zeros(nc, np.uint8), np.zeros(nc, np.uint32), np.zeros(nc, np.uint64)
+    cap = results.get("bad_cap")
+    bad = np.zeros(int(cap), np.uint32) if cap is not None else None
+    n_bad = np.zeros(1, np.uint64)
+    r = results_desc(a(role), a(flags), a(code), a(fail), a(ok), a(weight), a(used),
+                     a(bad) if cap else 0, cap or 0, a(n_bad))
+    _check(fn(*head, ctypes.byref(r), _ptr(dig), last))
+    n = int(n_bad[0])
+    return TxResults(code, fail, bad[:min(n, int(cap))] if bad is not None else None, n, ok, weight, used, dig)
+
+
 def _checks_desc(protocol_version, sig_len, check_begin, check_needed, signer_begin, signer_type, signer_weight,
                  signer_key, n_checks, n_signers, payload=None):
     """sv_txchecks over raw addresses (host arrays' or device pointers).
@@ -580,7 +666,7 @@ def _checks_desc(protocol_version, sig_len, check_begin, check_needed, signer_be
 
 def _check_host(fn, last, network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, key_begin, key,
                 check_begin, check_needed, signer_begin, signer_type, signer_weight, signer_key, sig_len,
-                protocol_version, pkey_begin=None, pkey=None, pkey_payload=None, pkey_len=None):
+                protocol_version, pkey_begin=None, pkey=None, pkey_payload=None, pkey_len=None, results=None):
     nid, bodies, off, ln, kind, nb, sb, hint, sig, ns, kb, key, nk = _hinted_args(
         network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, key_begin, key)
     cb = _csr(check_begin, nb, "check_begin")
@@ -612,11 +698,9 @@ def _check_host(fn, last, network_id, bodies, body_off, body_len, body_kind, sig
         raise ValueError("payload tables need pkey_begin")
     ck = _checks_desc(protocol_version, a(sl) if sl is not None else 0, a(cb), a(need), a(gb), a(gt), a(gw), a(gk),
                       nc, ng, payload)
-    ok, weight, used = np.zeros(nc, np.uint8), np.zeros(nc, np.uint32), np.zeros(nc, np.uint64)
-    dig = np.zeros((nb, 32), np.uint8)
-    _check(fn(_ptr(nid), _ptr(bodies), _ptr(off), _ptr(ln), _ptr(kind), nb, _ptr(sb), _ptr(hint), _ptr(sig), ns,
-              _ptr(kb), _ptr(key), nk, ctypes.byref(ck), _ptr(ok), _ptr(weight), _ptr(used), _ptr(dig), last))
-    return ok, weight, used, dig
+    head = (_ptr(nid), _ptr(bodies), _ptr(off), _ptr(ln), _ptr(kind), nb, _ptr(sb), _ptr(hint), _ptr(sig), ns,
+            _ptr(kb), _ptr(key), nk, ctypes.byref(ck))
+    return _checked_call(fn, head, nb, nc, last, results)
 
 
 def check_txbodies(network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, key_begin, key,
@@ -700,7 +784,7 @@ def _accounts_desc(protocol_version, sig_len, acct_key, acct_thresholds, asigner
 def _accounts_host(fn, last, network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, acct_key,
                    acct_thresholds, asigner_begin, asigner_type, asigner_weight, asigner_key, asigner_payload,
                    apayload, apayload_len, bacct_begin, bacct, check_begin, check_acct, check_level, check_needed,
-                   sig_len, protocol_version):
+                   sig_len, protocol_version, results=None):
     nid = np.ascontiguousarray(np.frombuffer(bytes(network_id), np.uint8))
     if nid.size != 32:
         raise ValueError("network_id must be 32 bytes")
@@ -746,11 +830,9 @@ def _accounts_host(fn, last, network_id, bodies, body_off, body_len, body_kind, 
     ac = _accounts_desc(protocol_version, a(sl), a(ak), a(th), gb.__array_interface__["data"][0], a(gt), a(gw), a(gk),
                         a(gp), a(pay), a(pl), a(eb), a(ea), a(cb), a(ca), a(lv), a(need), na, ng, npay, ea.shape[0],
                         nc)
-    ok, weight, used = np.zeros(nc, np.uint8), np.zeros(nc, np.uint32), np.zeros(nc, np.uint64)
-    dig = np.zeros((nb, 32), np.uint8)
-    _check(fn(_ptr(nid), _ptr(bodies), _ptr(off), _ptr(ln), _ptr(kind), nb, _ptr(sb), _ptr(hint), _ptr(sig), ns,
-              ctypes.byref(ac), _ptr(ok), _ptr(weight), _ptr(used), _ptr(dig), last))
-    return ok, weight, used, dig
+    head = (_ptr(nid), _ptr(bodies), _ptr(off), _ptr(ln), _ptr(kind), nb, _ptr(sb), _ptr(hint), _ptr(sig), ns,
+            ctypes.byref(ac))
+    return _checked_call(fn, head, nb, nc, last, results)
 
 
 def check_txbodies_accounts(network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, acct_key,
@@ -814,6 +896,131 @@ def check_txbodies_accounts_device(device: int, network_id, d_bodies: int, d_bod
         device, _ptr(nid), d_bodies or None, d_body_off or None, d_body_len or None, d_body_kind or None, n_bodies,
         d_sig_begin or None, d_hint or None, d_sig or None, n_sigs, ctypes.byref(ac), d_check_ok or None,
         d_check_weight or None, d_check_used or None, d_digests or None, stream or None))
+
+
+def _results_spec(res, check_role, body_flags, want_checks, want_fail, bad_cap):
+    if res is not None:
+        return res
+    return {"check_role": check_role, "body_flags": body_flags, "want_checks": want_checks, "want_fail": want_fail,
+            "bad_cap": bad_cap}
+
+
+def decide_txbodies(network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, key_begin, key,
+                    check_begin, check_needed, signer_begin, signer_type, signer_weight, signer_key, check_role=None,
+                    body_flags=None, sig_len=None, protocol_version: int = 21, device: int = -1, max_devices: int = 0,
+                    path=None, pkey_begin=None, pkey=None, pkey_payload=None, pkey_len=None, want_checks=False,
+                    want_fail=True, bad_cap=None, res=None):
+    """One signature result per body (sv_ed25519_decide_txbodies): the inputs of
+    check_txbodies plus check_role (TXROLE_* per check; None: all TXROLE_TX) and
+    body_flags (TXBODY_SKIP_UNUSED per body; None: 0).  Returns TxResults:
+    body_code (TXRESULT_*), body_fail (the body-local index of the first failing
+    check, TXRESULT_NONE: none), with bad_cap the ascending failing bodies (at
+    most bad_cap of them) and their exact count n_bad, with want_checks the
+    three check arrays of check_txbodies, and the digests.  res: an
+    sv_txresults over the caller's own arrays (results_desc), passed as is; the
+    call then returns the digests."""
+    lib = load_library()
+    return _check_host(lib.sv_ed25519_decide_txbodies, _opts(device, max_devices, path), network_id, bodies, body_off,
+                       body_len, body_kind, sig_begin, hint, sig, key_begin, key, check_begin, check_needed,
+                       signer_begin, signer_type, signer_weight, signer_key, sig_len, protocol_version, pkey_begin,
+                       pkey, pkey_payload, pkey_len,
+                       results=_results_spec(res, check_role, body_flags, want_checks, want_fail, bad_cap))
+
+
+def decide_txbodies_cpu(network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, key_begin, key,
+                        check_begin, check_needed, signer_begin, signer_type, signer_weight, signer_key,
+                        check_role=None, body_flags=None, sig_len=None, protocol_version: int = 21, threads: int = 0,
+                        pkey_begin=None, pkey=None, pkey_payload=None, pkey_len=None, want_checks=False,
+                        want_fail=True, bad_cap=None, res=None):
+    """The same on the engine's CPU path (what a caller runs on an engine error)."""
+    lib = load_library()
+    return _check_host(lib.sv_ed25519_decide_txbodies_cpu, int(threads), network_id, bodies, body_off, body_len,
+                       body_kind, sig_begin, hint, sig, key_begin, key, check_begin, check_needed, signer_begin,
+                       signer_type, signer_weight, signer_key, sig_len, protocol_version, pkey_begin, pkey,
+                       pkey_payload, pkey_len,
+                       results=_results_spec(res, check_role, body_flags, want_checks, want_fail, bad_cap))
+
+
+def decide_txbodies_device(device: int, network_id, d_bodies: int, d_body_off: int, d_body_len: int, d_body_kind: int,
+                           n_bodies: int, d_sig_begin: int, d_hint: int, d_sig: int, n_sigs: int, d_key_begin: int,
+                           d_key: int, n_keys: int, d_check_begin: int, d_check_needed: int, n_checks: int,
+                           d_signer_begin: int, d_signer_type: int, d_signer_weight: int, d_signer_key: int,
+                           n_signers: int, res, d_sig_len: int = 0, protocol_version: int = 21, d_digests: int = 0,
+                           stream: int = 0, d_pkey_begin: int = 0, d_pkey: int = 0, d_pkey_payload: int = 0,
+                           d_pkey_len: int = 0, n_pkeys=None) -> None:
+    """Device-resident form (raw device pointers; network_id is 32 host bytes;
+    res: results_desc over device pointers, n_bad included).  Waits no more
+    often than check_txbodies_device; the results land in res's arrays."""
+    lib = load_library()
+    nid = np.ascontiguousarray(np.frombuffer(bytes(network_id), np.uint8))
+    if nid.size != 32:
+        raise ValueError("network_id must be 32 bytes")
+    ck = _checks_desc(protocol_version, d_sig_len, d_check_begin, d_check_needed, d_signer_begin, d_signer_type,
+                      d_signer_weight, d_signer_key, n_checks, n_signers,
+                      None if n_pkeys is None else (d_pkey_begin, d_pkey, d_pkey_payload, d_pkey_len, n_pkeys))
+    _check(lib.sv_ed25519_decide_txbodies_device(
+        device, _ptr(nid), d_bodies or None, d_body_off or None, d_body_len or None, d_body_kind or None, n_bodies,
+        d_sig_begin or None, d_hint or None, d_sig or None, n_sigs, d_key_begin or None, d_key or None, n_keys,
+        ctypes.byref(ck), ctypes.byref(res), d_digests or None, stream or None))
+
+
+def decide_txbodies_accounts(network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, acct_key,
+                             acct_thresholds, asigner_begin, asigner_type, asigner_weight, asigner_key,
+                             asigner_payload, apayload, apayload_len, bacct_begin, bacct, check_begin, check_acct,
+                             check_level, check_needed=None, check_role=None, body_flags=None, sig_len=None,
+                             protocol_version: int = 21, device: int = -1, max_devices: int = 0, path=None,
+                             want_checks=False, want_fail=True, bad_cap=None, res=None):
+    """One signature result per body against an account table
+    (sv_ed25519_decide_txbodies_accounts): the inputs of check_txbodies_accounts
+    plus check_role and body_flags; returns TxResults as decide_txbodies."""
+    lib = load_library()
+    return _accounts_host(lib.sv_ed25519_decide_txbodies_accounts, _opts(device, max_devices, path), network_id,
+                          bodies, body_off, body_len, body_kind, sig_begin, hint, sig, acct_key, acct_thresholds,
+                          asigner_begin, asigner_type, asigner_weight, asigner_key, asigner_payload, apayload,
+                          apayload_len, bacct_begin, bacct, check_begin, check_acct, check_level, check_needed,
+                          sig_len, protocol_version,
+                          results=_results_spec(res, check_role, body_flags, want_checks, want_fail, bad_cap))
+
+
+def decide_txbodies_accounts_cpu(network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, acct_key,
+                                 acct_thresholds, asigner_begin, asigner_type, asigner_weight, asigner_key,
+                                 asigner_payload, apayload, apayload_len, bacct_begin, bacct, check_begin, check_acct,
+                                 check_level, check_needed=None, check_role=None, body_flags=None, sig_len=None,
+                                 protocol_version: int = 21, threads: int = 0, want_checks=False, want_fail=True,
+                                 bad_cap=None, res=None):
+    """The same on the engine's CPU path (what a caller runs on an engine error)."""
+    lib = load_library()
+    return _accounts_host(lib.sv_ed25519_decide_txbodies_accounts_cpu, int(threads), network_id, bodies, body_off,
+                          body_len, body_kind, sig_begin, hint, sig, acct_key, acct_thresholds, asigner_begin,
+                          asigner_type, asigner_weight, asigner_key, asigner_payload, apayload, apayload_len,
+                          bacct_begin, bacct, check_begin, check_acct, check_level, check_needed, sig_len,
+                          protocol_version,
+                          results=_results_spec(res, check_role, body_flags, want_checks, want_fail, bad_cap))
+
+
+def decide_txbodies_accounts_device(device: int, network_id, d_bodies: int, d_body_off: int, d_body_len: int,
+                                    d_body_kind: int, n_bodies: int, d_sig_begin: int, d_hint: int, d_sig: int,
+                                    n_sigs: int, d_acct_key: int, d_acct_thresholds: int, d_asigner_begin: int,
+                                    d_asigner_type: int, d_asigner_weight: int, d_asigner_key: int,
+                                    d_asigner_payload: int, d_apayload: int, d_apayload_len: int, n_accounts: int,
+                                    n_asigners: int, n_apayloads: int, d_bacct_begin: int, d_bacct: int, n_bacct: int,
+                                    d_check_begin: int, d_check_acct: int, d_check_level: int, d_check_needed: int,
+                                    n_checks: int, res, d_sig_len: int = 0, protocol_version: int = 21,
+                                    d_digests: int = 0, stream: int = 0) -> None:
+    """Device-resident form (raw device pointers; res: results_desc over device
+    pointers).  Waits as often as check_txbodies_accounts_device."""
+    lib = load_library()
+    nid = np.ascontiguousarray(np.frombuffer(bytes(network_id), np.uint8))
+    if nid.size != 32:
+        raise ValueError("network_id must be 32 bytes")
+    ac = _accounts_desc(protocol_version, d_sig_len, d_acct_key, d_acct_thresholds, d_asigner_begin, d_asigner_type,
+                        d_asigner_weight, d_asigner_key, d_asigner_payload, d_apayload, d_apayload_len, d_bacct_begin,
+                        d_bacct, d_check_begin, d_check_acct, d_check_level, d_check_needed, n_accounts, n_asigners,
+                        n_apayloads, n_bacct, n_checks)
+    _check(lib.sv_ed25519_decide_txbodies_accounts_device(
+        device, _ptr(nid), d_bodies or None, d_body_off or None, d_body_len or None, d_body_kind or None, n_bodies,
+        d_sig_begin or None, d_hint or None, d_sig or None, n_sigs, ctypes.byref(ac), ctypes.byref(res),
+        d_digests or None, stream or None))
 
 
 def verify_gather(items, keys: bool = False, device: int = -1, max_devices: int = 0):

@@ -14,6 +14,7 @@
 #include "engine_state.h"
 #include "host_image.h"
 #include "txacct.h"
+#include "txresult.h"
 
 namespace sv {
 namespace {
@@ -844,15 +845,65 @@ inline int hinted_slice(Device& D, const HintIn& in, size_t B0, size_t B1, PairS
 
 // ------------------------------------------------- checks decided on the device
 // Where a slice's decisions go: the caller's arrays, indexed by global check.
+// What a decide call adds to a slice (txresult.h): the caller's roles and flags, indexed by global check and body,
+// and where the codes go, indexed by global body.  body_fail is body-local, so chunks and slots rebase nothing.
+struct ResultOut {
+  const uint8_t* role;   // optional
+  const uint8_t* flags;  // optional
+  uint8_t* code;
+  uint32_t* fail;        // optional
+};
 struct CheckOut {
-  uint8_t* ok;
+  uint8_t* ok;  // (a decide call: each of the three optional)
   uint32_t* weight;
   uint64_t* used;
   uint8_t* digests;  // optional
+  const ResultOut* res = nullptr;  // a decide call's; null: a check call, which launches and copies what it always did
 };
+// does the chunk's 13 bytes per check come back?
+inline bool check_arrays_wanted(const CheckOut& out) { return !out.res || out.ok || out.weight || out.used; }
+
+// A decide chunk's roles and flags behind its image (role: nc bytes | flags: k bytes, each only where the caller
+// has them), and its results behind the check arrays on the device: body_code (k) | body_fail (4 k) | the result
+// kernels' workspace.  Without `res` the image is `img` bytes and nothing else is laid out.
+struct ResultBufs {
+  size_t o_role, o_flag, img;  // the image
+  size_t o_code, o_fail, o_ws, dev;  // s.d_verdict
+};
+inline ResultBufs result_layout(const ResultOut* res, size_t img, size_t nc, size_t k, size_t dev) {
+  ResultBufs b;
+  b.o_role = b.o_flag = b.img = img;
+  b.o_code = b.o_fail = b.o_ws = b.dev = dev;
+  if (!res) return b;
+  b.o_role = al16(img);
+  b.o_flag = b.o_role + (res->role ? al16(nc) : 0);
+  b.img = b.o_flag + (res->flags ? al16(k) : 0);
+  b.o_code = al16(dev);
+  b.o_fail = b.o_code + al16(k);
+  b.o_ws = b.o_fail + al16(4 * k);
+  b.dev = b.o_ws + al16(sv_txresult_ws_bytes(k));
+  return b;
+}
+inline void result_pack(const ResultOut* res, const ResultBufs& b, size_t c0, size_t nc, size_t b0, size_t k,
+                        uint8_t* h) {
+  if (!res) return;
+  if (res->role && nc) std::memcpy(h + b.o_role, res->role + c0, nc);
+  if (res->flags && k) std::memcpy(h + b.o_flag, res->flags + b0, k);
+}
+// The result kernel behind the chunk's check kernel, on the same stream: d the chunk's image, dv its s.d_verdict
+// with the check arrays at o_res (used | weight | ok).
+inline int result_launch(const ResultOut* res, const ResultBufs& b, const uint8_t* d, uint8_t* dv, size_t o_res,
+                         const uint64_t* d_cb, const uint64_t* d_sb, size_t k, size_t nc, size_t m, hipStream_t st) {
+  const sv_txresult_in I{d_cb, d_sb, dv + o_res + 12 * nc, (const uint64_t*)(dv + o_res),
+                         res->role ? d + b.o_role : nullptr, res->flags ? d + b.o_flag : nullptr, k, nc, m};
+  SV_HIP(sv_launch_txresult(&I, dv + b.o_code, res->fail ? (uint32_t*)(dv + b.o_fail) : nullptr, dv + b.o_ws, nullptr, 0,
+                            nullptr, st));
+  return SV_OK;
+}
 
 // A chunk's results in its pinned slot: check_used (8 nc) | check_weight (4 nc)
-// | check_ok (nc, padded to 16) | digests (32 k).
+// | check_ok (nc, padded to 16) | digests (32 k) and, for a decide call,
+// | body_code (k, padded to 16) | body_fail (4 k, only where asked for).
 struct CheckPending {
   bool busy = false;
   CheckChunk c;
@@ -865,11 +916,16 @@ inline int check_drain(Stage& s, CheckPending& pd, const CheckOut& out) {
   const size_t nc = c.c1 - c.c0, k = c.p.b1 - c.p.b0;
   const uint8_t* h = (const uint8_t*)s.h_out.p;
   if (nc) {
-    std::memcpy(out.used + c.c0, h, 8 * nc);
-    std::memcpy(out.weight + c.c0, h + 8 * nc, 4 * nc);
-    std::memcpy(out.ok + c.c0, h + 12 * nc, nc);
+    if (out.used) std::memcpy(out.used + c.c0, h, 8 * nc);
+    if (out.weight) std::memcpy(out.weight + c.c0, h + 8 * nc, 4 * nc);
+    if (out.ok) std::memcpy(out.ok + c.c0, h + 12 * nc, nc);
   }
-  if (out.digests) std::memcpy(out.digests + 32 * c.p.b0, h + al16(13 * nc), 32 * k);
+  const size_t o_dig = al16(13 * nc);
+  if (out.digests) std::memcpy(out.digests + 32 * c.p.b0, h + o_dig, 32 * k);
+  if (out.res) {
+    std::memcpy(out.res->code + c.p.b0, h + o_dig + 32 * k, k);
+    if (out.res->fail) std::memcpy(out.res->fail + c.p.b0, h + o_dig + 32 * k + al16(k), 4 * k);
+  }
   return SV_OK;
 }
 
@@ -899,7 +955,8 @@ inline int check_slice_locked(Device& D, const CheckIn& in, size_t B0, size_t B1
     const PayloadChunk pc = payload_chunk(in, c);
     const size_t nc = c.c1 - c.c0, ng = c.g1 - c.g0, nq = pc.q1 - pc.q0;
     const size_t wsb = al16(sv_pair_ws_bytes(k)), pbb = al16(8 * (k + 1)), pwsb = al16(sv_ppair_ws_bytes(k));
-    if ((rc = s.h_in.ensure(pc.bytes)) || (rc = s.d_in.ensure(pc.bytes)) ||
+    const size_t img = result_layout(out.res, pc.bytes, nc, k, 0).img;
+    if ((rc = s.h_in.ensure(img)) || (rc = s.d_in.ensure(img)) ||
         (rc = s.d_pair.ensure(wsb + pbb + (nq ? pwsb + pbb : 0))) ||
         (rc = s.d_keys.ensure(32 * k)) || (rc = s.h_cnt.ensure(64)))
       return rc;
@@ -907,7 +964,8 @@ inline int check_slice_locked(Device& D, const CheckIn& in, size_t B0, size_t B1
     uint8_t* d = (uint8_t*)s.d_in.p;
     check_pack(in, c, hp);
     payload_pack(in, c, pc, hp);
-    if ((rc = upload_image(D, d, hp, pc.bytes, up_s))) return rc;
+    result_pack(out.res, result_layout(out.res, pc.bytes, nc, k, 0), c.c0, nc, c.p.b0, k, hp);
+    if ((rc = upload_image(D, d, hp, img, up_s))) return rc;
     const uint64_t* d_sb = (const uint64_t*)(d + c.p.o_sb);
     const uint64_t* d_kb = (const uint64_t*)(d + c.p.o_kb);
     uint64_t* d_pb = (uint64_t*)((uint8_t*)s.d_pair.p + wsb);
@@ -937,8 +995,9 @@ inline int check_slice_locked(Device& D, const CheckIn& in, size_t B0, size_t B1
     if (npp && (rc = ensure_txpp(D, ppair_layout(npp).bytes))) return rc;
     // verdicts (np, padded) | pair_sig, pair_key (4 np each, padded) | used | weight | ok
     const size_t o_idx = al16(np), o_res = o_idx + al16(8 * np), o_dig = al16(13 * nc);
-    if ((rc = ensure_txpairs(D, np)) || (rc = s.d_verdict.ensure(o_res + 13 * nc + 16)) ||
-        (rc = s.h_out.ensure(o_dig + 32 * k)))
+    const ResultBufs RB = result_layout(out.res, pc.bytes, nc, k, o_res + 13 * nc);
+    if ((rc = ensure_txpairs(D, np)) || (rc = s.d_verdict.ensure(RB.dev + 16)) ||
+        (rc = s.h_out.ensure(o_dig + 32 * k + (out.res ? al16(k) + 4 * k : 0))))
       return rc;
     uint8_t* dv = (uint8_t*)s.d_verdict.p;
     uint32_t* d_ps = (uint32_t*)(dv + o_idx);
@@ -958,13 +1017,19 @@ inline int check_slice_locked(Device& D, const CheckIn& in, size_t B0, size_t B1
         (const uint64_t*)(d + c.o_gb), d + c.o_gt, (const uint32_t*)(d + c.o_gw), (const uint32_t*)(d + c.o_gk), ng,
         clamp, d_ppb, (const uint32_t*)(dpp + L.o_idx), (const uint32_t*)(dpp + L.o_idx) + npp, dpp, npp, pl.qb, nq,
         dv + o_res + 12 * nc, (uint32_t*)(dv + o_res + 8 * nc), (uint64_t*)(dv + o_res), D.stream));
+    if (out.res &&
+        (rc = result_launch(out.res, RB, d, dv, o_res, (const uint64_t*)(d + c.o_cb), d_sb, k, nc, m, D.stream)))
+      return rc;
     if (!single) {
       SV_HIP(hipEventRecord(s.done, D.stream));
       SV_HIP(hipStreamWaitEvent(D.d2h, s.done, 0));
     }
     uint8_t* ho = (uint8_t*)s.h_out.p;
-    if (nc) SV_HIP(hipMemcpyAsync(ho, dv + o_res, 13 * nc, hipMemcpyDeviceToHost, down_s));
+    if (nc && check_arrays_wanted(out)) SV_HIP(hipMemcpyAsync(ho, dv + o_res, 13 * nc, hipMemcpyDeviceToHost, down_s));
     if (out.digests) SV_HIP(hipMemcpyAsync(ho + o_dig, s.d_keys.p, 32 * k, hipMemcpyDeviceToHost, down_s));
+    if (out.res)
+      SV_HIP(hipMemcpyAsync(ho + o_dig + 32 * k, dv + RB.o_code, al16(k) + (out.res->fail ? 4 * k : 0),
+                            hipMemcpyDeviceToHost, down_s));
     SV_HIP(hipEventRecord(s.down, down_s));
     pend[ci & 1].busy = true;
     pend[ci & 1].c = c;
@@ -1117,7 +1182,8 @@ inline int acct_slice_locked(Device& D, const AcctIn& in, const sv_txaccounts& A
     const size_t q = c.nk, nq = c.nq, ng = c.ng;
     const size_t wsb = al16(sv_pair_ws_bytes(k)), pbb = al16(8 * (k + 1)), pwsb = al16(sv_ppair_ws_bytes(k));
     const AcctBufs L = acct_layout(sv_acct_ws_bytes(k, ne, nc), k, nc, false, q, nq, ng);
-    if ((rc = s.h_in.ensure(c.bytes)) || (rc = s.d_in.ensure(c.bytes)) || (rc = s.d_acct.ensure(L.bytes)) ||
+    const size_t img = result_layout(out.res, c.bytes, nc, k, 0).img;
+    if ((rc = s.h_in.ensure(img)) || (rc = s.d_in.ensure(img)) || (rc = s.d_acct.ensure(L.bytes)) ||
         (rc = s.d_pair.ensure(wsb + pbb + (nq ? pwsb + pbb : 0))) || (rc = s.d_keys.ensure(32 * k)) ||
         (rc = s.h_cnt.ensure(64)))
       return rc;
@@ -1125,7 +1191,8 @@ inline int acct_slice_locked(Device& D, const AcctIn& in, const sv_txaccounts& A
     uint8_t* d = (uint8_t*)s.d_in.p;
     uint8_t* da = (uint8_t*)s.d_acct.p;
     acct_pack(in, c, hp);
-    if ((rc = upload_image(D, d, hp, c.bytes, up_s))) return rc;
+    result_pack(out.res, result_layout(out.res, c.bytes, nc, k, 0), c.c0, nc, c.p.b0, k, hp);
+    if ((rc = upload_image(D, d, hp, img, up_s))) return rc;
     const uint64_t* d_sb = (const uint64_t*)(d + c.p.o_sb);
     uint64_t* d_pb = (uint64_t*)((uint8_t*)s.d_pair.p + wsb);
     SV_HIP(sv_launch_txhash(D.grid * 8, in.h.nid, d + c.p.o_body, (const uint64_t*)(d + c.p.o_off),
@@ -1160,8 +1227,9 @@ inline int acct_slice_locked(Device& D, const AcctIn& in, const sv_txaccounts& A
     if (npp && (rc = ensure_txpp(D, ppair_layout(npp).bytes))) return rc;
     // verdicts (np, padded) | pair_sig, pair_key (4 np each, padded) | used | weight | ok
     const size_t o_idx = al16(np), o_res = o_idx + al16(8 * np), o_dig = al16(13 * nc);
-    if ((rc = ensure_txpairs(D, np)) || (rc = s.d_verdict.ensure(o_res + 13 * nc + 16)) ||
-        (rc = s.h_out.ensure(o_dig + 32 * k)))
+    const ResultBufs RB = result_layout(out.res, c.bytes, nc, k, o_res + 13 * nc);
+    if ((rc = ensure_txpairs(D, np)) || (rc = s.d_verdict.ensure(RB.dev + 16)) ||
+        (rc = s.h_out.ensure(o_dig + 32 * k + (out.res ? al16(k) + 4 * k : 0))))
       return rc;
     uint8_t* dv = (uint8_t*)s.d_verdict.p;
     uint32_t* d_ps = (uint32_t*)(dv + o_idx);
@@ -1180,13 +1248,19 @@ inline int acct_slice_locked(Device& D, const AcctIn& in, const sv_txaccounts& A
         dv, np, s.d_keys.p, (const uint64_t*)(d + c.o_cb), O.check_needed, nc, O.signer_begin, O.gtype, O.gweight,
         O.gkey, ng, clamp, d_ppb, (const uint32_t*)(dpp + PL.o_idx), (const uint32_t*)(dpp + PL.o_idx) + npp, dpp, npp,
         pl.qb, nq, dv + o_res + 12 * nc, (uint32_t*)(dv + o_res + 8 * nc), (uint64_t*)(dv + o_res), D.stream));
+    if (out.res &&
+        (rc = result_launch(out.res, RB, d, dv, o_res, (const uint64_t*)(d + c.o_cb), d_sb, k, nc, m, D.stream)))
+      return rc;
     if (!single) {
       SV_HIP(hipEventRecord(s.done, D.stream));
       SV_HIP(hipStreamWaitEvent(D.d2h, s.done, 0));
     }
     uint8_t* ho = (uint8_t*)s.h_out.p;
-    if (nc) SV_HIP(hipMemcpyAsync(ho, dv + o_res, 13 * nc, hipMemcpyDeviceToHost, down_s));
+    if (nc && check_arrays_wanted(out)) SV_HIP(hipMemcpyAsync(ho, dv + o_res, 13 * nc, hipMemcpyDeviceToHost, down_s));
     if (out.digests) SV_HIP(hipMemcpyAsync(ho + o_dig, s.d_keys.p, 32 * k, hipMemcpyDeviceToHost, down_s));
+    if (out.res)
+      SV_HIP(hipMemcpyAsync(ho + o_dig + 32 * k, dv + RB.o_code, al16(k) + (out.res->fail ? 4 * k : 0),
+                            hipMemcpyDeviceToHost, down_s));
     SV_HIP(hipEventRecord(s.down, down_s));
     pend[ci & 1].busy = true;
     pend[ci & 1].c.p = c.p;

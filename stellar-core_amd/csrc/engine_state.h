@@ -297,6 +297,7 @@ struct Device {
   // by-account check calls: the account table (host form: its image; both forms: the per-account counts and
   // ranks), and the device-resident form's expansion -- workspace and CSR arrays, then the rows sized from its totals
   DevBuf txatab, txaws, txarows;
+  DevBuf txres;  // device-resident decide calls: the check arrays the caller did not ask for, the result kernels' workspace
   KernelTimer timer;  // the bulk launches (launch_locked)
   LatLane lat;
   KeyTabs kt;  // (under mu)
@@ -414,7 +415,7 @@ inline void release_device(Device& D) {
   D.msg.release(); D.off.release(); D.len.release(); D.keys.release(); D.h_sha.release();
   D.txmsg.release();
   D.txpk.release(); D.txsg.release(); D.txpair.release(); D.h_txcnt.release(); D.txchk.release(); D.txpp.release();
-  D.txatab.release(); D.txaws.release(); D.txarows.release();
+  D.txatab.release(); D.txaws.release(); D.txarows.release(); D.txres.release();
   D.ws.release();
   D.kt.index.release(); D.kt.store.release(); D.kt.kslot.release(); D.kt.builders.release();
   D.kt.count.release(); D.kt.h_count.release();

@@ -1122,6 +1122,30 @@ void checkTxBodiesAccountsUncached(const uint8_t* networkID, const uint8_t* bodi
   gCpuSigs += nSigs;
 }
 
+void decideTxBodiesAccountsUncached(const uint8_t* networkID, const uint8_t* bodies, const uint64_t* bodyOff,
+                                    const uint32_t* bodyLen, const uint8_t* bodyKind, size_t nBodies,
+                                    const uint64_t* sigBegin, const uint8_t* hint, const uint8_t* sig, size_t nSigs,
+                                    const ::sv_txaccounts& accounts, const ::sv_txresults& results, uint8_t* digests) {
+  if (nBodies == 0) return;
+  const size_t work = std::max<size_t>(nSigs, 1);
+  int rc = timedBatch(true, work, [&] {
+    return sv_ed25519_decide_txbodies_accounts(networkID, bodies, bodyOff, bodyLen, bodyKind, nBodies, sigBegin, hint,
+                                               sig, nSigs, &accounts, &results, digests, nullptr);
+  });
+  if (rc == SV_OK) {
+    gGpuSigs += nSigs;
+    gGpuBatches += 1;
+    return;
+  }
+  ++gFallbacks;
+  rc = timedBatch(false, work, [&] {
+    return sv_ed25519_decide_txbodies_accounts_cpu(networkID, bodies, bodyOff, bodyLen, bodyKind, nBodies, sigBegin,
+                                                   hint, sig, nSigs, &accounts, &results, digests, 0);
+  });
+  if (rc != SV_OK) throw std::invalid_argument("decideTxBodiesAccountsUncached: malformed batch");
+  gCpuSigs += nSigs;
+}
+
 bool verifySig(PublicKey const& key, Signature const& signature, ByteSlice const& bin) {
   // the hit path as the reference runs it (SecretKey.cpp:446-456): key, one
   // lock, lookup, touch -- no batch bookkeeping; anything else (a miss, or an

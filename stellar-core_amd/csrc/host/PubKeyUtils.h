@@ -38,6 +38,7 @@
 
 struct sv_txchecks;  // include/stellar_sigverify.h
 struct sv_txaccounts;
+struct sv_txresults;
 
 namespace stellar {
 
@@ -191,6 +192,12 @@ void checkTxBodiesAccountsUncached(const uint8_t* networkID, const uint8_t* bodi
                                    const uint64_t* sigBegin, const uint8_t* hint, const uint8_t* sig, size_t nSigs,
                                    const ::sv_txaccounts& accounts, uint8_t* checkOk, uint32_t* checkWeight,
                                    uint64_t* checkUsed, uint8_t* digests);
+// ... and one result per body instead of the three arrays per check (sv_ed25519_decide_txbodies_accounts, on an
+// engine error its _cpu form: a fallback is counted, never a reject).  `results` says what comes back.
+void decideTxBodiesAccountsUncached(const uint8_t* networkID, const uint8_t* bodies, const uint64_t* bodyOff,
+                                    const uint32_t* bodyLen, const uint8_t* bodyKind, size_t nBodies,
+                                    const uint64_t* sigBegin, const uint8_t* hint, const uint8_t* sig, size_t nSigs,
+                                    const ::sv_txaccounts& accounts, const ::sv_txresults& results, uint8_t* digests);
 
 void clearVerifySigCache();
 void maybeSeedVerifySigCache(unsigned int seed);

@@ -571,7 +571,8 @@ uint32_t SignatureBatchPrefetch::appendAccount(uint256 const* id, uint8_t const*
 }
 
 bool SignatureBatchPrefetch::addDecidedRefs(TxBody const& body, std::vector<DecoratedSignature> const& signatures,
-                                            std::vector<SignatureCheckRef> const& checks) {
+                                            std::vector<SignatureCheckRef> const& checks, bool skipUnused,
+                                            bool listedOk) {
   if (signatures.size() > 64) return false;
   for (auto const& sig : signatures)
     if (sig.signature.size() > 64) return false;
@@ -620,30 +621,37 @@ bool SignatureBatchPrefetch::addDecidedRefs(TxBody const& body, std::vector<Deco
     a.cacct.push_back((uint32_t)(pos - e0));
     a.clevel.push_back(c.level);
     d.needed.push_back(c.needed);
+    d.role.push_back(c.role);
   }
+  d.bodyFlags.push_back(skipUnused ? SV_TXBODY_SKIP_UNUSED : 0);
+  d.listedOk.push_back(listedOk ? 1 : 0);
   d.sigBegin.push_back(d.sigLen.size());
   d.checkBegin.push_back(d.needed.size());
   a.bacctBegin.push_back(a.bacct.size());
   return true;
 }
 
-void SignatureBatchPrefetch::runDecidedRefs(const uint8_t* networkID, const uint8_t* blob, uint32_t protocolVersion) {
-  Decided& d = dec_;
-  Accounts& a = acct_;
-  const size_t nb = bodies_.size(), nc = d.needed.size();
-  d.ok.assign(nc, 0);
-  d.outWeight.assign(nc, 0);
-  d.used.assign(nc, 0);
-  if (nb == 0) return;
-  std::vector<uint64_t> off(nb);
-  std::vector<uint32_t> len(nb);
-  std::vector<uint8_t> kind(nb), digests(32 * nb);
-  for (size_t b = 0; b < nb; ++b) {
-    off[b] = bodies_[b].body.off;
-    len[b] = bodies_[b].body.len;
-    kind[b] = bodies_[b].body.kind;
-  }
+struct SignatureBatchPrefetch::AccountsCall {
+  std::vector<uint64_t> off;
+  std::vector<uint32_t> len;
+  std::vector<uint8_t> kind, digests;
   sv_txaccounts A{};
+};
+
+void SignatureBatchPrefetch::fillAccountsCall(AccountsCall& c, uint32_t protocolVersion) const {
+  Decided const& d = dec_;
+  Accounts const& a = acct_;
+  const size_t nb = bodies_.size(), nc = d.needed.size();
+  c.off.resize(nb);
+  c.len.resize(nb);
+  c.kind.resize(nb);
+  c.digests.resize(32 * nb);
+  for (size_t b = 0; b < nb; ++b) {
+    c.off[b] = bodies_[b].body.off;
+    c.len[b] = bodies_[b].body.len;
+    c.kind[b] = bodies_[b].body.kind;
+  }
+  sv_txaccounts& A = c.A;
   A.struct_size = sizeof A;
   A.protocol_version = protocolVersion;
   A.sig_len = d.sigLen.data();
@@ -667,11 +675,51 @@ void SignatureBatchPrefetch::runDecidedRefs(const uint8_t* networkID, const uint
   A.n_apayloads = a.plen.size();
   A.n_bacct = a.bacct.size();
   A.n_checks = nc;
-  PubKeyUtils::checkTxBodiesAccountsUncached(networkID, blob, off.data(), len.data(), kind.data(), nb,
-                                             d.sigBegin.data(), d.hint.data(), d.sig.data(), d.sigLen.size(), A,
-                                             d.ok.data(), d.outWeight.data(), d.used.data(), digests.data());
+}
+
+void SignatureBatchPrefetch::runDecidedRefs(const uint8_t* networkID, const uint8_t* blob, uint32_t protocolVersion) {
+  Decided& d = dec_;
+  const size_t nb = bodies_.size(), nc = d.needed.size();
+  d.ok.assign(nc, 0);
+  d.outWeight.assign(nc, 0);
+  d.used.assign(nc, 0);
+  if (nb == 0) return;
+  AccountsCall c;
+  fillAccountsCall(c, protocolVersion);
+  PubKeyUtils::checkTxBodiesAccountsUncached(networkID, blob, c.off.data(), c.len.data(), c.kind.data(), nb,
+                                             d.sigBegin.data(), d.hint.data(), d.sig.data(), d.sigLen.size(), c.A,
+                                             d.ok.data(), d.outWeight.data(), d.used.data(), c.digests.data());
   for (size_t b = 0; b < nb; ++b)
-    if (bodies_[b].body.hashOut) std::memcpy(bodies_[b].body.hashOut->data(), &digests[32 * b], 32);
+    if (bodies_[b].body.hashOut) std::memcpy(bodies_[b].body.hashOut->data(), &c.digests[32 * b], 32);
+}
+
+void SignatureBatchPrefetch::runDecidedResults(const uint8_t* networkID, const uint8_t* blob,
+                                               uint32_t protocolVersion) {
+  Decided& d = dec_;
+  const size_t nb = bodies_.size();
+  // (fail closed: a body the engine never reached is not OK)
+  d.bodyCode.assign(nb, SV_TXRESULT_BAD_AUTH);
+  d.bodyFail.assign(nb, 0);
+  if (nb == 0) return;
+  AccountsCall c;
+  fillAccountsCall(c, protocolVersion);
+  sv_txresults R{};
+  R.struct_size = sizeof R;
+  R.check_role = d.role.data();
+  R.body_flags = d.bodyFlags.data();
+  R.body_code = d.bodyCode.data();
+  R.body_fail = d.bodyFail.data();
+  PubKeyUtils::decideTxBodiesAccountsUncached(networkID, blob, c.off.data(), c.len.data(), c.kind.data(), nb,
+                                              d.sigBegin.data(), d.hint.data(), d.sig.data(), d.sigLen.size(), c.A, R,
+                                              c.digests.data());
+  for (size_t b = 0; b < nb; ++b)
+    if (bodies_[b].body.hashOut) std::memcpy(bodies_[b].body.hashOut->data(), &c.digests[32 * b], 32);
+}
+
+SignatureBatchPrefetch::BodyResult SignatureBatchPrefetch::bodyResult(size_t body) const {
+  if (body >= dec_.bodyCode.size() || body >= dec_.listedOk.size())
+    throw std::out_of_range("SignatureBatchPrefetch::bodyResult: no such body (or runDecidedResults has not run)");
+  return BodyResult{dec_.bodyCode[body], dec_.bodyFail[body], dec_.listedOk[body] != 0};
 }
 
 SignatureBatchPrefetch::Decision SignatureBatchPrefetch::decision(size_t body, size_t check) const {

@@ -78,7 +78,9 @@ struct SignatureCheck {
 // One checkSignature call by reference -- nothing is copied.  A ledger account: `id` its account ID, `thresholds`
 // its four threshold bytes, `signers` its signer list, `level` 1..3 (needed = thresholds[level]).  The key of an
 // account that does not exist (checkSignatureNoAccount): `id` alone, level 0, needed 0.  The extra signers
-// (checkExtraSigners): `extra`, level 0, needed = their count.
+// (checkExtraSigners): `extra`, level 0, needed = their count.  `role` says whose failure a failing check is
+// (include/stellar_sigverify.h SV_TXROLE_*): 0 the transaction's (txBAD_AUTH: the source account, the extra
+// signers, a fee bump's fee source), 1 an operation's (opBAD_AUTH); only the results form reads it.
 struct SignatureCheckRef {
   uint256 const* id;
   uint8_t const* thresholds;
@@ -86,6 +88,7 @@ struct SignatureCheckRef {
   std::vector<SignerKey> const* extra;
   uint8_t level;
   int32_t needed;
+  uint8_t role = 0;
 };
 
 // Verdicts computed ahead of the checkers.
@@ -196,9 +199,23 @@ class SignatureBatchPrefetch {
   // it on the _cpu form and counts a fallback, never a reject); decision() then works as after runDecided, and
   // every decision is final (decidedFinal()): signed-payload signers are in the table.  A prefetch takes one
   // form only.
+  // Results form of the by-account form (sv_txresults): addDecidedRefs also records every check's role and, per
+  // body, skipUnused (the walk that listed the checks never asks "was every signature used":
+  // processSignatures below protocol 10) and listedOk (that walk, with every check true, ended in success -- it
+  // met no txNO_ACCOUNT / opNO_ACCOUNT).  runDecidedResults makes ONE sv_ed25519_decide_txbodies_accounts call
+  // that requests no per-check output (an engine error re-runs it on the _cpu form and counts a fallback, never a
+  // reject); bodyResult(body) is then the body's code, its first failing check and listedOk.  decision() is not
+  // available after it.
   bool addDecidedRefs(TxBody const& body, std::vector<DecoratedSignature> const& signatures,
-                      std::vector<SignatureCheckRef> const& checks);
+                      std::vector<SignatureCheckRef> const& checks, bool skipUnused = false, bool listedOk = true);
   void runDecidedRefs(const uint8_t* networkID, const uint8_t* blob, uint32_t protocolVersion);
+  struct BodyResult {
+    uint8_t code;   // SV_TXRESULT_*
+    uint32_t fail;  // body-local index of the first failing check, SV_TXRESULT_NONE: none
+    bool listedOk;
+  };
+  void runDecidedResults(const uint8_t* networkID, const uint8_t* blob, uint32_t protocolVersion);
+  BodyResult bodyResult(size_t body) const;
   size_t decidedAccounts() const { return acct_.thr.size() / 4; }
   size_t decidedChecks() const { return dec_.needed.size(); }
   // verdict for (pk, sig, msg) if prefetched (tx: see addBatch)
@@ -267,6 +284,9 @@ class SignatureBatchPrefetch {
     bool payload = false;
     std::vector<uint64_t> pkeyBegin{0};
     std::vector<uint8_t> pkey, pkeyPayload, pkeyLen;
+    // results form: roles per check; flags, the listing's outcome and the results per body
+    std::vector<uint8_t> role, bodyFlags, listedOk, bodyCode;
+    std::vector<uint32_t> bodyFail;
   } dec_;
   struct IdHash {
     size_t operator()(uint256 const& k) const {
@@ -281,6 +301,8 @@ class SignatureBatchPrefetch {
     std::vector<uint32_t> sweight, spay, bacct, cacct;
     std::unordered_map<uint256, uint32_t, IdHash> byId;  // ledger accounts already in the table
   } acct_;
+  struct AccountsCall;  // the arguments of one by-account engine call over dec_ / acct_
+  void fillAccountsCall(AccountsCall& c, uint32_t protocolVersion) const;
   uint32_t appendAccount(uint256 const* id, uint8_t const* thresholds, std::vector<Signer> const* signers,
                          std::vector<SignerKey> const* extra);
   std::vector<uint64_t> hSigBegin_{0}, hKeyBegin_{0};  // hinted body form: CSR by body, in addHinted order

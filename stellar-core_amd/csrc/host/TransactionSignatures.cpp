@@ -7,11 +7,15 @@
 
 #include <atomic>
 
+#include "../../../include/stellar_sigverify.h"
+
 namespace stellar {
 namespace {
 
 // signer lists built as std::vector<Signer> copies (signerListsBuilt())
 std::atomic<uint64_t> gSignerListsBuilt{0};
+// transactions of the results form that were not answered by their body's code alone (decidedWalks())
+std::atomic<uint64_t> gDecidedWalks{0};
 
 // TransactionFrame::checkSignature: master key (if its weight is non-zero)
 // then the account's signers
@@ -64,6 +68,11 @@ SignatureCheckRef extraRef(std::vector<SignerKey> const& keys) {
   return SignatureCheckRef{nullptr, nullptr, nullptr, &keys, 0, (int32_t)keys.size()};
 }
 SignatureCheckRef noAccountRef(uint256 const& id) { return SignatureCheckRef{&id, nullptr, nullptr, nullptr, 0, 0}; }
+// an operation's check: its failure is opBAD_AUTH (the results form reads the role; every other checker ignores it)
+SignatureCheckRef ofOperation(SignatureCheckRef r) {
+  r.role = SV_TXROLE_OP;
+  return r;
+}
 
 // ... and the list a reference stands for, as the copy the reference's checkSignature is handed
 SignatureCheck materialize(SignatureCheckRef const& r) {
@@ -86,6 +95,7 @@ SignatureCheck materialize(SignatureCheckRef const& r) {
 }  // namespace
 
 uint64_t signerListsBuilt() { return gSignerListsBuilt.load(std::memory_order_relaxed); }
+uint64_t decidedWalks() { return gDecidedWalks.load(std::memory_order_relaxed); }
 
 TxSigResult checkFeeBumpSignatures(FeeBumpSigInfo const& tx, AccountSnapshot const& accounts, uint32_t protocol,
                                    SignatureBatchPrefetch const* prefetched, bool forApply) {
@@ -148,7 +158,7 @@ TxSigResult walkTransaction(TransactionSigInfo const& tx, AccountSnapshot const&
     bool ok;
     int32_t opc = opINNER;
     if (acc) {
-      ok = check(accountRef(*acc, op.level));
+      ok = check(ofOperation(accountRef(*acc, op.level)));
       if (!ok) opc = opBAD_AUTH;
     } else if (!op.sourceAccount) {
       // (processSignatures calls OperationFrame::checkSignature with
@@ -158,7 +168,7 @@ TxSigResult walkTransaction(TransactionSigInfo const& tx, AccountSnapshot const&
       ok = false;
       opc = opNO_ACCOUNT;
     } else {
-      ok = check(noAccountRef(id));
+      ok = check(ofOperation(noAccountRef(id)));
       if (!ok) opc = opBAD_AUTH;
     }
     if (!ok && r.code != txFAILED) {
@@ -268,6 +278,18 @@ std::vector<SignatureCheckRef> listTransactionCheckRefs(TransactionSigInfo const
   return out;
 }
 
+TxSigResult listTransactionCheckRefs(TransactionSigInfo const& tx, AccountSnapshot const& accounts, uint32_t protocol,
+                                     bool forApply, std::vector<SignatureCheckRef>& out) {
+  out.clear();
+  return walkTransaction(
+      tx, accounts, protocol, forApply,
+      [&](SignatureCheckRef const& r) {
+        out.push_back(r);
+        return true;
+      },
+      [] { return true; });
+}
+
 std::vector<SignatureCheckRef> listFeeBumpOuterCheckRefs(FeeBumpSigInfo const& tx, AccountSnapshot const& accounts) {
   std::vector<SignatureCheckRef> out;
   if (AccountSigState const* fee = find(accounts, tx.feeSource)) out.push_back(accountRef(*fee, THRESHOLD_LOW_LEVEL));
@@ -320,6 +342,44 @@ TxSigResult checkFeeBumpSignaturesDecidedRefs(FeeBumpSigInfo const& tx, AccountS
     return r;
   }
   TxSigResult inner = checkTransactionSignaturesDecidedRefs(tx.inner, accounts, protocol, pre, innerBody, forApply);
+  r.code = inner.code == txSUCCESS ? txFEE_BUMP_INNER_SUCCESS : txFEE_BUMP_INNER_FAILED;
+  r.innerCode = inner.code;
+  r.failedOp = inner.failedOp;
+  r.opCode = inner.opCode;
+  return r;
+}
+
+TxSigResult checkTransactionSignaturesResults(TransactionSigInfo const& tx, AccountSnapshot const& accounts,
+                                              uint32_t protocol, SignatureBatchPrefetch const& pre, size_t body,
+                                              bool forApply) {
+  const SignatureBatchPrefetch::BodyResult b = pre.bodyResult(body);
+  // every check passed, every signature was used (or nobody asks), and the listing met no missing account
+  if (b.code == SV_TXRESULT_OK && b.listedOk) return TxSigResult();
+  // The first failure decides the walk: with check i false exactly for i = fail it takes the path the decisions
+  // themselves would have led it along (a later false check changes nothing once one has failed).
+  gDecidedWalks.fetch_add(1, std::memory_order_relaxed);
+  size_t next = 0;
+  return walkTransaction(
+      tx, accounts, protocol, forApply, [&](SignatureCheckRef const&) { return next++ != (size_t)b.fail; },
+      [&] { return b.code != SV_TXRESULT_BAD_AUTH_EXTRA; });
+}
+
+TxSigResult checkFeeBumpSignaturesResults(FeeBumpSigInfo const& tx, AccountSnapshot const& accounts,
+                                          uint32_t protocol, SignatureBatchPrefetch const& pre, size_t outerBody,
+                                          size_t innerBody, bool forApply) {
+  TxSigResult r;
+  auto failed = [&](int32_t code) {
+    gDecidedWalks.fetch_add(1, std::memory_order_relaxed);
+    r.code = code;
+    return r;
+  };
+  if (protocol < 13) return failed(txNOT_SUPPORTED);
+  if (!find(accounts, tx.feeSource)) return failed(txNO_ACCOUNT);
+  // the outer body: the fee source at LOW (role TX), then "every outer signature used"
+  const SignatureBatchPrefetch::BodyResult outer = pre.bodyResult(outerBody);
+  if (outer.code == SV_TXRESULT_BAD_AUTH_EXTRA) return failed(txBAD_AUTH_EXTRA);
+  if (outer.code != SV_TXRESULT_OK) return failed(txBAD_AUTH);
+  TxSigResult inner = checkTransactionSignaturesResults(tx.inner, accounts, protocol, pre, innerBody, forApply);
   r.code = inner.code == txSUCCESS ? txFEE_BUMP_INNER_SUCCESS : txFEE_BUMP_INNER_FAILED;
   r.innerCode = inner.code;
   r.failedOp = inner.failedOp;

@@ -130,6 +130,10 @@ std::vector<SignatureCheck> listFeeBumpOuterChecks(FeeBumpSigInfo const& tx, Acc
 std::vector<SignatureCheckRef> listTransactionCheckRefs(TransactionSigInfo const& tx, AccountSnapshot const& accounts,
                                                         uint32_t protocol, bool forApply = false);
 std::vector<SignatureCheckRef> listFeeBumpOuterCheckRefs(FeeBumpSigInfo const& tx, AccountSnapshot const& accounts);
+// The list into `out`, returning what the listing walk itself came to with every check true: txSUCCESS, or the
+// txNO_ACCOUNT / txFAILED with opNO_ACCOUNT that is decided without a check.  Every ref carries its role.
+TxSigResult listTransactionCheckRefs(TransactionSigInfo const& tx, AccountSnapshot const& accounts, uint32_t protocol,
+                                     bool forApply, std::vector<SignatureCheckRef>& out);
 // std::vector<Signer> copies of signer lists this module has built since the process started (the lists above
 // build none; every other path builds one per check)
 uint64_t signerListsBuilt();
@@ -159,6 +163,22 @@ TxSigResult checkTransactionSignaturesDecidedRefs(TransactionSigInfo const& tx, 
 TxSigResult checkFeeBumpSignaturesDecidedRefs(FeeBumpSigInfo const& tx, AccountSnapshot const& accounts,
                                               uint32_t protocol, SignatureBatchPrefetch const& pre, size_t outerBody,
                                               size_t innerBody, bool forApply = false);
+
+// ... and over one result per body (a prefetch filled with addDecidedRefs -- the lists above, skipUnused =
+// forApply && protocol < 10, listedOk = the listing returned txSUCCESS -- whose runDecidedResults has run).  A
+// body that is SV_TXRESULT_OK under a successful listing is a success WITHOUT any walk.  Otherwise the
+// transaction is walked once with check(i) = (i != the body's first failing check) and allUsed = (code !=
+// BAD_AUTH_EXTRA): the first failure decides a walk, so this is the TxSigResult the decisions themselves give
+// (checkTransactionSignaturesDecidedRefs), failedOp and opCode included.  A fee bump combines its outer body's
+// code with the inner transaction's result as checkFeeBumpSignaturesDecidedRefs does.  decidedWalks() counts
+// the transactions that were not answered by the fast path.
+TxSigResult checkTransactionSignaturesResults(TransactionSigInfo const& tx, AccountSnapshot const& accounts,
+                                              uint32_t protocol, SignatureBatchPrefetch const& pre, size_t body,
+                                              bool forApply = false);
+TxSigResult checkFeeBumpSignaturesResults(FeeBumpSigInfo const& tx, AccountSnapshot const& accounts,
+                                          uint32_t protocol, SignatureBatchPrefetch const& pre, size_t outerBody,
+                                          size_t innerBody, bool forApply = false);
+uint64_t decidedWalks();
 
 // Adds every (signature, signer) pair the checks of `tx` can reach.  With a
 // body (SignatureBatchPrefetch's body form) the contents hash is not read: it

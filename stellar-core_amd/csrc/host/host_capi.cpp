@@ -444,6 +444,7 @@ int svh_check_txset(const svh_tx* txs, size_t ntx, const svh_decorated_sig* sigs
 }
 
 uint64_t svh_signer_lists_built(void) { return stellar::signerListsBuilt(); }
+uint64_t svh_decided_walks(void) { return stellar::decidedWalks(); }
 
 void svh_txset_last_phases(double out[4]) { std::memcpy(out, t_txset_phases, sizeof t_txset_phases); }
 
@@ -480,9 +481,10 @@ int checkEnvelopes(const svh_envelope* env, size_t n, const svh_decorated_sig* s
                    const EnvelopeBodies* eb) {
   try {
     if (eb) {
-      if (prefetch != 0 && prefetch != 1 && prefetch != 3 && prefetch != 5 && prefetch != 6 && prefetch != 7)
+      if (prefetch != 0 && prefetch != 1 && prefetch != 3 && prefetch != 5 && prefetch != 6 && prefetch != 7 &&
+          prefetch != 8)
         throw std::invalid_argument(
-            "svh_check_envelopes_bodies: prefetch must be 0, 1, 3, 5, 6 or 7 (no keyed, cache-seeding form)");
+            "svh_check_envelopes_bodies: prefetch must be 0, 1, 3, 5, 6, 7 or 8 (no keyed, cache-seeding form)");
       if (!eb->networkID || !eb->contentsHashOut || !eb->feeBumpHashOut || (n && !eb->body))
         throw std::invalid_argument("svh_check_envelopes_bodies: null argument");
       for (size_t t = 0; t < n; ++t) {
@@ -542,15 +544,21 @@ int checkEnvelopes(const svh_envelope* env, size_t n, const svh_decorated_sig* s
     std::vector<size_t> innerBody, outerBody;
     bool decidedRun = false;
     bool decidedRefs = false;
-    if (prefetch == 7 && eb) {
+    bool decidedResults = false;
+    if ((prefetch == 7 || prefetch == 8) && eb) {
       // prefetch 7: the checks go to the engine as references to the snapshot's accounts (addDecidedRefs: every
       // account once in the prefetch's table, no signer list copied), ONE sv_ed25519_check_txbodies_accounts call,
       // every decision final; an envelope beyond the limits is checked by a plain SignatureChecker as in prefetch 5
       auto at = [&](uint64_t off) { return eb->blob ? eb->blob + off : nullptr; };
       innerBody.assign(n, kPlain);
       outerBody.assign(n, kPlain);
+      // prefetch 8: the same tables with each check's role, each body's SKIP_UNUSED flag and the outcome of the
+      // listing walk; ONE sv_ed25519_decide_txbodies_accounts call returns a code per body and nothing per check
+      const bool results = prefetch == 8;
+      const bool skipUnused = for_apply != 0 && protocol < 10;
       size_t nbodies = 0;
       const std::vector<SignatureCheckRef> none;
+      std::vector<SignatureCheckRef> listed;
       for (size_t t = 0; t < n; ++t) {
         svh_envelope_body const& b = eb->body[t];
         const bool bump = env[t].fee_bump != 0;
@@ -563,9 +571,12 @@ int checkEnvelopes(const svh_envelope* env, size_t n, const svh_decorated_sig* s
         }
         if (taken) {
           const SignatureBatchPrefetch::TxBody inner{b.off, b.len, (uint8_t)b.kind, &txs[t].inner.contentsHash};
-          taken = pre.addDecidedRefs(
-              inner, txs[t].inner.signatures,
-              !bump || protocol >= 13 ? listTransactionCheckRefs(txs[t].inner, snap, protocol, for_apply != 0) : none);
+          if (!bump || protocol >= 13) {
+            const TxSigResult l = listTransactionCheckRefs(txs[t].inner, snap, protocol, for_apply != 0, listed);
+            taken = pre.addDecidedRefs(inner, txs[t].inner.signatures, listed, skipUnused, l.code == txSUCCESS);
+          } else {
+            taken = pre.addDecidedRefs(inner, txs[t].inner.signatures, none);
+          }
           if (taken) innerBody[t] = nbodies++;
         }
         if (!taken) {
@@ -574,8 +585,10 @@ int checkEnvelopes(const svh_envelope* env, size_t n, const svh_decorated_sig* s
           if (bump) txs[t].contentsHash = hostContentsHash(eb->networkID, 2, at(b.outer_off), b.outer_len);
         }
       }
-      pre.runDecidedRefs(eb->networkID, eb->blob, protocol);
+      if (results) pre.runDecidedResults(eb->networkID, eb->blob, protocol);
+      else pre.runDecidedRefs(eb->networkID, eb->blob, protocol);
       decidedRun = decidedRefs = true;
+      decidedResults = results;
     } else if ((prefetch == 5 || prefetch == 6) && eb) {
       auto at = [&](uint64_t off) { return eb->blob ? eb->blob + off : nullptr; };
       innerBody.assign(n, kPlain);
@@ -642,7 +655,12 @@ int checkEnvelopes(const svh_envelope* env, size_t n, const svh_decorated_sig* s
     auto check = [&](size_t a, size_t b) {
       for (size_t t = a; t < b; ++t) {
         TxSigResult r;
-        if (decidedRefs && innerBody[t] != kPlain)
+        if (decidedResults && innerBody[t] != kPlain)
+          r = env[t].fee_bump
+                  ? checkFeeBumpSignaturesResults(txs[t], snap, protocol, pre, outerBody[t], innerBody[t],
+                                                  for_apply != 0)
+                  : checkTransactionSignaturesResults(txs[t].inner, snap, protocol, pre, innerBody[t], for_apply != 0);
+        else if (decidedRefs && innerBody[t] != kPlain)
           r = env[t].fee_bump
                   ? checkFeeBumpSignaturesDecidedRefs(txs[t], snap, protocol, pre, outerBody[t], innerBody[t],
                                                       for_apply != 0)

@@ -1,6 +1,6 @@
 // The one declaration of every extern "C" launcher and size query that
 // crosses between the kernel files (sv_kernels.hip, sv_comb.hip, sv_hash.hip,
-// sv_txhash.hip, sv_txpair.hip, sv_txcheck.hip), sv_cpu.cpp and the engine (sv_api.cpp and its modules).
+// sv_txhash.hip, sv_txpair.hip, sv_txcheck.hip, sv_txacct.hip, sv_txresult.hip), sv_cpu.cpp and the engine (sv_api.cpp and its modules).
 // Included by the callers and by every definer, so a changed parameter list
 // is a compile error instead of arguments corrupted at run time.
 #pragma once
@@ -51,6 +51,18 @@ int sv_txaccounts_check(const uint8_t* network_id, const uint8_t* bodies, const 
                         const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig, size_t n_sigs,
                         const struct sv_txaccounts* accts, const uint8_t* check_ok, const uint32_t* check_weight,
                         const uint64_t* check_used, uint32_t* acnt);
+
+// Argument checks of the decide entry points' sv_txresults (sv_cpu.cpp): the struct itself (struct_size, body_code,
+// bad_body against bad_cap); then, once the twin's check has vouched for the counts, the roles (<= 1) and the flags
+// (bit 0 only).  The bad list of a host form from body_code (global indices, *n_bad exact), and txresult.h over
+// host arrays: body_code, body_fail, then the bad list.
+struct sv_txresults;
+int sv_txresults_args(const struct sv_txresults* res);
+int sv_txresults_check(const struct sv_txresults* res, size_t n_bodies, size_t n_checks);
+void sv_txresults_bad_list(const struct sv_txresults* res, size_t n_bodies);
+void sv_txresults_fold(const struct sv_txresults* res, const uint64_t* check_begin, const uint64_t* sig_begin,
+                       const uint8_t* check_ok, const uint64_t* check_used, size_t n_bodies, size_t n_checks,
+                       size_t n_sigs);
 
 }  // extern "C"
 
@@ -153,6 +165,15 @@ hipError_t sv_launch_acct_count(const struct sv_acct_tab* T, const void* tab_ws,
                                 const struct sv_acct_out* O, void* ws, hipStream_t s);
 hipError_t sv_launch_acct_fill(const struct sv_acct_tab* T, const void* tab_ws, const struct sv_acct_use* U,
                                const struct sv_acct_out* O, void* ws, hipStream_t s);
+// one result per body (sv_txresult.hip, txresult.h), after the check kernel on the same stream: body_code (and
+// body_fail, optional) from I's check_ok / check_used; with bad_body or n_bad also the scan and, with bad_body and
+// bad_cap > 0, the fill of the ascending non-OK bodies (entries at or past bad_cap are never written, *n_bad is
+// exact).  `ws` holds sv_txresult_ws_bytes(nb); the struct is host memory, its arrays and the outputs device memory.
+struct sv_txresult_in;
+int sv_txresult_block(void);
+size_t sv_txresult_ws_bytes(uint64_t n_bodies);
+hipError_t sv_launch_txresult(const struct sv_txresult_in* I, uint8_t* body_code, uint32_t* body_fail, void* ws,
+                              uint32_t* bad_body, uint64_t bad_cap, uint64_t* n_bad, hipStream_t s);
 // warm-key latency path (sv_comb.hip)
 size_t sv_comb_btab_bytes(void);
 size_t sv_key_slot_bytes(void);

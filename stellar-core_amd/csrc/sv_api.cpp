@@ -833,22 +833,44 @@ int sv_ed25519_verify_txbodies_hinted_device(int device, const uint8_t* network_
   return SV_OK;
 }
 
-int sv_ed25519_check_txbodies(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
-                              const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
-                              const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig, size_t n_sigs,
-                              const uint64_t* key_begin, const uint8_t* key, size_t n_keys, const sv_txchecks* checks,
-                              uint8_t* check_ok, uint32_t* check_weight, uint64_t* check_used, uint8_t* digests,
-                              const sv_opts* opts) {
+// (the twins' argument checks only ask whether the three check outputs are there; a decide call may leave any out)
+static const uint64_t kPresent = 0;
+static int results_args(const sv_txresults* res) {
+  if (sv_txresults_args(res))
+    return fail(SV_ERR_INVALID_ARG,
+                "tx results: null struct or body_code, a struct_size that is too small, or bad_cap without bad_body");
+  return SV_OK;
+}
+static int results_check(const sv_txresults* res, size_t n_bodies, size_t n_checks) {
+  if (sv_txresults_check(res, n_bodies, n_checks))
+    return fail(SV_ERR_INVALID_ARG, "tx results: a check_role > 1 or a body_flags bit other than bit 0");
+  return SV_OK;
+}
+
+// sv_ed25519_check_txbodies and, with `res`, sv_ed25519_decide_txbodies (the three check outputs are then res's,
+// each optional).
+static int check_host(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                      const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies, const uint64_t* sig_begin,
+                      const uint8_t* hint, const uint8_t* sig, size_t n_sigs, const uint64_t* key_begin,
+                      const uint8_t* key, size_t n_keys, const sv_txchecks* checks, uint8_t* check_ok,
+                      uint32_t* check_weight, uint64_t* check_used, const sv_txresults* res, uint8_t* digests,
+                      const sv_opts* opts) {
   LifeGuard life_;
   int rc = check_opts(opts);
   if (rc) return rc;
+  if (res && (rc = results_args(res))) return rc;
   if (sv_txchecks_check(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, n_sigs,
-                        key_begin, key, n_keys, checks, check_ok, check_weight, check_used))
+                        key_begin, key, n_keys, checks, res ? (const uint8_t*)&kPresent : check_ok,
+                        res ? (const uint32_t*)&kPresent : check_weight, res ? &kPresent : check_used))
     return fail(SV_ERR_INVALID_ARG,
                 "tx checks: null pointer, body kind > 2, malformed CSR array, signer type > 3, key index outside its "
                 "body, sig_len > 64, more than 64 signatures or signers in a check, protocol 7, or a malformed payload "
                 "table (pkey_begin, pkey_len > 64, null table, 2^32 or more candidates)");
-  if (n_bodies == 0) return SV_OK;
+  if (res && (rc = results_check(res, n_bodies, checks->n_checks))) return rc;
+  if (n_bodies == 0) {
+    if (res) sv_txresults_bad_list(res, 0);
+    return SV_OK;
+  }
   if ((rc = debug_fail())) return rc;
   if ((rc = ensure_init())) return rc;
   std::vector<Device*> devs;
@@ -866,16 +888,46 @@ int sv_ed25519_check_txbodies(const uint8_t* network_id, const uint8_t* bodies, 
     in.qlen = pt->pkey_len;
   }
   const int clamp = checks->protocol_version >= 10;
-  const CheckOut out{check_ok, check_weight, check_used, digests};
+  ResultOut ro{};
+  if (res) ro = ResultOut{res->check_role, res->body_flags, res->body_code, res->body_fail};
+  const CheckOut out{check_ok, check_weight, check_used, digests, res ? &ro : nullptr};
   const size_t G = devs.size();
-  if (G == 1) return check_slice(*devs[0], in, 0, n_bodies, clamp, out, path);
-  // Slices of whole bodies: a body's checks are contiguous, so every slot
-  // writes its decisions straight into the caller's arrays.
-  const std::vector<size_t> cut = pair_slices(sig_begin, n_bodies, G);
-  return shard(devs, G, [&](Device& D, size_t g, size_t) {
-    if (cut[g] == cut[g + 1]) return SV_OK;
-    return check_slice(D, in, cut[g], cut[g + 1], clamp, out, path);
-  });
+  if (G == 1) {
+    rc = check_slice(*devs[0], in, 0, n_bodies, clamp, out, path);
+  } else {
+    // Slices of whole bodies: a body's checks are contiguous, so every slot
+    // writes its decisions straight into the caller's arrays.
+    const std::vector<size_t> cut = pair_slices(sig_begin, n_bodies, G);
+    rc = shard(devs, G, [&](Device& D, size_t g, size_t) {
+      if (cut[g] == cut[g + 1]) return SV_OK;
+      return check_slice(D, in, cut[g], cut[g + 1], clamp, out, path);
+    });
+  }
+  // (the bad list of a decide call: on the host, from the codes of every chunk and slot)
+  if (rc == SV_OK && res) sv_txresults_bad_list(res, n_bodies);
+  return rc;
+}
+
+int sv_ed25519_check_txbodies(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                              const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                              const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig, size_t n_sigs,
+                              const uint64_t* key_begin, const uint8_t* key, size_t n_keys, const sv_txchecks* checks,
+                              uint8_t* check_ok, uint32_t* check_weight, uint64_t* check_used, uint8_t* digests,
+                              const sv_opts* opts) {
+  return check_host(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, n_sigs,
+                    key_begin, key, n_keys, checks, check_ok, check_weight, check_used, nullptr, digests, opts);
+}
+
+int sv_ed25519_decide_txbodies(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                               const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                               const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig, size_t n_sigs,
+                               const uint64_t* key_begin, const uint8_t* key, size_t n_keys, const sv_txchecks* checks,
+                               const sv_txresults* res, uint8_t* digests, const sv_opts* opts) {
+  if (!res) return fail(SV_ERR_INVALID_ARG, "tx results: null struct");
+  return check_host(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, n_sigs,
+                    key_begin, key, n_keys, checks, res->struct_size >= sizeof(sv_txresults) ? res->check_ok : nullptr,
+                    res->struct_size >= sizeof(sv_txresults) ? res->check_weight : nullptr,
+                    res->struct_size >= sizeof(sv_txresults) ? res->check_used : nullptr, res, digests, opts);
 }
 
 }  // extern "C"
@@ -883,13 +935,18 @@ int sv_ed25519_check_txbodies(const uint8_t* network_id, const uint8_t* bodies, 
 namespace {
 // The device-resident check call on slot D (caller holds D.mu, device set, slot ready, arguments checked): `ck`'s
 // arrays and `pl` are device memory.  Shared by sv_ed25519_check_txbodies_device and the by-account form, which
-// runs it on the tables it expanded.
+// runs it on the tables it expanded.  With `res` (a decide call) the result kernels follow the check kernel on
+// the slot's stream, ahead of the event the caller's stream waits for: no wait is added.
+struct DevDecide {
+  const sv_txresults* res = nullptr;
+  void* ws = nullptr;  // sv_txresult_ws_bytes(n_bodies)
+};
 int check_device_locked(Device& D, const uint8_t* network_id, const void* d_bodies, const uint64_t* d_body_off,
                         const uint32_t* d_body_len, const uint8_t* d_body_kind, size_t n_bodies,
                         const uint64_t* d_sig_begin, const void* d_hint, const void* d_sig, size_t n_sigs,
                         const uint64_t* d_key_begin, const void* d_key, size_t n_keys, const sv_txchecks* ck,
                         const PayloadDev& pl, void* d_check_ok, uint32_t* d_check_weight, uint64_t* d_check_used,
-                        void* d_digests, void* stream) {
+                        void* d_digests, void* stream, const DevDecide& dec = DevDecide()) {
   int rc;
   hipStream_t user = (hipStream_t)stream;
   // the pairing workspace, pair_begin, a digest array when the caller wants
@@ -947,22 +1004,73 @@ int check_device_locked(Device& D, const uint8_t* network_id, const void* d_bodi
                            ck->protocol_version >= 10, d_ppb, (const uint32_t*)(dpp + L.o_idx),
                            (const uint32_t*)(dpp + L.o_idx) + npp, dpp, npp, pl.qb, pl.nq, (uint8_t*)d_check_ok,
                            d_check_weight, d_check_used, D.stream));
+  if (dec.res) {
+    const sv_txresults& R = *dec.res;
+    const sv_txresult_in I{ck->check_begin, d_sig_begin,  (const uint8_t*)d_check_ok, d_check_used, R.check_role,
+                           R.body_flags,    n_bodies,     ck->n_checks,               n_sigs};
+    SV_HIP(sv_launch_txresult(&I, R.body_code, R.body_fail, dec.ws, R.bad_body, R.bad_cap, R.n_bad, D.stream));
+  }
   SV_HIP(hipEventRecord(D.dep_out, D.stream));
   SV_HIP(hipStreamWaitEvent(user, D.dep_out, 0));
+  return SV_OK;
+}
+
+// A device-resident decide call's sv_txresults: the pointers and their alignment.
+int decide_device_args(const sv_txresults* res, size_t n_bodies) {
+  if (!res || res->struct_size < sizeof(sv_txresults) || (n_bodies && !res->body_code) ||
+      (res->bad_cap && !res->bad_body))
+    return fail(SV_ERR_INVALID_ARG,
+                "tx results: null struct or body_code, a struct_size that is too small, or bad_cap without bad_body");
+  if (((uintptr_t)res->body_fail & 3u) || ((uintptr_t)res->check_weight & 3u) || ((uintptr_t)res->check_used & 7u) ||
+      ((uintptr_t)res->bad_body & 3u) || ((uintptr_t)res->n_bad & 7u))
+    return fail(SV_ERR_ALIGN, "tx results: the output arrays must be naturally aligned");
+  return SV_OK;
+}
+// A decide call over no body: nothing runs, the count of failing bodies is 0.
+int decide_device_empty(const sv_txresults* res, void* stream) {
+  if (res->n_bad) SV_HIP(hipMemsetAsync(res->n_bad, 0, 8, (hipStream_t)stream));
+  return SV_OK;
+}
+// Its check arrays and workspace on slot D (caller holds D.mu): the caller's arrays where it asked for them, else
+// D.txres -- used (8 nc) | weight (4 nc) | ok (nc) | the result kernels' workspace.  Growing drains the kernel
+// stream, as the twin's own buffers do.
+int decide_device_bufs(Device& D, const sv_txresults* res, size_t n_bodies, size_t nc, void** ok, uint32_t** weight,
+                       uint64_t** used, DevDecide* dec) {
+  const size_t o_w = al16(8 * nc), o_ok = o_w + al16(4 * nc), o_ws = o_ok + al16(nc);
+  const size_t need = o_ws + al16(sv_txresult_ws_bytes(n_bodies)) + 16;
+  if (need > D.txres.cap) {
+    SV_HIP(hipStreamSynchronize(D.stream));
+    int rc;
+    if ((rc = D.txres.ensure(need))) return rc;
+  }
+  uint8_t* b = (uint8_t*)D.txres.p;
+  *used = res->check_used ? res->check_used : (uint64_t*)b;
+  *weight = res->check_weight ? res->check_weight : (uint32_t*)(b + o_w);
+  *ok = res->check_ok ? (void*)res->check_ok : (void*)(b + o_ok);
+  dec->res = res;
+  dec->ws = b + o_ws;
   return SV_OK;
 }
 }  // namespace
 
 extern "C" {
 
-int sv_ed25519_check_txbodies_device(int device, const uint8_t* network_id, const void* d_bodies,
-                                     const uint64_t* d_body_off, const uint32_t* d_body_len,
-                                     const uint8_t* d_body_kind, size_t n_bodies, const uint64_t* d_sig_begin,
-                                     const void* d_hint, const void* d_sig, size_t n_sigs,
-                                     const uint64_t* d_key_begin, const void* d_key, size_t n_keys,
-                                     const sv_txchecks* ck, void* d_check_ok, uint32_t* d_check_weight,
-                                     uint64_t* d_check_used, void* d_digests, void* stream) {
+// sv_ed25519_check_txbodies_device and, with `res`, sv_ed25519_decide_txbodies_device (the three check arrays are
+// then res's, or the slot's own where res has none).
+static int check_device(int device, const uint8_t* network_id, const void* d_bodies, const uint64_t* d_body_off,
+                        const uint32_t* d_body_len, const uint8_t* d_body_kind, size_t n_bodies,
+                        const uint64_t* d_sig_begin, const void* d_hint, const void* d_sig, size_t n_sigs,
+                        const uint64_t* d_key_begin, const void* d_key, size_t n_keys, const sv_txchecks* ck,
+                        void* d_check_ok, uint32_t* d_check_weight, uint64_t* d_check_used, const sv_txresults* res,
+                        void* d_digests, void* stream) {
   LifeGuard life_;
+  int rc;
+  if (res) {
+    if ((rc = decide_device_args(res, n_bodies))) return rc;
+    d_check_ok = res->check_ok ? (void*)res->check_ok : (void*)&kPresent;
+    d_check_weight = res->check_weight ? res->check_weight : (uint32_t*)&kPresent;
+    d_check_used = res->check_used ? res->check_used : (uint64_t*)&kPresent;
+  }
   if (!network_id || !ck || ck->struct_size < sizeof(sv_txchecks) ||
       (n_bodies && (!d_bodies || !d_body_off || !d_body_len || !d_body_kind || !d_sig_begin || !d_key_begin ||
                     !ck->check_begin)) ||
@@ -993,29 +1101,56 @@ int sv_ed25519_check_txbodies_device(int device, const uint8_t* network_id, cons
       ((uintptr_t)ck->signer_weight & 3u) || ((uintptr_t)ck->signer_key & 3u) || ((uintptr_t)d_check_weight & 3u) ||
       ((uintptr_t)d_check_used & 7u))
     return fail(SV_ERR_ALIGN, "sig/key/digests must be 16-byte aligned, hint and the check arrays naturally aligned");
-  int rc;
   if ((rc = debug_fail())) return rc;
   Device* Dp;
   if ((rc = slot_arg(device, Dp))) return rc;
   Device& D = *Dp;
-  if (n_bodies == 0) return SV_OK;
+  if (n_bodies == 0) return res ? decide_device_empty(res, stream) : SV_OK;
   std::lock_guard<std::mutex> g(D.mu);
   SV_HIP(hipSetDevice(D.phys));
   if ((rc = ready_locked(D))) return rc;
+  DevDecide dec;
+  if (res && (rc = decide_device_bufs(D, res, n_bodies, ck->n_checks, &d_check_ok, &d_check_weight, &d_check_used,
+                                      &dec)))
+    return rc;
   return check_device_locked(D, network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin,
                              d_hint, d_sig, n_sigs, d_key_begin, d_key, n_keys, ck, pl, d_check_ok, d_check_weight,
-                             d_check_used, d_digests, stream);
+                             d_check_used, d_digests, stream, dec);
 }
 
-int sv_ed25519_check_txbodies_accounts(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
-                                       const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
-                                       const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig,
-                                       size_t n_sigs, const sv_txaccounts* A, uint8_t* check_ok,
-                                       uint32_t* check_weight, uint64_t* check_used, uint8_t* digests,
-                                       const sv_opts* opts) {
+int sv_ed25519_check_txbodies_device(int device, const uint8_t* network_id, const void* d_bodies,
+                                     const uint64_t* d_body_off, const uint32_t* d_body_len,
+                                     const uint8_t* d_body_kind, size_t n_bodies, const uint64_t* d_sig_begin,
+                                     const void* d_hint, const void* d_sig, size_t n_sigs,
+                                     const uint64_t* d_key_begin, const void* d_key, size_t n_keys,
+                                     const sv_txchecks* ck, void* d_check_ok, uint32_t* d_check_weight,
+                                     uint64_t* d_check_used, void* d_digests, void* stream) {
+  return check_device(device, network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin, d_hint,
+                      d_sig, n_sigs, d_key_begin, d_key, n_keys, ck, d_check_ok, d_check_weight, d_check_used, nullptr,
+                      d_digests, stream);
+}
+
+int sv_ed25519_decide_txbodies_device(int device, const uint8_t* network_id, const void* d_bodies,
+                                      const uint64_t* d_body_off, const uint32_t* d_body_len,
+                                      const uint8_t* d_body_kind, size_t n_bodies, const uint64_t* d_sig_begin,
+                                      const void* d_hint, const void* d_sig, size_t n_sigs,
+                                      const uint64_t* d_key_begin, const void* d_key, size_t n_keys,
+                                      const sv_txchecks* ck, const sv_txresults* res, void* d_digests, void* stream) {
+  if (!res) return fail(SV_ERR_INVALID_ARG, "tx results: null struct");
+  return check_device(device, network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin, d_hint,
+                      d_sig, n_sigs, d_key_begin, d_key, n_keys, ck, nullptr, nullptr, nullptr, res, d_digests, stream);
+}
+
+// sv_ed25519_check_txbodies_accounts and, with `res`, sv_ed25519_decide_txbodies_accounts.
+static int accounts_host(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                         const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                         const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig, size_t n_sigs,
+                         const sv_txaccounts* A, uint8_t* check_ok, uint32_t* check_weight, uint64_t* check_used,
+                         const sv_txresults* res, uint8_t* digests, const sv_opts* opts) {
   LifeGuard life_;
   int rc = check_opts(opts);
   if (rc) return rc;
+  if (res && (rc = results_args(res))) return rc;
   // (the per-account row counts come out of the argument check: made once, used by every slot's planner)
   std::vector<uint32_t> acnt(2);
   if (A && A->struct_size >= sizeof(sv_txaccounts) && !((uint64_t)A->n_accounts >> 32)) {
@@ -1026,13 +1161,18 @@ int sv_ed25519_check_txbodies_accounts(const uint8_t* network_id, const uint8_t*
     }
   }
   if (sv_txaccounts_check(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, n_sigs, A,
-                          check_ok, check_weight, check_used, acnt.data()))
+                          res ? (const uint8_t*)&kPresent : check_ok, res ? (const uint32_t*)&kPresent : check_weight,
+                          res ? &kPresent : check_used, acnt.data()))
     return fail(SV_ERR_INVALID_ARG,
                 "tx checks by account: null pointer, body kind > 2, malformed CSR array, bacct entry >= n_accounts, "
                 "check_acct outside its body, level > 3, signer type > 3, payload index >= n_apayloads, apayload_len "
                 "or sig_len > 64, more than 64 signatures in a body with checks or signers in an account's expanded "
                 "list, protocol 7, 2^32 or more rows, or a struct_size that is too small");
-  if (n_bodies == 0) return SV_OK;
+  if (res && (rc = results_check(res, n_bodies, A->n_checks))) return rc;
+  if (n_bodies == 0) {
+    if (res) sv_txresults_bad_list(res, 0);
+    return SV_OK;
+  }
   if ((rc = debug_fail())) return rc;
   if ((rc = ensure_init())) return rc;
   std::vector<Device*> devs;
@@ -1042,25 +1182,60 @@ int sv_ed25519_check_txbodies_accounts(const uint8_t* network_id, const uint8_t*
                   A->sig_len,     A->bacct_begin,  A->bacct,   A->check_begin, A->check_acct,
                   A->check_level, A->check_needed, acnt.data()};
   const int clamp = A->protocol_version >= 10;
-  const CheckOut out{check_ok, check_weight, check_used, digests};
+  ResultOut ro{};
+  if (res) ro = ResultOut{res->check_role, res->body_flags, res->body_code, res->body_fail};
+  const CheckOut out{check_ok, check_weight, check_used, digests, res ? &ro : nullptr};
   const size_t G = devs.size();
-  if (G == 1) return acct_slice(*devs[0], in, *A, 0, n_bodies, clamp, out, path);
-  // (slices of whole bodies as in sv_ed25519_check_txbodies; every slot takes the whole account table)
-  const std::vector<size_t> cut = pair_slices(sig_begin, n_bodies, G);
-  return shard(devs, G, [&](Device& D, size_t g, size_t) {
-    if (cut[g] == cut[g + 1]) return SV_OK;
-    return acct_slice(D, in, *A, cut[g], cut[g + 1], clamp, out, path);
-  });
+  if (G == 1) {
+    rc = acct_slice(*devs[0], in, *A, 0, n_bodies, clamp, out, path);
+  } else {
+    // (slices of whole bodies as in sv_ed25519_check_txbodies; every slot takes the whole account table)
+    const std::vector<size_t> cut = pair_slices(sig_begin, n_bodies, G);
+    rc = shard(devs, G, [&](Device& D, size_t g, size_t) {
+      if (cut[g] == cut[g + 1]) return SV_OK;
+      return acct_slice(D, in, *A, cut[g], cut[g + 1], clamp, out, path);
+    });
+  }
+  if (rc == SV_OK && res) sv_txresults_bad_list(res, n_bodies);
+  return rc;
 }
 
-int sv_ed25519_check_txbodies_accounts_device(int device, const uint8_t* network_id, const void* d_bodies,
-                                              const uint64_t* d_body_off, const uint32_t* d_body_len,
-                                              const uint8_t* d_body_kind, size_t n_bodies,
-                                              const uint64_t* d_sig_begin, const void* d_hint, const void* d_sig,
-                                              size_t n_sigs, const sv_txaccounts* A, void* d_check_ok,
-                                              uint32_t* d_check_weight, uint64_t* d_check_used, void* d_digests,
-                                              void* stream) {
+int sv_ed25519_check_txbodies_accounts(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                       const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                       const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig,
+                                       size_t n_sigs, const sv_txaccounts* A, uint8_t* check_ok,
+                                       uint32_t* check_weight, uint64_t* check_used, uint8_t* digests,
+                                       const sv_opts* opts) {
+  return accounts_host(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, n_sigs, A,
+                       check_ok, check_weight, check_used, nullptr, digests, opts);
+}
+
+int sv_ed25519_decide_txbodies_accounts(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                        const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                        const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig,
+                                        size_t n_sigs, const sv_txaccounts* A, const sv_txresults* res,
+                                        uint8_t* digests, const sv_opts* opts) {
+  if (!res) return fail(SV_ERR_INVALID_ARG, "tx results: null struct");
+  const bool whole = res->struct_size >= sizeof(sv_txresults);
+  return accounts_host(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, n_sigs, A,
+                       whole ? res->check_ok : nullptr, whole ? res->check_weight : nullptr,
+                       whole ? res->check_used : nullptr, res, digests, opts);
+}
+
+// sv_ed25519_check_txbodies_accounts_device and, with `res`, sv_ed25519_decide_txbodies_accounts_device.
+static int accounts_device(int device, const uint8_t* network_id, const void* d_bodies, const uint64_t* d_body_off,
+                           const uint32_t* d_body_len, const uint8_t* d_body_kind, size_t n_bodies,
+                           const uint64_t* d_sig_begin, const void* d_hint, const void* d_sig, size_t n_sigs,
+                           const sv_txaccounts* A, void* d_check_ok, uint32_t* d_check_weight, uint64_t* d_check_used,
+                           const sv_txresults* res, void* d_digests, void* stream) {
   LifeGuard life_;
+  int rc;
+  if (res) {
+    if ((rc = decide_device_args(res, n_bodies))) return rc;
+    d_check_ok = res->check_ok ? (void*)res->check_ok : (void*)&kPresent;
+    d_check_weight = res->check_weight ? res->check_weight : (uint32_t*)&kPresent;
+    d_check_used = res->check_used ? res->check_used : (uint64_t*)&kPresent;
+  }
   if (!network_id || !A || A->struct_size < sizeof(sv_txaccounts))
     return fail(SV_ERR_INVALID_ARG, "tx checks by account: null pointer or a struct_size that is too small");
   const size_t na = A->n_accounts, ns = A->n_asigners, np = A->n_apayloads, ne = A->n_bacct, nc = A->n_checks;
@@ -1082,16 +1257,18 @@ int sv_ed25519_check_txbodies_accounts_device(int device, const uint8_t* network
       ((uintptr_t)A->check_needed & 3u) || ((uintptr_t)d_check_weight & 3u) || ((uintptr_t)d_check_used & 7u))
     return fail(SV_ERR_ALIGN,
                 "sig/digests/acct_key/asigner_key/apayload must be 16-byte aligned, the other arrays naturally aligned");
-  int rc;
   if ((rc = debug_fail())) return rc;
   Device* Dp;
   if ((rc = slot_arg(device, Dp))) return rc;
   Device& D = *Dp;
-  if (n_bodies == 0) return SV_OK;
+  if (n_bodies == 0) return res ? decide_device_empty(res, stream) : SV_OK;
   hipStream_t user = (hipStream_t)stream;
   std::lock_guard<std::mutex> g(D.mu);
   SV_HIP(hipSetDevice(D.phys));
   if ((rc = ready_locked(D))) return rc;
+  DevDecide dec;
+  if (res && (rc = decide_device_bufs(D, res, n_bodies, nc, &d_check_ok, &d_check_weight, &d_check_used, &dec)))
+    return rc;
   const sv_acct_tab T{A->acct_key,       A->acct_thresholds, A->asigner_begin,   A->asigner_type,
                       A->asigner_weight, A->asigner_key,     A->asigner_payload, A->apayload,
                       A->apayload_len,   na,                 ns,                 np};
@@ -1147,7 +1324,29 @@ int sv_ed25519_check_txbodies_accounts_device(int device, const uint8_t* network
   }
   return check_device_locked(D, network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin,
                              d_hint, d_sig, n_sigs, O.key_begin, O.key, nk, &P.checks, pl, d_check_ok, d_check_weight,
-                             d_check_used, d_digests, stream);
+                             d_check_used, d_digests, stream, dec);
+}
+
+int sv_ed25519_check_txbodies_accounts_device(int device, const uint8_t* network_id, const void* d_bodies,
+                                              const uint64_t* d_body_off, const uint32_t* d_body_len,
+                                              const uint8_t* d_body_kind, size_t n_bodies,
+                                              const uint64_t* d_sig_begin, const void* d_hint, const void* d_sig,
+                                              size_t n_sigs, const sv_txaccounts* A, void* d_check_ok,
+                                              uint32_t* d_check_weight, uint64_t* d_check_used, void* d_digests,
+                                              void* stream) {
+  return accounts_device(device, network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin,
+                         d_hint, d_sig, n_sigs, A, d_check_ok, d_check_weight, d_check_used, nullptr, d_digests, stream);
+}
+
+int sv_ed25519_decide_txbodies_accounts_device(int device, const uint8_t* network_id, const void* d_bodies,
+                                               const uint64_t* d_body_off, const uint32_t* d_body_len,
+                                               const uint8_t* d_body_kind, size_t n_bodies,
+                                               const uint64_t* d_sig_begin, const void* d_hint, const void* d_sig,
+                                               size_t n_sigs, const sv_txaccounts* A, const sv_txresults* res,
+                                               void* d_digests, void* stream) {
+  if (!res) return fail(SV_ERR_INVALID_ARG, "tx results: null struct");
+  return accounts_device(device, network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin,
+                         d_hint, d_sig, n_sigs, A, nullptr, nullptr, nullptr, res, d_digests, stream);
 }
 
 int sv_ed25519_verify_device(int device, const void* d_pk, const void* d_sig, const void* d_msg,
@@ -1394,7 +1593,7 @@ int sv_workspace_bytes(int device, size_t* bytes) {
   std::lock_guard<std::mutex> gl(Dp->lat.mu);
   std::lock_guard<std::mutex> g(Dp->mu);
   size_t b = Dp->ws.cap + Dp->txmsg.cap + Dp->txpk.cap + Dp->txsg.cap + Dp->txpair.cap + Dp->txchk.cap + Dp->txpp.cap;
-  b += Dp->txatab.cap + Dp->txaws.cap + Dp->txarows.cap;
+  b += Dp->txatab.cap + Dp->txaws.cap + Dp->txarows.cap + Dp->txres.cap;
   for (const LatCtx& c : Dp->lat.ctx) b += c.ws.cap + c.d_in.cap + c.d_out.cap + c.d_keys.cap;
   *bytes = b;
   return SV_OK;

@@ -28,6 +28,7 @@
 #include "txhash.h"
 #include "txcheck.h"
 #include "txacct.h"
+#include "txresult.h"
 #pragma GCC diagnostic pop
 
 #include <algorithm>
@@ -636,6 +637,118 @@ int sv_ed25519_check_txbodies_accounts_cpu(const uint8_t* network_id, const uint
   return sv_ed25519_check_txbodies_cpu(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint,
                                        sig, n_sigs, kb.data(), key.data(), nk, &P.checks, check_ok, check_weight,
                                        check_used, digests, threads);
+}
+
+// Argument check of the decide entry points' sv_txresults (declared in launch.h), the part that needs no table:
+// SV_OK or SV_ERR_INVALID_ARG.
+int sv_txresults_args(const sv_txresults* res) {
+  if (!res || res->struct_size < sizeof(sv_txresults) || !res->body_code) return SV_ERR_INVALID_ARG;
+  if (res->bad_cap && !res->bad_body) return SV_ERR_INVALID_ARG;
+  return SV_OK;
+}
+
+// ... and its roles and flags, once the twin's argument check has vouched for n_checks and n_bodies.
+int sv_txresults_check(const sv_txresults* res, size_t n_bodies, size_t n_checks) {
+  if (res->check_role)
+    for (size_t c = 0; c < n_checks; ++c)
+      if (res->check_role[c] > SV_TXROLE_OP) return SV_ERR_INVALID_ARG;
+  if (res->body_flags)
+    for (size_t t = 0; t < n_bodies; ++t)
+      if (res->body_flags[t] & ~(uint8_t)SV_TXBODY_SKIP_UNUSED) return SV_ERR_INVALID_ARG;
+  return SV_OK;
+}
+
+// The bad list of a host form, from body_code after the last chunk: global indices, ascending; *n_bad is exact
+// even where it exceeds bad_cap, and no entry at or past bad_cap is written.
+void sv_txresults_bad_list(const sv_txresults* res, size_t n_bodies) {
+  if (!res->bad_body && !res->n_bad) return;
+  uint64_t n = 0;
+  for (size_t t = 0; t < n_bodies; ++t) {
+    if (res->body_code[t] == SV_TXRESULT_OK) continue;
+    if (res->bad_body && n < res->bad_cap) res->bad_body[n] = (uint32_t)t;
+    ++n;
+  }
+  if (res->n_bad) *res->n_bad = n;
+}
+
+// txresult.h over host arrays: body_code and body_fail of every body, then the bad list.
+void sv_txresults_fold(const sv_txresults* res, const uint64_t* check_begin, const uint64_t* sig_begin,
+                       const uint8_t* check_ok, const uint64_t* check_used, size_t n_bodies, size_t n_checks,
+                       size_t n_sigs) {
+  const sv_txresult_in I{check_begin, sig_begin, check_ok, check_used, res->check_role, res->body_flags,
+                         n_bodies,    n_checks,  n_sigs};
+  for (size_t t = 0; t < n_bodies; ++t) {
+    uint32_t fail;
+    res->body_code[t] = sv_txresult_body(I, t, &fail);
+    if (res->body_fail) res->body_fail[t] = fail;
+  }
+  sv_txresults_bad_list(res, n_bodies);
+}
+
+namespace {
+// The three check arrays of a decide call on the CPU path: the caller's where it asked for them, else the call's own.
+struct DecideBufs {
+  std::vector<uint8_t> ok;
+  std::vector<uint32_t> weight;
+  std::vector<uint64_t> used;
+  uint8_t* pok;
+  uint32_t* pweight;
+  uint64_t* pused;
+  DecideBufs(const sv_txresults* res, size_t nc) {
+    if (!res->check_ok) ok.resize(nc + 1);
+    if (!res->check_weight) weight.resize(nc + 1);
+    if (!res->check_used) used.resize(nc + 1);
+    pok = res->check_ok ? res->check_ok : ok.data();
+    pweight = res->check_weight ? res->check_weight : weight.data();
+    pused = res->check_used ? res->check_used : used.data();
+  }
+};
+// (the twin's argument check only asks whether the three outputs are there)
+const uint64_t g_present = 0;
+}  // namespace
+
+int sv_ed25519_decide_txbodies_cpu(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                   const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                   const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig, size_t n_sigs,
+                                   const uint64_t* key_begin, const uint8_t* key, size_t n_keys, const sv_txchecks* ck,
+                                   const sv_txresults* res, uint8_t* digests, int threads) {
+  int rc = sv_txresults_args(res);
+  if (rc) return rc;
+  if ((rc = sv_txchecks_check(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, n_sigs,
+                              key_begin, key, n_keys, ck, (const uint8_t*)&g_present, (const uint32_t*)&g_present,
+                              &g_present)))
+    return rc;
+  const size_t nc = ck->n_checks;
+  if ((rc = sv_txresults_check(res, n_bodies, nc))) return rc;
+  DecideBufs b(res, nc);
+  if ((rc = sv_ed25519_check_txbodies_cpu(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint,
+                                          sig, n_sigs, key_begin, key, n_keys, ck, b.pok, b.pweight, b.pused, digests,
+                                          threads)))
+    return rc;
+  sv_txresults_fold(res, ck->check_begin, sig_begin, b.pok, b.pused, n_bodies, nc, n_sigs);
+  return SV_OK;
+}
+
+int sv_ed25519_decide_txbodies_accounts_cpu(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                            const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                            const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig,
+                                            size_t n_sigs, const sv_txaccounts* A, const sv_txresults* res,
+                                            uint8_t* digests, int threads) {
+  int rc = sv_txresults_args(res);
+  if (rc) return rc;
+  if ((rc = sv_txaccounts_check(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig,
+                                n_sigs, A, (const uint8_t*)&g_present, (const uint32_t*)&g_present, &g_present,
+                                nullptr)))
+    return rc;
+  const size_t nc = A->n_checks;
+  if ((rc = sv_txresults_check(res, n_bodies, nc))) return rc;
+  DecideBufs b(res, nc);
+  if ((rc = sv_ed25519_check_txbodies_accounts_cpu(network_id, bodies, body_off, body_len, body_kind, n_bodies,
+                                                   sig_begin, hint, sig, n_sigs, A, b.pok, b.pweight, b.pused, digests,
+                                                   threads)))
+    return rc;
+  sv_txresults_fold(res, A->check_begin, sig_begin, b.pok, b.pused, n_bodies, nc, n_sigs);
+  return SV_OK;
 }
 
 int sv_ed25519_verify_cpu(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, size_t msg_len) {
