@@ -679,8 +679,7 @@ inline int ensure_txpp(Device& D, size_t bytes) {
   return D.txpp.ensure(bytes);
 }
 
-// The payload tables of a check call on the device (all device pointers; nq == 0: none) and, after
-// ppair_run, its payload pairs for the check kernel.
+// The payload tables of a check call on the device (all device pointers; nq == 0: none).
 struct PayloadDev {
   const uint64_t* qb = nullptr;  // n_bodies + 1
   const uint8_t* key = nullptr;
@@ -688,17 +687,156 @@ struct PayloadDev {
   const uint8_t* len = nullptr;
   size_t nq = 0;
 };
-// Fill and verify the npp payload pairs counted by sv_launch_ppair_count (caller holds D.mu, device set, D.txpp
-// holds ppair_layout(npp)): the second, variable-length verify launch of a check call, on D.stream.
-inline int ppair_run(Device& D, const PayloadDev& pd, const uint64_t* d_sb, const void* d_hint, const void* d_sig,
-                     size_t m, size_t k, void* ws, void* pws, uint64_t* d_ppb, size_t npp, int path) {
+
+// ------------------------------------------------- the device sequence of the hinted and check forms
+// HintIn's device twin: the body, signature and key arguments of a device-resident call, or of a chunk's image.
+struct HintDev {
+  const uint8_t* nid;  // (host memory)
+  const void* bodies;
+  const uint64_t* off;
+  const uint32_t* len;
+  const uint8_t* kind;
+  size_t nb;
+  const uint64_t* sb;  // signatures of body t: [sb[t], sb[t + 1]) of m
+  const void* hint;
+  const void* sig;
+  size_t m;
+  const uint64_t* kb;  // candidate keys of body t: [kb[t], kb[t + 1]) of q (a by-account call: the expansion's)
+  const void* key;
+  size_t q;
+};
+inline HintDev hint_dev_of(const uint8_t* nid, const PairChunk& p, const uint8_t* d) {
+  return HintDev{nid, d + p.o_body, (const uint64_t*)(d + p.o_off), (const uint32_t*)(d + p.o_len), d + p.o_kind,
+                 p.b1 - p.b0, (const uint64_t*)(d + p.o_sb), d + p.o_hint, d + p.o_sig, p.s1 - p.s0,
+                 (const uint64_t*)(d + p.o_kb), d, p.k1 - p.k0};
+}
+// The check tables on the device.
+struct CheckTabs {
+  const uint8_t* sig_len = nullptr;  // per signature, or null: all 64
+  int clamp = 0;
+  const uint64_t* check_begin = nullptr;  // checks of body t
+  const int32_t* needed = nullptr;
+  size_t nc = 0;
+  const uint64_t* signer_begin = nullptr;  // signers of check c
+  const uint8_t* type = nullptr;
+  const uint32_t* weight = nullptr;
+  const uint32_t* key = nullptr;
+  size_t ng = 0;
+};
+// The device view of one call or chunk: the hinted forms have `h` and `digests`, the check forms everything.
+struct TxDev {
+  HintDev h;
+  void* digests;  // nb x 32 B: the contents hashes (tx_enqueue_hash)
+  CheckTabs c;
+  PayloadDev pl;
+};
+// The buffers the sequence writes, in one device buffer: the head -- ws, sv_pair_ws_bytes(k) | pair_begin, k + 1
+// words -- from its start and, with payload candidates, the tail -- pws, sv_ppair_ws_bytes(k) | ppair_begin, k + 1
+// words -- from o_tail, every section 16-byte aligned; h_cnt: the two pinned words the pair counts come back in.
+struct TxBufs {
+  void* ws;
+  uint64_t* pair_begin;
+  void* pws;
+  uint64_t* ppair_begin;
+  void* h_cnt;
+  static size_t head(size_t k) { return al16(sv_pair_ws_bytes(k)) + al16(8 * (k + 1)); }
+  static size_t tail(size_t k) { return al16(sv_ppair_ws_bytes(k)) + al16(8 * (k + 1)); }
+  static TxBufs at(void* base, size_t o_tail, size_t k, void* h_cnt) {
+    uint8_t* b = (uint8_t*)base;
+    return TxBufs{b, (uint64_t*)(b + al16(sv_pair_ws_bytes(k))), b + o_tail,
+                  (uint64_t*)(b + o_tail + al16(sv_ppair_ws_bytes(k))), h_cnt};
+  }
+};
+// What the check kernel writes per check and, for a decide call, what the result kernels read and write
+// (sv_launch_txresult; bad, bad_cap and n_bad: the device-resident form's only).
+struct ResultDev {
+  const uint8_t* role = nullptr;
+  const uint8_t* flags = nullptr;
+  uint8_t* code = nullptr;
+  uint32_t* fail = nullptr;
+  void* ws = nullptr;
+  uint32_t* bad = nullptr;
+  uint64_t bad_cap = 0;
+  uint64_t* n_bad = nullptr;
+};
+struct DecideDev {
+  uint8_t* ok;
+  uint32_t* weight;
+  uint64_t* used;
+  const ResultDev* res;  // a decide call's, or null
+};
+
+// The contents hashes of T's bodies, on `st`.
+inline int tx_enqueue_hash(const Device& D, const TxDev& T, hipStream_t st) {
+  const HintDev& h = T.h;
+  SV_HIP(sv_launch_txhash(D.grid * 8, h.nid, h.bodies, h.off, h.len, h.kind, h.nb, nullptr, 0, nullptr, T.digests, st));
+  return SV_OK;
+}
+
+// Enqueue-counts, on `st` (the contents hashes need not be there yet): the pair count and scan, the payload-pair
+// count and scan where the call has candidates, and both totals to B.h_cnt in one copy (the payload pairing's
+// total is the word behind the ed25519 pairing's).  The caller waits -- a chunk for its upload event, a device call
+// for its stream -- and reads the totals with tx_counted.
+inline int tx_enqueue_counts(const TxDev& T, const TxBufs& B, hipStream_t st) {
+  const HintDev& h = T.h;
+  SV_HIP(sv_launch_pair_count(h.sb, h.hint, h.sig, h.m, h.kb, h.key, h.q, h.nb, B.ws, B.pair_begin, st));
+  if (T.pl.nq)
+    SV_HIP(sv_launch_ppair_count(h.sb, h.hint, h.m, T.pl.qb, T.pl.key, T.pl.payload, T.pl.len, T.pl.nq, h.nb, B.ws,
+                                 B.pws, B.ppair_begin, st));
+  SV_HIP(hipMemcpyAsync(B.h_cnt, sv_pair_total(B.ws, h.nb), T.pl.nq ? 16 : 8, hipMemcpyDeviceToHost, st));
+  return SV_OK;
+}
+inline void tx_counted(const TxDev& T, const TxBufs& B, size_t* np, size_t* npp) {
+  *np = (size_t)((const uint64_t*)B.h_cnt)[0];
+  *npp = T.pl.nq ? (size_t)((const uint64_t*)B.h_cnt)[1] : 0;
+}
+
+// The np counted pairs on D.stream (caller holds D.mu, device set): the fill into pair_sig / pair_key and the
+// gathered arrays, and with `verdict` the verify launch over them (mode 0, 32-byte messages).
+inline int tx_enqueue_pairs(Device& D, const TxDev& T, const TxBufs& B, size_t np, uint32_t* pair_sig,
+                            uint32_t* pair_key, void* verdict, void* bitmap, int path) {
+  const HintDev& h = T.h;
+  int rc;
+  if ((rc = ensure_txpairs(D, np))) return rc;
+  SV_HIP(sv_launch_pair_fill(h.sb, h.hint, h.sig, h.m, h.kb, h.key, h.q, h.nb, B.ws, B.pair_begin, np, pair_sig,
+                             pair_key, D.txpk.p, D.txsg.p, D.txmsg.p, T.digests, D.stream));
+  if (!np || !verdict) return SV_OK;
+  return launch_locked(D, 0, path, D.txpk.p, D.txsg.p, D.txmsg.p, nullptr, nullptr, 32, np, verdict, bitmap,
+                       kt_mode() == 1);
+}
+
+// Enqueue-decide, on D.stream after the counts came back: the fill and the verify launch, the payload pairs' fill
+// and their variable-length verify launch (in D.txpp, ppair_layout(npp)), the check kernel and, with out.res, the
+// result kernels.  dv: verdicts (np, padded to 16) | pair_sig | pair_key (4 np each), sized by the caller.
+inline int tx_enqueue_decide(Device& D, const TxDev& T, const TxBufs& B, size_t np, size_t npp, uint8_t* dv,
+                             const DecideDev& out, int path) {
+  const HintDev& h = T.h;
+  const CheckTabs& c = T.c;
+  int rc;
+  uint32_t* d_ps = (uint32_t*)(dv + al16(np));
+  uint32_t* d_pk = d_ps + np;
+  if (npp && (rc = ensure_txpp(D, ppair_layout(npp).bytes))) return rc;
+  if ((rc = tx_enqueue_pairs(D, T, B, np, d_ps, d_pk, dv, nullptr, path))) return rc;
   const PPairBufs L = ppair_layout(npp);
   uint8_t* b = (uint8_t*)D.txpp.p;
-  SV_HIP(sv_launch_ppair_fill(d_sb, d_hint, d_sig, m, pd.qb, pd.key, pd.payload, pd.len, pd.nq, k, ws, pws, d_ppb, npp,
-                              (uint32_t*)(b + L.o_idx), (uint32_t*)(b + L.o_idx) + npp, b + L.o_key, b + L.o_sig,
-                              b + L.o_msg, (uint64_t*)(b + L.o_off), (uint32_t*)(b + L.o_len), D.stream));
-  return launch_locked(D, 1, path, b + L.o_key, b + L.o_sig, b + L.o_msg, (const uint64_t*)(b + L.o_off),
-                       (const uint32_t*)(b + L.o_len), 0, npp, b, nullptr);
+  uint32_t* d_pps = (uint32_t*)(b + L.o_idx);
+  if (npp) {
+    SV_HIP(sv_launch_ppair_fill(h.sb, h.hint, h.sig, h.m, T.pl.qb, T.pl.key, T.pl.payload, T.pl.len, T.pl.nq, h.nb, B.ws,
+                                B.pws, B.ppair_begin, npp, d_pps, d_pps + npp, b + L.o_key, b + L.o_sig, b + L.o_msg,
+                                (uint64_t*)(b + L.o_off), (uint32_t*)(b + L.o_len), D.stream));
+    if ((rc = launch_locked(D, 1, path, b + L.o_key, b + L.o_sig, b + L.o_msg, (const uint64_t*)(b + L.o_off),
+                            (const uint32_t*)(b + L.o_len), 0, npp, b, nullptr)))
+      return rc;
+  }
+  SV_HIP(sv_launch_txcheck_payload(h.sb, h.hint, h.sig, c.sig_len, h.m, h.kb, h.key, h.q, h.nb, B.pair_begin, d_ps, d_pk,
+                                   dv, np, T.digests, c.check_begin, c.needed, c.nc, c.signer_begin, c.type, c.weight,
+                                   c.key, c.ng, c.clamp, B.ppair_begin, d_pps, d_pps + npp, b, npp, T.pl.qb, T.pl.nq,
+                                   out.ok, out.weight, out.used, D.stream));
+  if (const ResultDev* R = out.res) {
+    const sv_txresult_in I{c.check_begin, h.sb, out.ok, out.used, R->role, R->flags, h.nb, c.nc, h.m};
+    SV_HIP(sv_launch_txresult(&I, R->code, R->fail, R->ws, R->bad, R->bad_cap, R->n_bad, D.stream));
+  }
+  return SV_OK;
 }
 
 // Where a slice's pairs go: the caller's arrays (one slot), or vectors of the
@@ -778,28 +916,22 @@ inline int hinted_slice_locked(Device& D, const HintIn& in, size_t B0, size_t B1
     const PairChunk& c = plan[ci];
     Stage& s = D.st[ci & 1];
     if ((rc = pair_drain(s, pend[ci & 1], sink, pair_begin, digests))) return rc;
-    const size_t m = c.s1 - c.s0, q = c.k1 - c.k0, k = c.b1 - c.b0;
-    const size_t wsb = al16(sv_pair_ws_bytes(k));
-    if ((rc = s.h_in.ensure(c.bytes)) || (rc = s.d_in.ensure(c.bytes)) || (rc = s.d_pair.ensure(wsb + 8 * (k + 1))) ||
+    const size_t k = c.b1 - c.b0;
+    if ((rc = s.h_in.ensure(c.bytes)) || (rc = s.d_in.ensure(c.bytes)) || (rc = s.d_pair.ensure(TxBufs::head(k))) ||
         (rc = s.d_keys.ensure(32 * k)) || (rc = s.h_cnt.ensure(64)))
       return rc;
     uint8_t* hp = (uint8_t*)s.h_in.p;
     uint8_t* d = (uint8_t*)s.d_in.p;
     pair_pack(in, c, hp);
     if ((rc = upload_image(D, d, hp, c.bytes, up_s))) return rc;
-    const uint64_t* d_sb = (const uint64_t*)(d + c.o_sb);
-    const uint64_t* d_kb = (const uint64_t*)(d + c.o_kb);
-    const uint64_t* d_off = (const uint64_t*)(d + c.o_off);
-    const uint32_t* d_len = (const uint32_t*)(d + c.o_len);
-    uint64_t* d_pb = (uint64_t*)((uint8_t*)s.d_pair.p + wsb);
-    if (!overflow)
-      SV_HIP(sv_launch_txhash(D.grid * 8, in.nid, d + c.o_body, d_off, d_len, d + c.o_kind, k, nullptr, 0, nullptr,
-                              s.d_keys.p, up_s));
-    SV_HIP(sv_launch_pair_count(d_sb, d + c.o_hint, d + c.o_sig, m, d_kb, d, q, k, s.d_pair.p, d_pb, up_s));
-    SV_HIP(hipMemcpyAsync(s.h_cnt.p, sv_pair_total(s.d_pair.p, k), 8, hipMemcpyDeviceToHost, up_s));
+    const TxDev T{hint_dev_of(in.nid, c, d), s.d_keys.p};
+    const TxBufs B = TxBufs::at(s.d_pair.p, TxBufs::head(k), k, s.h_cnt.p);  // (no payload candidates: no tail)
+    if (!overflow && (rc = tx_enqueue_hash(D, T, up_s))) return rc;
+    if ((rc = tx_enqueue_counts(T, B, up_s))) return rc;
     SV_HIP(hipEventRecord(s.up, up_s));
     SV_HIP(hipEventSynchronize(s.up));
-    const size_t np = (size_t)*(const uint64_t*)s.h_cnt.p;
+    size_t np, npp;
+    tx_counted(T, B, &np, &npp);
     const size_t base = total;
     total += np;
     if (overflow || !sink.room(total)) {
@@ -808,14 +940,9 @@ inline int hinted_slice_locked(Device& D, const HintIn& in, size_t B0, size_t B1
     }
     if (!single) SV_HIP(hipStreamWaitEvent(D.stream, s.up, 0));
     const size_t o_idx = al16(np), o_pb = o_idx + al16(8 * np), o_dig = o_pb + al16(8 * k);
-    if ((rc = ensure_txpairs(D, np)) || (rc = s.d_verdict.ensure(o_pb + 16)) || (rc = s.h_out.ensure(o_dig + 32 * k)))
-      return rc;
+    if ((rc = s.d_verdict.ensure(o_pb + 16)) || (rc = s.h_out.ensure(o_dig + 32 * k))) return rc;
     uint8_t* dv = (uint8_t*)s.d_verdict.p;
-    SV_HIP(sv_launch_pair_fill(d_sb, d + c.o_hint, d + c.o_sig, m, d_kb, d, q, k, s.d_pair.p, d_pb, np,
-                               (uint32_t*)(dv + o_idx), (uint32_t*)(dv + o_idx) + np, D.txpk.p, D.txsg.p, D.txmsg.p,
-                               s.d_keys.p, D.stream));
-    if (np && (rc = launch_locked(D, 0, path, D.txpk.p, D.txsg.p, D.txmsg.p, nullptr, nullptr, 32, np, dv, nullptr,
-                                  kt_mode() == 1)))
+    if ((rc = tx_enqueue_pairs(D, T, B, np, (uint32_t*)(dv + o_idx), (uint32_t*)(dv + o_idx) + np, dv, nullptr, path)))
       return rc;
     if (!single) {
       SV_HIP(hipEventRecord(s.done, D.stream));
@@ -823,7 +950,7 @@ inline int hinted_slice_locked(Device& D, const HintIn& in, size_t B0, size_t B1
     }
     uint8_t* ho = (uint8_t*)s.h_out.p;
     if (np) SV_HIP(hipMemcpyAsync(ho, dv, o_idx + 8 * np, hipMemcpyDeviceToHost, down_s));
-    SV_HIP(hipMemcpyAsync(ho + o_pb, d_pb, 8 * k, hipMemcpyDeviceToHost, down_s));
+    SV_HIP(hipMemcpyAsync(ho + o_pb, B.pair_begin, 8 * k, hipMemcpyDeviceToHost, down_s));
     if (digests) SV_HIP(hipMemcpyAsync(ho + o_dig, s.d_keys.p, 32 * k, hipMemcpyDeviceToHost, down_s));
     SV_HIP(hipEventRecord(s.down, down_s));
     pend[ci & 1].busy = true;
@@ -890,15 +1017,10 @@ inline void result_pack(const ResultOut* res, const ResultBufs& b, size_t c0, si
   if (res->role && nc) std::memcpy(h + b.o_role, res->role + c0, nc);
   if (res->flags && k) std::memcpy(h + b.o_flag, res->flags + b0, k);
 }
-// The result kernel behind the chunk's check kernel, on the same stream: d the chunk's image, dv its s.d_verdict
-// with the check arrays at o_res (used | weight | ok).
-inline int result_launch(const ResultOut* res, const ResultBufs& b, const uint8_t* d, uint8_t* dv, size_t o_res,
-                         const uint64_t* d_cb, const uint64_t* d_sb, size_t k, size_t nc, size_t m, hipStream_t st) {
-  const sv_txresult_in I{d_cb, d_sb, dv + o_res + 12 * nc, (const uint64_t*)(dv + o_res),
-                         res->role ? d + b.o_role : nullptr, res->flags ? d + b.o_flag : nullptr, k, nc, m};
-  SV_HIP(sv_launch_txresult(&I, dv + b.o_code, res->fail ? (uint32_t*)(dv + b.o_fail) : nullptr, dv + b.o_ws, nullptr, 0,
-                            nullptr, st));
-  return SV_OK;
+// What the result kernel behind the chunk's check kernel reads and writes: d the chunk's image, dv its s.d_verdict.
+inline ResultDev result_dev(const ResultOut& res, const ResultBufs& b, const uint8_t* d, uint8_t* dv) {
+  return ResultDev{res.role ? d + b.o_role : nullptr, res.flags ? d + b.o_flag : nullptr, dv + b.o_code,
+                   res.fail ? (uint32_t*)(dv + b.o_fail) : nullptr, dv + b.o_ws};
 }
 
 // A chunk's results in its pinned slot: check_used (8 nc) | check_weight (4 nc)
@@ -929,97 +1051,65 @@ inline int check_drain(Stage& s, CheckPending& pd, const CheckOut& out) {
   return SV_OK;
 }
 
-// Bodies [B0, B1) with their signatures, keys and checks on one slot (caller
-// holds D.mu, device set): hinted_slice_locked's sequence per chunk -- pack ->
-// H2D -> contents hashes -> count and scan -> the pair count back (the one
-// wait) -> fill -> verify launch -- followed by the check kernel on the same
-// stream; only the three check arrays and the digests come back.  The pairs
-// live in the stage's device buffer, sized from the count.
-inline int check_slice_locked(Device& D, const CheckIn& in, size_t B0, size_t B1, int clamp, const CheckOut& out,
-                              int path) {
+// The chunk loop of the check forms.  Bodies [B0, B1) with their signatures and checks on one slot (caller holds
+// D.mu, device set).  Per chunk: pack -> H2D -> contents hashes -> the form's tables -> pair counts and scans ->
+// the counts back (the one wait: it covers the upload, the hash, the tables and the pairing, on the upload
+// stream, not a verify) -> fill -> verify launches -> check kernel (-> result kernel), over the slot's two
+// staging slots, so chunk c + 1 is packed while chunk c verifies; only the check arrays, the digests and a decide
+// call's codes come back.  The pairs live in the stage's d_verdict, sized from the count.  `src` is the form (src.in.h: its HintIn):
+//   plan(B0, B1)              its chunks (each with .p, the hinted image, and .c0 / .c1, its checks)
+//   begin(D, single)          once, ahead of the first chunk
+//   prepare(s, c, &bytes, &nq) the chunk's image size and payload candidates; sizes what else of the stage it uses
+//   pack(c, hp)               the image
+//   tables(D, s, c, d, st, T) enqueues on `st` what makes the chunk's key, check and payload tables, and names
+//                             them in T (T.h, the chunk's hinted image, is filled in)
+template <class Src>
+inline int check_chunks_locked(Device& D, Src& src, size_t B0, size_t B1, const CheckOut& out, int path) {
   int rc;
-  // (a signer is 9 bytes of image against a signature's 68: eight staging chunks of them bound a chunk, so a
-  // multisig batch is not cut many times more often than its signatures would cut it -- every chunk waits once
-  // for its pair count)
-  const std::vector<CheckChunk> plan = check_plan(in, B0, B1, stage_chunk(), stage_chunk(), txbody_chunk_bytes(),
-                                                  stage_chunk(), 8 * stage_chunk());
+  const auto plan = src.plan(B0, B1);
   if (plan.empty()) return SV_OK;
   const bool single = plan.size() == 1;
   hipStream_t up_s = single ? D.stream : D.h2d, down_s = single ? D.stream : D.d2h;
+  if ((rc = src.begin(D, single))) return rc;
   CheckPending pend[2];
   for (size_t ci = 0; ci < plan.size(); ++ci) {
-    const CheckChunk& c = plan[ci];
+    const auto& c = plan[ci];
     Stage& s = D.st[ci & 1];
     if ((rc = check_drain(s, pend[ci & 1], out))) return rc;
-    const size_t m = c.p.s1 - c.p.s0, q = c.p.k1 - c.p.k0, k = c.p.b1 - c.p.b0;
-    const PayloadChunk pc = payload_chunk(in, c);
-    const size_t nc = c.c1 - c.c0, ng = c.g1 - c.g0, nq = pc.q1 - pc.q0;
-    const size_t wsb = al16(sv_pair_ws_bytes(k)), pbb = al16(8 * (k + 1)), pwsb = al16(sv_ppair_ws_bytes(k));
-    const size_t img = result_layout(out.res, pc.bytes, nc, k, 0).img;
+    const size_t k = c.p.b1 - c.p.b0, nc = c.c1 - c.c0;
+    size_t bytes, nq;
+    if ((rc = src.prepare(s, c, &bytes, &nq))) return rc;
+    const size_t img = result_layout(out.res, bytes, nc, k, 0).img;
     if ((rc = s.h_in.ensure(img)) || (rc = s.d_in.ensure(img)) ||
-        (rc = s.d_pair.ensure(wsb + pbb + (nq ? pwsb + pbb : 0))) ||
-        (rc = s.d_keys.ensure(32 * k)) || (rc = s.h_cnt.ensure(64)))
+        (rc = s.d_pair.ensure(TxBufs::head(k) + (nq ? TxBufs::tail(k) : 0))) || (rc = s.d_keys.ensure(32 * k)) ||
+        (rc = s.h_cnt.ensure(64)))
       return rc;
+    const TxBufs B = TxBufs::at(s.d_pair.p, TxBufs::head(k), k, s.h_cnt.p);
     uint8_t* hp = (uint8_t*)s.h_in.p;
     uint8_t* d = (uint8_t*)s.d_in.p;
-    check_pack(in, c, hp);
-    payload_pack(in, c, pc, hp);
-    result_pack(out.res, result_layout(out.res, pc.bytes, nc, k, 0), c.c0, nc, c.p.b0, k, hp);
+    src.pack(c, hp);
+    result_pack(out.res, result_layout(out.res, bytes, nc, k, 0), c.c0, nc, c.p.b0, k, hp);
     if ((rc = upload_image(D, d, hp, img, up_s))) return rc;
-    const uint64_t* d_sb = (const uint64_t*)(d + c.p.o_sb);
-    const uint64_t* d_kb = (const uint64_t*)(d + c.p.o_kb);
-    uint64_t* d_pb = (uint64_t*)((uint8_t*)s.d_pair.p + wsb);
-    SV_HIP(sv_launch_txhash(D.grid * 8, in.h.nid, d + c.p.o_body, (const uint64_t*)(d + c.p.o_off),
-                            (const uint32_t*)(d + c.p.o_len), d + c.p.o_kind, k, nullptr, 0, nullptr, s.d_keys.p,
-                            up_s));
-    SV_HIP(sv_launch_pair_count(d_sb, d + c.p.o_hint, d + c.p.o_sig, m, d_kb, d, q, k, s.d_pair.p, d_pb, up_s));
-    // the chunk's payload candidates: their pairing beside it, both counts in the one copy
-    PayloadDev pl;
-    void* d_pws = (uint8_t*)s.d_pair.p + wsb + pbb;
-    uint64_t* d_ppb = (uint64_t*)((uint8_t*)s.d_pair.p + wsb + pbb + pwsb);
-    if (nq) {
-      pl.qb = (const uint64_t*)(d + pc.o_qb);
-      pl.key = d + pc.o_qk;
-      pl.payload = d + pc.o_qp;
-      pl.len = d + pc.o_ql;
-      pl.nq = nq;
-      SV_HIP(sv_launch_ppair_count(d_sb, d + c.p.o_hint, m, pl.qb, pl.key, pl.payload, pl.len, nq, k, s.d_pair.p, d_pws,
-                                   d_ppb, up_s));
-    }
-    SV_HIP(hipMemcpyAsync(s.h_cnt.p, sv_pair_total(s.d_pair.p, k), nq ? 16 : 8, hipMemcpyDeviceToHost, up_s));
+    TxDev T{hint_dev_of(src.in.h.nid, c.p, d), s.d_keys.p};
+    if ((rc = tx_enqueue_hash(D, T, up_s))) return rc;
+    if ((rc = src.tables(D, s, c, d, up_s, &T))) return rc;
+    if ((rc = tx_enqueue_counts(T, B, up_s))) return rc;
     SV_HIP(hipEventRecord(s.up, up_s));
     SV_HIP(hipEventSynchronize(s.up));
-    const size_t np = (size_t)*(const uint64_t*)s.h_cnt.p;
-    const size_t npp = nq ? (size_t)((const uint64_t*)s.h_cnt.p)[1] : 0;
+    size_t np, npp;
+    tx_counted(T, B, &np, &npp);
     if (!single) SV_HIP(hipStreamWaitEvent(D.stream, s.up, 0));
-    if (npp && (rc = ensure_txpp(D, ppair_layout(npp).bytes))) return rc;
     // verdicts (np, padded) | pair_sig, pair_key (4 np each, padded) | used | weight | ok
-    const size_t o_idx = al16(np), o_res = o_idx + al16(8 * np), o_dig = al16(13 * nc);
-    const ResultBufs RB = result_layout(out.res, pc.bytes, nc, k, o_res + 13 * nc);
-    if ((rc = ensure_txpairs(D, np)) || (rc = s.d_verdict.ensure(RB.dev + 16)) ||
+    const size_t o_res = al16(np) + al16(8 * np), o_dig = al16(13 * nc);
+    const ResultBufs RB = result_layout(out.res, bytes, nc, k, o_res + 13 * nc);
+    if ((rc = s.d_verdict.ensure(RB.dev + 16)) ||
         (rc = s.h_out.ensure(o_dig + 32 * k + (out.res ? al16(k) + 4 * k : 0))))
       return rc;
     uint8_t* dv = (uint8_t*)s.d_verdict.p;
-    uint32_t* d_ps = (uint32_t*)(dv + o_idx);
-    uint32_t* d_pk = d_ps + np;
-    SV_HIP(sv_launch_pair_fill(d_sb, d + c.p.o_hint, d + c.p.o_sig, m, d_kb, d, q, k, s.d_pair.p, d_pb, np, d_ps, d_pk,
-                               D.txpk.p, D.txsg.p, D.txmsg.p, s.d_keys.p, D.stream));
-    if (np && (rc = launch_locked(D, 0, path, D.txpk.p, D.txsg.p, D.txmsg.p, nullptr, nullptr, 32, np, dv, nullptr,
-                                  kt_mode() == 1)))
-      return rc;
-    if (npp && (rc = ppair_run(D, pl, d_sb, d + c.p.o_hint, d + c.p.o_sig, m, k, s.d_pair.p, d_pws, d_ppb, npp, path)))
-      return rc;
-    const PPairBufs L = ppair_layout(npp);
-    const uint8_t* dpp = (const uint8_t*)D.txpp.p;
-    SV_HIP(sv_launch_txcheck_payload(
-        d_sb, d + c.p.o_hint, d + c.p.o_sig, in.sig_len ? d + c.o_sl : nullptr, m, d_kb, d, q, k, d_pb, d_ps, d_pk, dv,
-        np, s.d_keys.p, (const uint64_t*)(d + c.o_cb), (const int32_t*)(d + c.o_need), nc,
-        (const uint64_t*)(d + c.o_gb), d + c.o_gt, (const uint32_t*)(d + c.o_gw), (const uint32_t*)(d + c.o_gk), ng,
-        clamp, d_ppb, (const uint32_t*)(dpp + L.o_idx), (const uint32_t*)(dpp + L.o_idx) + npp, dpp, npp, pl.qb, nq,
-        dv + o_res + 12 * nc, (uint32_t*)(dv + o_res + 8 * nc), (uint64_t*)(dv + o_res), D.stream));
-    if (out.res &&
-        (rc = result_launch(out.res, RB, d, dv, o_res, (const uint64_t*)(d + c.o_cb), d_sb, k, nc, m, D.stream)))
-      return rc;
+    const ResultDev R = out.res ? result_dev(*out.res, RB, d, dv) : ResultDev();
+    const DecideDev dd{dv + o_res + 12 * nc, (uint32_t*)(dv + o_res + 8 * nc), (uint64_t*)(dv + o_res),
+                       out.res ? &R : nullptr};
+    if ((rc = tx_enqueue_decide(D, T, B, np, npp, dv, dd, path))) return rc;
     if (!single) {
       SV_HIP(hipEventRecord(s.done, D.stream));
       SV_HIP(hipStreamWaitEvent(D.d2h, s.done, 0));
@@ -1032,15 +1122,53 @@ inline int check_slice_locked(Device& D, const CheckIn& in, size_t B0, size_t B1
                             hipMemcpyDeviceToHost, down_s));
     SV_HIP(hipEventRecord(s.down, down_s));
     pend[ci & 1].busy = true;
-    pend[ci & 1].c = c;
+    pend[ci & 1].c.p = c.p;
+    pend[ci & 1].c.c0 = c.c0;
+    pend[ci & 1].c.c1 = c.c1;
   }
   for (int i = 0; i < 2; ++i)
     if ((rc = check_drain(D.st[i], pend[i], out))) return rc;
   return SV_OK;
 }
 
+// The explicit form: the chunk's tables are sections of its image.
+struct CheckSrc {
+  const CheckIn& in;
+  int clamp;
+  PayloadChunk pc{};
+  // (a signer is 9 bytes of image against a signature's 68: eight staging chunks of them bound a chunk, so a
+  // multisig batch is not cut many times more often than its signatures would cut it -- every chunk waits once
+  // for its pair count)
+  std::vector<CheckChunk> plan(size_t B0, size_t B1) const {
+    return check_plan(in, B0, B1, stage_chunk(), stage_chunk(), txbody_chunk_bytes(), stage_chunk(),
+                      8 * stage_chunk());
+  }
+  int begin(Device&, bool) { return SV_OK; }
+  int prepare(Stage&, const CheckChunk& c, size_t* bytes, size_t* nq) {
+    pc = payload_chunk(in, c);
+    *bytes = pc.bytes;
+    *nq = pc.q1 - pc.q0;
+    return SV_OK;
+  }
+  void pack(const CheckChunk& c, uint8_t* hp) const {
+    check_pack(in, c, hp);
+    payload_pack(in, c, pc, hp);
+  }
+  int tables(Device&, Stage&, const CheckChunk& c, const uint8_t* d, hipStream_t, TxDev* T) const {
+    T->c = CheckTabs{in.sig_len ? d + c.o_sl : nullptr, clamp, (const uint64_t*)(d + c.o_cb),
+                     (const int32_t*)(d + c.o_need), c.c1 - c.c0, (const uint64_t*)(d + c.o_gb), d + c.o_gt,
+                     (const uint32_t*)(d + c.o_gw), (const uint32_t*)(d + c.o_gk), c.g1 - c.g0};
+    if (const size_t nq = pc.q1 - pc.q0)
+      T->pl = PayloadDev{(const uint64_t*)(d + pc.o_qb), d + pc.o_qk, d + pc.o_qp, d + pc.o_ql, nq};
+    return SV_OK;
+  }
+};
+
 inline int check_slice(Device& D, const CheckIn& in, size_t B0, size_t B1, int clamp, const CheckOut& out, int path) {
-  return with_slot(D, [&] { return check_slice_locked(D, in, B0, B1, clamp, out, path); });
+  return with_slot(D, [&] {
+    CheckSrc src{in, clamp};
+    return check_chunks_locked(D, src, B0, B1, out, path);
+  });
 }
 
 // ------------------------------------------------- checks by account
@@ -1088,6 +1216,15 @@ inline sv_acct_out acct_out(const AcctBufs& L, uint8_t* head, uint8_t* rows, siz
   O.nq = nq;
   O.ng = ng;
   return O;
+}
+// ... as the key, check and payload tables of the device sequence, with what the caller keeps of the check tables
+inline void acct_tables(const sv_acct_out& O, const uint8_t* sig_len, int clamp, const uint64_t* check_begin,
+                        size_t nc, TxDev* T) {
+  T->h.kb = O.key_begin;
+  T->h.key = O.key;
+  T->h.q = O.nk;
+  T->c = CheckTabs{sig_len, clamp, check_begin, O.check_needed, nc, O.signer_begin, O.gtype, O.gweight, O.gkey, O.ng};
+  if (O.nq) T->pl = PayloadDev{O.pkey_begin, O.pkey, O.ppay, O.plen, O.nq};
 }
 
 // The account table of a host call in D.txatab: key (32 na) | signer keys (32 ns) | payload rows (64 np) |
@@ -1153,128 +1290,56 @@ inline int acct_table_upload(Device& D, const sv_txaccounts& A, sv_acct_tab* T, 
   return SV_OK;
 }
 
-// Bodies [B0, B1) with their signatures, account entries and checks on one slot (caller holds D.mu, device set):
-// the account table up once, then check_slice_locked's sequence per chunk with the expansion kernels between the
-// upload and the pairing -- pack -> H2D -> contents hashes -> count, scan, begin, rows, signers (the row counts
-// are the planner's: no wait) -> pair count and scan -> the pair count back (the one wait) -> fill -> verify
-// launch -> check kernel.  A chunk's explicit tables live in the stage's d_acct.
-inline int acct_slice_locked(Device& D, const AcctIn& in, const sv_txaccounts& A, size_t B0, size_t B1, int clamp,
-                             const CheckOut& out, int path) {
-  int rc;
-  const std::vector<AcctChunk> plan = acct_plan(in, B0, B1, stage_chunk(), stage_chunk(), txbody_chunk_bytes(),
-                                                stage_chunk(), 8 * stage_chunk());
-  if (plan.empty()) return SV_OK;
-  const bool single = plan.size() == 1;
-  hipStream_t up_s = single ? D.stream : D.h2d, down_s = single ? D.stream : D.d2h;
-  sv_acct_tab T;
+// The by-account form of check_chunks_locked: the account table up once, then per chunk the expansion kernels
+// between the contents hashes and the pairing -- count, scan, begin, rows, signers (the row counts are the
+// planner's: no wait).  A chunk's explicit tables live in the stage's d_acct.
+struct AcctSrc {
+  const AcctIn& in;
+  const sv_txaccounts& A;
+  int clamp;
+  sv_acct_tab tab{};
   const void* tab_ws = nullptr;
-  if ((rc = acct_table_upload(D, A, &T, &tab_ws))) return rc;
-  if (!single) {
-    SV_HIP(hipEventRecord(D.dep_in, D.stream));
-    SV_HIP(hipStreamWaitEvent(D.h2d, D.dep_in, 0));
+  AcctBufs L{};
+  std::vector<AcctChunk> plan(size_t B0, size_t B1) const {
+    return acct_plan(in, B0, B1, stage_chunk(), stage_chunk(), txbody_chunk_bytes(), stage_chunk(), 8 * stage_chunk());
   }
-  CheckPending pend[2];
-  for (size_t ci = 0; ci < plan.size(); ++ci) {
-    const AcctChunk& c = plan[ci];
-    Stage& s = D.st[ci & 1];
-    if ((rc = check_drain(s, pend[ci & 1], out))) return rc;
-    const size_t m = c.p.s1 - c.p.s0, k = c.p.b1 - c.p.b0, ne = c.e1 - c.e0, nc = c.c1 - c.c0;
-    const size_t q = c.nk, nq = c.nq, ng = c.ng;
-    const size_t wsb = al16(sv_pair_ws_bytes(k)), pbb = al16(8 * (k + 1)), pwsb = al16(sv_ppair_ws_bytes(k));
-    const AcctBufs L = acct_layout(sv_acct_ws_bytes(k, ne, nc), k, nc, false, q, nq, ng);
-    const size_t img = result_layout(out.res, c.bytes, nc, k, 0).img;
-    if ((rc = s.h_in.ensure(img)) || (rc = s.d_in.ensure(img)) || (rc = s.d_acct.ensure(L.bytes)) ||
-        (rc = s.d_pair.ensure(wsb + pbb + (nq ? pwsb + pbb : 0))) || (rc = s.d_keys.ensure(32 * k)) ||
-        (rc = s.h_cnt.ensure(64)))
-      return rc;
-    uint8_t* hp = (uint8_t*)s.h_in.p;
-    uint8_t* d = (uint8_t*)s.d_in.p;
-    uint8_t* da = (uint8_t*)s.d_acct.p;
-    acct_pack(in, c, hp);
-    result_pack(out.res, result_layout(out.res, c.bytes, nc, k, 0), c.c0, nc, c.p.b0, k, hp);
-    if ((rc = upload_image(D, d, hp, img, up_s))) return rc;
-    const uint64_t* d_sb = (const uint64_t*)(d + c.p.o_sb);
-    uint64_t* d_pb = (uint64_t*)((uint8_t*)s.d_pair.p + wsb);
-    SV_HIP(sv_launch_txhash(D.grid * 8, in.h.nid, d + c.p.o_body, (const uint64_t*)(d + c.p.o_off),
-                            (const uint32_t*)(d + c.p.o_len), d + c.p.o_kind, k, nullptr, 0, nullptr, s.d_keys.p,
-                            up_s));
-    // the chunk's explicit tables from the table and the chunk's references
-    const sv_acct_use U{(const uint64_t*)(d + c.o_eb), (const uint32_t*)(d + c.o_ea), (const uint64_t*)(d + c.o_cb),
-                        (const uint32_t*)(d + c.o_ca), d + c.o_lvl, (const int32_t*)(d + c.o_need), k, ne, nc};
-    const sv_acct_out O = acct_out(L, da, da, q, nq, ng);
-    SV_HIP(sv_launch_acct_count(&T, tab_ws, &U, &O, da, up_s));
-    SV_HIP(sv_launch_acct_fill(&T, tab_ws, &U, &O, da, up_s));
-    const uint64_t* d_kb = O.key_begin;
-    SV_HIP(sv_launch_pair_count(d_sb, d + c.p.o_hint, d + c.p.o_sig, m, d_kb, O.key, q, k, s.d_pair.p, d_pb, up_s));
-    PayloadDev pl;
-    void* d_pws = (uint8_t*)s.d_pair.p + wsb + pbb;
-    uint64_t* d_ppb = (uint64_t*)((uint8_t*)s.d_pair.p + wsb + pbb + pwsb);
-    if (nq) {
-      pl.qb = O.pkey_begin;
-      pl.key = O.pkey;
-      pl.payload = O.ppay;
-      pl.len = O.plen;
-      pl.nq = nq;
-      SV_HIP(sv_launch_ppair_count(d_sb, d + c.p.o_hint, m, pl.qb, pl.key, pl.payload, pl.len, nq, k, s.d_pair.p, d_pws,
-                                   d_ppb, up_s));
-    }
-    SV_HIP(hipMemcpyAsync(s.h_cnt.p, sv_pair_total(s.d_pair.p, k), nq ? 16 : 8, hipMemcpyDeviceToHost, up_s));
-    SV_HIP(hipEventRecord(s.up, up_s));
-    SV_HIP(hipEventSynchronize(s.up));
-    const size_t np = (size_t)*(const uint64_t*)s.h_cnt.p;
-    const size_t npp = nq ? (size_t)((const uint64_t*)s.h_cnt.p)[1] : 0;
-    if (!single) SV_HIP(hipStreamWaitEvent(D.stream, s.up, 0));
-    if (npp && (rc = ensure_txpp(D, ppair_layout(npp).bytes))) return rc;
-    // verdicts (np, padded) | pair_sig, pair_key (4 np each, padded) | used | weight | ok
-    const size_t o_idx = al16(np), o_res = o_idx + al16(8 * np), o_dig = al16(13 * nc);
-    const ResultBufs RB = result_layout(out.res, c.bytes, nc, k, o_res + 13 * nc);
-    if ((rc = ensure_txpairs(D, np)) || (rc = s.d_verdict.ensure(RB.dev + 16)) ||
-        (rc = s.h_out.ensure(o_dig + 32 * k + (out.res ? al16(k) + 4 * k : 0))))
-      return rc;
-    uint8_t* dv = (uint8_t*)s.d_verdict.p;
-    uint32_t* d_ps = (uint32_t*)(dv + o_idx);
-    uint32_t* d_pk = d_ps + np;
-    SV_HIP(sv_launch_pair_fill(d_sb, d + c.p.o_hint, d + c.p.o_sig, m, d_kb, O.key, q, k, s.d_pair.p, d_pb, np, d_ps,
-                               d_pk, D.txpk.p, D.txsg.p, D.txmsg.p, s.d_keys.p, D.stream));
-    if (np && (rc = launch_locked(D, 0, path, D.txpk.p, D.txsg.p, D.txmsg.p, nullptr, nullptr, 32, np, dv, nullptr,
-                                  kt_mode() == 1)))
-      return rc;
-    if (npp && (rc = ppair_run(D, pl, d_sb, d + c.p.o_hint, d + c.p.o_sig, m, k, s.d_pair.p, d_pws, d_ppb, npp, path)))
-      return rc;
-    const PPairBufs PL = ppair_layout(npp);
-    const uint8_t* dpp = (const uint8_t*)D.txpp.p;
-    SV_HIP(sv_launch_txcheck_payload(
-        d_sb, d + c.p.o_hint, d + c.p.o_sig, in.sig_len ? d + c.o_sl : nullptr, m, d_kb, O.key, q, k, d_pb, d_ps, d_pk,
-        dv, np, s.d_keys.p, (const uint64_t*)(d + c.o_cb), O.check_needed, nc, O.signer_begin, O.gtype, O.gweight,
-        O.gkey, ng, clamp, d_ppb, (const uint32_t*)(dpp + PL.o_idx), (const uint32_t*)(dpp + PL.o_idx) + npp, dpp, npp,
-        pl.qb, nq, dv + o_res + 12 * nc, (uint32_t*)(dv + o_res + 8 * nc), (uint64_t*)(dv + o_res), D.stream));
-    if (out.res &&
-        (rc = result_launch(out.res, RB, d, dv, o_res, (const uint64_t*)(d + c.o_cb), d_sb, k, nc, m, D.stream)))
-      return rc;
+  int begin(Device& D, bool single) {
+    int rc;
+    if ((rc = acct_table_upload(D, A, &tab, &tab_ws))) return rc;
     if (!single) {
-      SV_HIP(hipEventRecord(s.done, D.stream));
-      SV_HIP(hipStreamWaitEvent(D.d2h, s.done, 0));
+      SV_HIP(hipEventRecord(D.dep_in, D.stream));
+      SV_HIP(hipStreamWaitEvent(D.h2d, D.dep_in, 0));
     }
-    uint8_t* ho = (uint8_t*)s.h_out.p;
-    if (nc && check_arrays_wanted(out)) SV_HIP(hipMemcpyAsync(ho, dv + o_res, 13 * nc, hipMemcpyDeviceToHost, down_s));
-    if (out.digests) SV_HIP(hipMemcpyAsync(ho + o_dig, s.d_keys.p, 32 * k, hipMemcpyDeviceToHost, down_s));
-    if (out.res)
-      SV_HIP(hipMemcpyAsync(ho + o_dig + 32 * k, dv + RB.o_code, al16(k) + (out.res->fail ? 4 * k : 0),
-                            hipMemcpyDeviceToHost, down_s));
-    SV_HIP(hipEventRecord(s.down, down_s));
-    pend[ci & 1].busy = true;
-    pend[ci & 1].c.p = c.p;
-    pend[ci & 1].c.c0 = c.c0;
-    pend[ci & 1].c.c1 = c.c1;
+    return SV_OK;
   }
-  for (int i = 0; i < 2; ++i)
-    if ((rc = check_drain(D.st[i], pend[i], out))) return rc;
-  return SV_OK;
-}
+  int prepare(Stage& s, const AcctChunk& c, size_t* bytes, size_t* nq) {
+    L = acct_layout(sv_acct_ws_bytes(c.p.b1 - c.p.b0, c.e1 - c.e0, c.c1 - c.c0), c.p.b1 - c.p.b0, c.c1 - c.c0, false,
+                    c.nk, c.nq, c.ng);
+    *bytes = c.bytes;
+    *nq = c.nq;
+    return s.d_acct.ensure(L.bytes);
+  }
+  void pack(const AcctChunk& c, uint8_t* hp) const { acct_pack(in, c, hp); }
+  int tables(Device&, Stage& s, const AcctChunk& c, const uint8_t* d, hipStream_t st, TxDev* T) const {
+    uint8_t* da = (uint8_t*)s.d_acct.p;
+    const size_t nc = c.c1 - c.c0;
+    const sv_acct_use U{(const uint64_t*)(d + c.o_eb), (const uint32_t*)(d + c.o_ea), (const uint64_t*)(d + c.o_cb),
+                        (const uint32_t*)(d + c.o_ca), d + c.o_lvl, (const int32_t*)(d + c.o_need), T->h.nb, c.e1 - c.e0,
+                        nc};
+    const sv_acct_out O = acct_out(L, da, da, c.nk, c.nq, c.ng);
+    SV_HIP(sv_launch_acct_count(&tab, tab_ws, &U, &O, da, st));
+    SV_HIP(sv_launch_acct_fill(&tab, tab_ws, &U, &O, da, st));
+    acct_tables(O, in.sig_len ? d + c.o_sl : nullptr, clamp, U.cbeg, nc, T);
+    return SV_OK;
+  }
+};
 
 inline int acct_slice(Device& D, const AcctIn& in, const sv_txaccounts& A, size_t B0, size_t B1, int clamp,
                       const CheckOut& out, int path) {
-  return with_slot(D, [&] { return acct_slice_locked(D, in, A, B0, B1, clamp, out, path); });
+  return with_slot(D, [&] {
+    AcctSrc src{in, A, clamp};
+    return check_chunks_locked(D, src, B0, B1, out, path);
+  });
 }
 
 }  // namespace

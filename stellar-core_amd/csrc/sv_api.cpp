@@ -420,6 +420,32 @@ int device_call(Device& D, void* stream, Work work) {
   return device_call(D, stream, [] { return SV_OK; }, work);
 }
 
+// The slot prelude of the device-resident tx-body forms, which wait on the host in mid-call and so queue their own
+// stream dependencies: the slot `device` names; idle(&rc), ahead of the lock -- true: the call is complete with rc;
+// then fn(D) under D.mu, with the device set and the slot's resources created.
+template <class Idle, class F>
+int slot_call(int device, Idle idle, F fn) {
+  Device* D;
+  int rc;
+  if ((rc = slot_arg(device, D))) return rc;
+  if (idle(&rc)) return rc;
+  std::lock_guard<std::mutex> g(D->mu);
+  SV_HIP(hipSetDevice(D->phys));
+  if ((rc = ready_locked(*D))) return rc;
+  return fn(*D);
+}
+
+// D.txpair of `bytes` and the pinned words the counts come back in (caller holds D.mu; growing drains the kernel
+// stream).
+int txpair_bufs(Device& D, size_t bytes) {
+  if (bytes > D.txpair.cap) {
+    SV_HIP(hipStreamSynchronize(D.stream));
+    int rc;
+    if ((rc = D.txpair.ensure(bytes))) return rc;
+  }
+  return D.h_txcnt.ensure(64);
+}
+
 }  // namespace
 
 extern "C" {
@@ -786,88 +812,99 @@ int sv_ed25519_verify_txbodies_hinted_device(int device, const uint8_t* network_
     return fail(SV_ERR_ALIGN, "sig/key/digests must be 16-byte aligned, hint and the pair arrays naturally aligned");
   int rc;
   if ((rc = debug_fail())) return rc;
-  Device* Dp;
-  if ((rc = slot_arg(device, Dp))) return rc;
-  Device& D = *Dp;
-  *n_pairs = 0;
+  const HintDev H{network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin,
+                  d_hint,     d_sig,    n_sigs,     d_key_begin, d_key,       n_keys};
   hipStream_t user = (hipStream_t)stream;
-  std::lock_guard<std::mutex> g(D.mu);
-  SV_HIP(hipSetDevice(D.phys));
-  if ((rc = ready_locked(D))) return rc;
-  if (n_bodies == 0) {
-    SV_HIP(hipMemsetAsync(d_pair_begin, 0, 8, user));
-    return SV_OK;
-  }
-  // the pairing workspace, a digest array when the caller wants none, and the
-  // pinned word the count comes back in (growing drains the kernel stream)
-  const size_t wsb = al16(sv_pair_ws_bytes(n_bodies));
-  const size_t need = wsb + (d_digests ? 0 : 32 * n_bodies);
-  if (need > D.txpair.cap) {
-    SV_HIP(hipStreamSynchronize(D.stream));
-    if ((rc = D.txpair.ensure(need))) return rc;
-  }
-  if ((rc = D.h_txcnt.ensure(64))) return rc;
-  void* dig = d_digests ? d_digests : (void*)((uint8_t*)D.txpair.p + wsb);
-  SV_HIP(hipEventRecord(D.dep_in, user));
-  SV_HIP(hipStreamWaitEvent(D.stream, D.dep_in, 0));
-  SV_HIP(sv_launch_txhash(D.grid * 8, network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, nullptr, 0,
-                          nullptr, dig, D.stream));
-  SV_HIP(sv_launch_pair_count(d_sig_begin, d_hint, d_sig, n_sigs, d_key_begin, d_key, n_keys, n_bodies, D.txpair.p,
-                              d_pair_begin, D.stream));
-  SV_HIP(hipMemcpyAsync(D.h_txcnt.p, sv_pair_total(D.txpair.p, n_bodies), 8, hipMemcpyDeviceToHost, D.stream));
-  // the one wait: the number of pairs is only known on the device
-  SV_HIP(hipStreamSynchronize(D.stream));
-  const size_t np = (size_t)*(const uint64_t*)D.h_txcnt.p;
-  *n_pairs = np;
-  if (np > pair_cap) return fail(SV_ERR_PAIR_CAP, "more pairs than pair_cap holds");
-  if ((rc = ensure_txpairs(D, np))) return rc;
-  SV_HIP(sv_launch_pair_fill(d_sig_begin, d_hint, d_sig, n_sigs, d_key_begin, d_key, n_keys, n_bodies, D.txpair.p,
-                             d_pair_begin, np, d_pair_sig, d_pair_key, D.txpk.p, D.txsg.p, D.txmsg.p, dig, D.stream));
-  // (no verdict array: the pairs and digests only)
-  if (np && d_pair_verdict &&
-      (rc = launch_locked(D, 0, SV_PATH_AUTO, D.txpk.p, D.txsg.p, D.txmsg.p, nullptr, nullptr, 32, np,
-                          d_pair_verdict, d_pair_bitmap, kt_mode() == 1)))
-    return rc;
-  SV_HIP(hipEventRecord(D.dep_out, D.stream));
-  SV_HIP(hipStreamWaitEvent(user, D.dep_out, 0));
-  return SV_OK;
+  return slot_call(
+      device,
+      [&](int*) {
+        *n_pairs = 0;
+        return false;
+      },
+      [&](Device& D) {
+        int rc;
+        if (n_bodies == 0) {
+          SV_HIP(hipMemsetAsync(d_pair_begin, 0, 8, user));
+          return SV_OK;
+        }
+        // the pairing workspace (pair_begin is the caller's), a digest array when the caller wants none, and the
+        // pinned word the count comes back in
+        const size_t wsb = al16(sv_pair_ws_bytes(n_bodies));
+        if ((rc = txpair_bufs(D, wsb + (d_digests ? 0 : 32 * n_bodies)))) return rc;
+        TxBufs B = TxBufs::at(D.txpair.p, 0, n_bodies, D.h_txcnt.p);
+        B.pair_begin = d_pair_begin;
+        void* dig = d_digests ? d_digests : (void*)((uint8_t*)D.txpair.p + wsb);
+        const TxDev T{H, dig};
+        SV_HIP(hipEventRecord(D.dep_in, user));
+        SV_HIP(hipStreamWaitEvent(D.stream, D.dep_in, 0));
+        if ((rc = tx_enqueue_hash(D, T, D.stream)) || (rc = tx_enqueue_counts(T, B, D.stream))) return rc;
+        // the one wait: the number of pairs is only known on the device
+        SV_HIP(hipStreamSynchronize(D.stream));
+        size_t np, npp;
+        tx_counted(T, B, &np, &npp);
+        *n_pairs = np;
+        if (np > pair_cap) return fail(SV_ERR_PAIR_CAP, "more pairs than pair_cap holds");
+        // (no verdict array: the pairs and digests only)
+        if ((rc = tx_enqueue_pairs(D, T, B, np, d_pair_sig, d_pair_key, d_pair_verdict, d_pair_bitmap, SV_PATH_AUTO)))
+          return rc;
+        SV_HIP(hipEventRecord(D.dep_out, D.stream));
+        SV_HIP(hipStreamWaitEvent(user, D.dep_out, 0));
+        return SV_OK;
+      });
 }
 
-// (the twins' argument checks only ask whether the three check outputs are there; a decide call may leave any out)
-static const uint64_t kPresent = 0;
-static int results_args(const sv_txresults* res) {
+}  // extern "C"
+
+namespace {
+
+// The three per-check outputs of a check call; of a decide call: res's where its struct_size covers them, each
+// optional.
+struct CheckPtrs {
+  uint8_t* ok = nullptr;
+  uint32_t* weight = nullptr;
+  uint64_t* used = nullptr;
+};
+CheckPtrs decide_outputs(const sv_txresults* res) {
+  if (res->struct_size < sizeof(sv_txresults)) return CheckPtrs();
+  return CheckPtrs{res->check_ok, res->check_weight, res->check_used};
+}
+// What the twins' argument checks see of them: those only ask whether the three are there (and aligned), and a
+// decide call may leave any out.
+const uint64_t kPresent = 0;
+CheckPtrs outputs_seen(const sv_txresults* res, CheckPtrs p) {
+  if (!res) return p;
+  return CheckPtrs{p.ok ? p.ok : (uint8_t*)&kPresent, p.weight ? p.weight : (uint32_t*)&kPresent,
+                   p.used ? p.used : (uint64_t*)&kPresent};
+}
+
+int no_results() { return fail(SV_ERR_INVALID_ARG, "tx results: null struct"); }
+int results_args(const sv_txresults* res) {
   if (sv_txresults_args(res))
     return fail(SV_ERR_INVALID_ARG,
                 "tx results: null struct or body_code, a struct_size that is too small, or bad_cap without bad_body");
   return SV_OK;
 }
-static int results_check(const sv_txresults* res, size_t n_bodies, size_t n_checks) {
+int results_check(const sv_txresults* res, size_t n_bodies, size_t n_checks) {
   if (sv_txresults_check(res, n_bodies, n_checks))
     return fail(SV_ERR_INVALID_ARG, "tx results: a check_role > 1 or a body_flags bit other than bit 0");
   return SV_OK;
 }
 
-// sv_ed25519_check_txbodies and, with `res`, sv_ed25519_decide_txbodies (the three check outputs are then res's,
-// each optional).
-static int check_host(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
-                      const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies, const uint64_t* sig_begin,
-                      const uint8_t* hint, const uint8_t* sig, size_t n_sigs, const uint64_t* key_begin,
-                      const uint8_t* key, size_t n_keys, const sv_txchecks* checks, uint8_t* check_ok,
-                      uint32_t* check_weight, uint64_t* check_used, const sv_txresults* res, uint8_t* digests,
-                      const sv_opts* opts) {
+// A host check call and, with `res`, its decide twin.  validate(seen, &n_checks): the form's argument check;
+// slice(D, B0, B1, out, path): bodies [B0, B1) on slot D.  One slot, or slices of whole bodies over several -- a
+// body's checks are contiguous, so every slot writes its decisions straight into the caller's arrays -- and then
+// the bad list of a decide call, on the host, from the codes of every chunk and slot.
+template <class Validate, class Slice>
+int check_call_host(const HintIn& h, size_t n_sigs, CheckPtrs p, const sv_txresults* res, uint8_t* digests,
+                    const sv_opts* opts, Validate validate, Slice slice) {
   LifeGuard life_;
   int rc = check_opts(opts);
   if (rc) return rc;
   if (res && (rc = results_args(res))) return rc;
-  if (sv_txchecks_check(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, n_sigs,
-                        key_begin, key, n_keys, checks, res ? (const uint8_t*)&kPresent : check_ok,
-                        res ? (const uint32_t*)&kPresent : check_weight, res ? &kPresent : check_used))
-    return fail(SV_ERR_INVALID_ARG,
-                "tx checks: null pointer, body kind > 2, malformed CSR array, signer type > 3, key index outside its "
-                "body, sig_len > 64, more than 64 signatures or signers in a check, protocol 7, or a malformed payload "
-                "table (pkey_begin, pkey_len > 64, null table, 2^32 or more candidates)");
-  if (res && (rc = results_check(res, n_bodies, checks->n_checks))) return rc;
-  if (n_bodies == 0) {
+  size_t n_checks = 0;
+  if ((rc = validate(outputs_seen(res, p), &n_checks))) return rc;
+  if (res && (rc = results_check(res, h.nb, n_checks))) return rc;
+  if (h.nb == 0) {
     if (res) sv_txresults_bad_list(res, 0);
     return SV_OK;
   }
@@ -876,143 +913,85 @@ static int check_host(const uint8_t* network_id, const uint8_t* bodies, const ui
   std::vector<Device*> devs;
   if ((rc = select_devices(opts, n_sigs, devs))) return rc;
   const int path = path_from_flags(opts ? opts->flags : 0u);
-  CheckIn in{{network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, key_begin, key},
-             checks->sig_len,      checks->check_begin,   checks->check_needed, checks->signer_begin,
-             checks->signer_type, checks->signer_weight, checks->signer_key};
-  // (payload tables without a candidate: the call without them)
-  const sv_txchecks_payload* pt = sv_txchecks_tables(checks);
-  if (pt && pt->n_pkeys) {
-    in.qb = pt->pkey_begin;
-    in.qkey = pt->pkey;
-    in.qpay = pt->pkey_payload;
-    in.qlen = pt->pkey_len;
-  }
-  const int clamp = checks->protocol_version >= 10;
   ResultOut ro{};
   if (res) ro = ResultOut{res->check_role, res->body_flags, res->body_code, res->body_fail};
-  const CheckOut out{check_ok, check_weight, check_used, digests, res ? &ro : nullptr};
+  const CheckOut out{p.ok, p.weight, p.used, digests, res ? &ro : nullptr};
   const size_t G = devs.size();
   if (G == 1) {
-    rc = check_slice(*devs[0], in, 0, n_bodies, clamp, out, path);
+    rc = slice(*devs[0], 0, h.nb, out, path);
   } else {
-    // Slices of whole bodies: a body's checks are contiguous, so every slot
-    // writes its decisions straight into the caller's arrays.
-    const std::vector<size_t> cut = pair_slices(sig_begin, n_bodies, G);
+    const std::vector<size_t> cut = pair_slices(h.sb, h.nb, G);
     rc = shard(devs, G, [&](Device& D, size_t g, size_t) {
       if (cut[g] == cut[g + 1]) return SV_OK;
-      return check_slice(D, in, cut[g], cut[g + 1], clamp, out, path);
+      return slice(D, cut[g], cut[g + 1], out, path);
     });
   }
-  // (the bad list of a decide call: on the host, from the codes of every chunk and slot)
-  if (rc == SV_OK && res) sv_txresults_bad_list(res, n_bodies);
+  if (rc == SV_OK && res) sv_txresults_bad_list(res, h.nb);
   return rc;
 }
 
-int sv_ed25519_check_txbodies(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
-                              const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
-                              const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig, size_t n_sigs,
-                              const uint64_t* key_begin, const uint8_t* key, size_t n_keys, const sv_txchecks* checks,
-                              uint8_t* check_ok, uint32_t* check_weight, uint64_t* check_used, uint8_t* digests,
-                              const sv_opts* opts) {
-  return check_host(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, n_sigs,
-                    key_begin, key, n_keys, checks, check_ok, check_weight, check_used, nullptr, digests, opts);
+// sv_ed25519_check_txbodies and, with `res`, sv_ed25519_decide_txbodies.
+int check_host(const HintIn& h, size_t n_sigs, size_t n_keys, const sv_txchecks* checks, CheckPtrs p,
+               const sv_txresults* res, uint8_t* digests, const sv_opts* opts) {
+  return check_call_host(
+      h, n_sigs, p, res, digests, opts,
+      [&](CheckPtrs seen, size_t* n_checks) {
+        if (sv_txchecks_check(h.nid, h.bodies, h.off, h.len, h.kind, h.nb, h.sb, h.hint, h.sig, n_sigs, h.kb, h.key,
+                              n_keys, checks, seen.ok, seen.weight, seen.used))
+          return fail(SV_ERR_INVALID_ARG,
+                      "tx checks: null pointer, body kind > 2, malformed CSR array, signer type > 3, key index outside "
+                      "its body, sig_len > 64, more than 64 signatures or signers in a check, protocol 7, or a "
+                      "malformed payload table (pkey_begin, pkey_len > 64, null table, 2^32 or more candidates)");
+        *n_checks = checks->n_checks;
+        return (int)SV_OK;
+      },
+      [&](Device& D, size_t B0, size_t B1, const CheckOut& out, int path) {
+        CheckIn in{h, checks->sig_len, checks->check_begin, checks->check_needed, checks->signer_begin,
+                   checks->signer_type, checks->signer_weight, checks->signer_key};
+        // (payload tables without a candidate: the call without them)
+        const sv_txchecks_payload* pt = sv_txchecks_tables(checks);
+        if (pt && pt->n_pkeys) {
+          in.qb = pt->pkey_begin;
+          in.qkey = pt->pkey;
+          in.qpay = pt->pkey_payload;
+          in.qlen = pt->pkey_len;
+        }
+        return check_slice(D, in, B0, B1, checks->protocol_version >= 10, out, path);
+      });
 }
 
-int sv_ed25519_decide_txbodies(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
-                               const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
-                               const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig, size_t n_sigs,
-                               const uint64_t* key_begin, const uint8_t* key, size_t n_keys, const sv_txchecks* checks,
-                               const sv_txresults* res, uint8_t* digests, const sv_opts* opts) {
-  if (!res) return fail(SV_ERR_INVALID_ARG, "tx results: null struct");
-  return check_host(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, n_sigs,
-                    key_begin, key, n_keys, checks, res->struct_size >= sizeof(sv_txresults) ? res->check_ok : nullptr,
-                    res->struct_size >= sizeof(sv_txresults) ? res->check_weight : nullptr,
-                    res->struct_size >= sizeof(sv_txresults) ? res->check_used : nullptr, res, digests, opts);
-}
-
-}  // extern "C"
-
-namespace {
-// The device-resident check call on slot D (caller holds D.mu, device set, slot ready, arguments checked): `ck`'s
-// arrays and `pl` are device memory.  Shared by sv_ed25519_check_txbodies_device and the by-account form, which
-// runs it on the tables it expanded.  With `res` (a decide call) the result kernels follow the check kernel on
-// the slot's stream, ahead of the event the caller's stream waits for: no wait is added.
-struct DevDecide {
-  const sv_txresults* res = nullptr;
-  void* ws = nullptr;  // sv_txresult_ws_bytes(n_bodies)
-};
-int check_device_locked(Device& D, const uint8_t* network_id, const void* d_bodies, const uint64_t* d_body_off,
-                        const uint32_t* d_body_len, const uint8_t* d_body_kind, size_t n_bodies,
-                        const uint64_t* d_sig_begin, const void* d_hint, const void* d_sig, size_t n_sigs,
-                        const uint64_t* d_key_begin, const void* d_key, size_t n_keys, const sv_txchecks* ck,
-                        const PayloadDev& pl, void* d_check_ok, uint32_t* d_check_weight, uint64_t* d_check_used,
-                        void* d_digests, void* stream, const DevDecide& dec = DevDecide()) {
-  int rc;
-  hipStream_t user = (hipStream_t)stream;
-  // the pairing workspace, pair_begin, a digest array when the caller wants
-  // none, and the pinned word the count comes back in (growing drains the
-  // kernel stream)
-  const size_t wsb = al16(sv_pair_ws_bytes(n_bodies)), pbb = al16(8 * (n_bodies + 1));
-  const size_t o_pws = wsb + pbb + (d_digests ? 0 : 32 * n_bodies), pwsb = al16(sv_ppair_ws_bytes(n_bodies));
-  const size_t need = o_pws + (pl.nq ? pwsb + pbb : 0);
-  if (need > D.txpair.cap) {
-    SV_HIP(hipStreamSynchronize(D.stream));
-    if ((rc = D.txpair.ensure(need))) return rc;
-  }
-  if ((rc = D.h_txcnt.ensure(64))) return rc;
-  uint64_t* d_pb = (uint64_t*)((uint8_t*)D.txpair.p + wsb);
-  void* dig = d_digests ? d_digests : (void*)((uint8_t*)D.txpair.p + wsb + pbb);
-  SV_HIP(hipEventRecord(D.dep_in, user));
-  SV_HIP(hipStreamWaitEvent(D.stream, D.dep_in, 0));
-  SV_HIP(sv_launch_txhash(D.grid * 8, network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, nullptr, 0,
-                          nullptr, dig, D.stream));
-  SV_HIP(sv_launch_pair_count(d_sig_begin, d_hint, d_sig, n_sigs, d_key_begin, d_key, n_keys, n_bodies, D.txpair.p,
-                              d_pb, D.stream));
-  void* d_pws = (uint8_t*)D.txpair.p + o_pws;
-  uint64_t* d_ppb = (uint64_t*)((uint8_t*)D.txpair.p + o_pws + pwsb);
-  if (pl.nq)
-    SV_HIP(sv_launch_ppair_count(d_sig_begin, d_hint, n_sigs, pl.qb, pl.key, pl.payload, pl.len, pl.nq, n_bodies,
-                                 D.txpair.p, d_pws, d_ppb, D.stream));
-  // (both counts in the one copy: the payload pairing's total is the word behind the ed25519 pairing's)
-  SV_HIP(hipMemcpyAsync(D.h_txcnt.p, sv_pair_total(D.txpair.p, n_bodies), pl.nq ? 16 : 8, hipMemcpyDeviceToHost,
-                        D.stream));
-  // the one wait: the number of pairs is only known on the device (the stream
-  // is idle afterwards, so the pair arrays may grow here)
-  SV_HIP(hipStreamSynchronize(D.stream));
-  const size_t np = (size_t)*(const uint64_t*)D.h_txcnt.p;
-  const size_t npp = pl.nq ? (size_t)((const uint64_t*)D.h_txcnt.p)[1] : 0;
-  const size_t o_idx = al16(np);
-  if ((rc = ensure_txpairs(D, np)) || (rc = D.txchk.ensure(o_idx + 8 * np + 16))) return rc;
-  // (the workspace of both verify launches now, so the second never grows it under the first)
-  if (npp && ((rc = ensure_txpp(D, ppair_layout(npp).bytes)) || (rc = presize_ws(D, SV_PATH_AUTO, npp)))) return rc;
-  uint8_t* dv = (uint8_t*)D.txchk.p;
-  uint32_t* d_ps = (uint32_t*)(dv + o_idx);
-  uint32_t* d_pk = d_ps + np;
-  SV_HIP(sv_launch_pair_fill(d_sig_begin, d_hint, d_sig, n_sigs, d_key_begin, d_key, n_keys, n_bodies, D.txpair.p,
-                             d_pb, np, d_ps, d_pk, D.txpk.p, D.txsg.p, D.txmsg.p, dig, D.stream));
-  if (np && (rc = launch_locked(D, 0, SV_PATH_AUTO, D.txpk.p, D.txsg.p, D.txmsg.p, nullptr, nullptr, 32, np, dv,
-                                nullptr, kt_mode() == 1)))
-    return rc;
-  if (npp && (rc = ppair_run(D, pl, d_sig_begin, d_hint, d_sig, n_sigs, n_bodies, D.txpair.p, d_pws, d_ppb, npp,
-                             SV_PATH_AUTO)))
-    return rc;
-  const PPairBufs L = ppair_layout(npp);
-  const uint8_t* dpp = (const uint8_t*)D.txpp.p;
-  SV_HIP(sv_launch_txcheck_payload(d_sig_begin, d_hint, d_sig, ck->sig_len, n_sigs, d_key_begin, d_key, n_keys, n_bodies, d_pb,
-                           d_ps, d_pk, dv, np, dig, ck->check_begin, ck->check_needed, ck->n_checks, ck->signer_begin,
-                           ck->signer_type, ck->signer_weight, ck->signer_key, ck->n_signers,
-                           ck->protocol_version >= 10, d_ppb, (const uint32_t*)(dpp + L.o_idx),
-                           (const uint32_t*)(dpp + L.o_idx) + npp, dpp, npp, pl.qb, pl.nq, (uint8_t*)d_check_ok,
-                           d_check_weight, d_check_used, D.stream));
-  if (dec.res) {
-    const sv_txresults& R = *dec.res;
-    const sv_txresult_in I{ck->check_begin, d_sig_begin,  (const uint8_t*)d_check_ok, d_check_used, R.check_role,
-                           R.body_flags,    n_bodies,     ck->n_checks,               n_sigs};
-    SV_HIP(sv_launch_txresult(&I, R.body_code, R.body_fail, dec.ws, R.bad_body, R.bad_cap, R.n_bad, D.stream));
-  }
-  SV_HIP(hipEventRecord(D.dep_out, D.stream));
-  SV_HIP(hipStreamWaitEvent(user, D.dep_out, 0));
-  return SV_OK;
+// sv_ed25519_check_txbodies_accounts and, with `res`, sv_ed25519_decide_txbodies_accounts (slices of whole bodies
+// as in sv_ed25519_check_txbodies; every slot takes the whole account table).
+int accounts_host(const HintIn& h, size_t n_sigs, const sv_txaccounts* A, CheckPtrs p, const sv_txresults* res,
+                  uint8_t* digests, const sv_opts* opts) {
+  // (the per-account row counts come out of the argument check: made once, used by every slot's planner)
+  std::vector<uint32_t> acnt(2);
+  return check_call_host(
+      h, n_sigs, p, res, digests, opts,
+      [&](CheckPtrs seen, size_t* n_checks) {
+        if (A && A->struct_size >= sizeof(sv_txaccounts) && !((uint64_t)A->n_accounts >> 32)) {
+          try {
+            acnt.resize(2 * A->n_accounts + 2);
+          } catch (const std::bad_alloc&) {
+            return fail(SV_ERR_ALLOC, "tx checks by account: no memory for the per-account row counts");
+          }
+        }
+        if (sv_txaccounts_check(h.nid, h.bodies, h.off, h.len, h.kind, h.nb, h.sb, h.hint, h.sig, n_sigs, A, seen.ok,
+                                seen.weight, seen.used, acnt.data()))
+          return fail(SV_ERR_INVALID_ARG,
+                      "tx checks by account: null pointer, body kind > 2, malformed CSR array, bacct entry >= "
+                      "n_accounts, check_acct outside its body, level > 3, signer type > 3, payload index >= "
+                      "n_apayloads, apayload_len or sig_len > 64, more than 64 signatures in a body with checks or "
+                      "signers in an account's expanded list, protocol 7, 2^32 or more rows, or a struct_size that is "
+                      "too small");
+        *n_checks = A->n_checks;
+        return (int)SV_OK;
+      },
+      [&](Device& D, size_t B0, size_t B1, const CheckOut& out, int path) {
+        const AcctIn in{h, A->sig_len, A->bacct_begin, A->bacct, A->check_begin, A->check_acct, A->check_level,
+                        A->check_needed, acnt.data()};
+        return acct_slice(D, in, *A, B0, B1, A->protocol_version >= 10, out, path);
+      });
 }
 
 // A device-resident decide call's sv_txresults: the pointers and their alignment.
@@ -1034,8 +1013,7 @@ int decide_device_empty(const sv_txresults* res, void* stream) {
 // Its check arrays and workspace on slot D (caller holds D.mu): the caller's arrays where it asked for them, else
 // D.txres -- used (8 nc) | weight (4 nc) | ok (nc) | the result kernels' workspace.  Growing drains the kernel
 // stream, as the twin's own buffers do.
-int decide_device_bufs(Device& D, const sv_txresults* res, size_t n_bodies, size_t nc, void** ok, uint32_t** weight,
-                       uint64_t** used, DevDecide* dec) {
+int decide_device_bufs(Device& D, const sv_txresults* res, size_t n_bodies, size_t nc, CheckPtrs* p, ResultDev* R) {
   const size_t o_w = al16(8 * nc), o_ok = o_w + al16(4 * nc), o_ws = o_ok + al16(nc);
   const size_t need = o_ws + al16(sv_txresult_ws_bytes(n_bodies)) + 16;
   if (need > D.txres.cap) {
@@ -1044,78 +1022,209 @@ int decide_device_bufs(Device& D, const sv_txresults* res, size_t n_bodies, size
     if ((rc = D.txres.ensure(need))) return rc;
   }
   uint8_t* b = (uint8_t*)D.txres.p;
-  *used = res->check_used ? res->check_used : (uint64_t*)b;
-  *weight = res->check_weight ? res->check_weight : (uint32_t*)(b + o_w);
-  *ok = res->check_ok ? (void*)res->check_ok : (void*)(b + o_ok);
-  dec->res = res;
-  dec->ws = b + o_ws;
+  if (!p->used) p->used = (uint64_t*)b;
+  if (!p->weight) p->weight = (uint32_t*)(b + o_w);
+  if (!p->ok) p->ok = b + o_ok;
+  *R = ResultDev{res->check_role, res->body_flags, res->body_code, res->body_fail,
+                 b + o_ws,        res->bad_body,   res->bad_cap,   res->n_bad};
   return SV_OK;
+}
+
+// A device-resident check call and, with `res`, its decide twin (the three check arrays are then res's, or the
+// slot's own where res has none).  validate(seen, &n_checks): the form's argument check; tables(D, &T): the form's
+// key, check and payload tables into T, whose signature side is filled in -- the explicit form names the caller's,
+// the by-account form expands them on D.stream, with a host wait of its own.  Then the sequence of a chunk over
+// the slot's own buffers: contents hashes -> pair counts -> the one wait -> fill -> verify launches -> check
+// kernel (-> result kernels: on the slot's stream, ahead of the event the caller's stream waits for, so a decide
+// call adds no wait).
+template <class Validate, class Tables>
+int check_call_device(int device, const HintDev& H, CheckPtrs p, const sv_txresults* res, void* d_digests,
+                      void* stream, Validate validate, Tables tables) {
+  LifeGuard life_;
+  int rc;
+  if (res && (rc = decide_device_args(res, H.nb))) return rc;
+  size_t nc = 0;
+  if ((rc = validate(outputs_seen(res, p), &nc))) return rc;
+  if ((rc = debug_fail())) return rc;
+  hipStream_t user = (hipStream_t)stream;
+  return slot_call(
+      device,
+      [&](int* done) {
+        if (H.nb) return false;
+        *done = res ? decide_device_empty(res, stream) : SV_OK;
+        return true;
+      },
+      [&](Device& D) {
+        int rc;
+        const size_t k = H.nb;
+        ResultDev R;
+        if (res && (rc = decide_device_bufs(D, res, k, nc, &p, &R))) return rc;
+        const DecideDev out{p.ok, p.weight, p.used, res ? &R : nullptr};
+        TxDev T{H, nullptr};
+        if ((rc = tables(D, &T))) return rc;
+        // the pairing workspace, pair_begin, a digest array when the caller wants none, the payload pairing's
+        // behind it, and the pinned words the counts come back in
+        const size_t o_tail = TxBufs::head(k) + (d_digests ? 0 : 32 * k);
+        if ((rc = txpair_bufs(D, o_tail + (T.pl.nq ? TxBufs::tail(k) : 0)))) return rc;
+        const TxBufs B = TxBufs::at(D.txpair.p, o_tail, k, D.h_txcnt.p);
+        T.digests = d_digests ? d_digests : (void*)((uint8_t*)D.txpair.p + TxBufs::head(k));
+        SV_HIP(hipEventRecord(D.dep_in, user));
+        SV_HIP(hipStreamWaitEvent(D.stream, D.dep_in, 0));
+        if ((rc = tx_enqueue_hash(D, T, D.stream)) || (rc = tx_enqueue_counts(T, B, D.stream))) return rc;
+        // the one wait: the number of pairs is only known on the device (the stream is idle afterwards, so the
+        // pair arrays may grow here)
+        SV_HIP(hipStreamSynchronize(D.stream));
+        size_t np, npp;
+        tx_counted(T, B, &np, &npp);
+        if ((rc = D.txchk.ensure(al16(np) + 8 * np + 16))) return rc;
+        // (the workspace of both verify launches now, so the second never grows it under the first)
+        if (npp && (rc = presize_ws(D, SV_PATH_AUTO, npp))) return rc;
+        if ((rc = tx_enqueue_decide(D, T, B, np, npp, (uint8_t*)D.txchk.p, out, SV_PATH_AUTO))) return rc;
+        SV_HIP(hipEventRecord(D.dep_out, D.stream));
+        SV_HIP(hipStreamWaitEvent(user, D.dep_out, 0));
+        return SV_OK;
+      });
+}
+
+// sv_ed25519_check_txbodies_device and, with `res`, sv_ed25519_decide_txbodies_device.
+int check_device(int device, const HintDev& H, const sv_txchecks* ck, CheckPtrs p, const sv_txresults* res,
+                 void* d_digests, void* stream) {
+  PayloadDev pl;
+  return check_call_device(
+      device, H, p, res, d_digests, stream,
+      [&](CheckPtrs seen, size_t* nc) {
+        if (!H.nid || !ck || ck->struct_size < sizeof(sv_txchecks) ||
+            (H.nb && (!H.bodies || !H.off || !H.len || !H.kind || !H.sb || !H.kb || !ck->check_begin)) ||
+            (H.m && (!H.hint || !H.sig)) || (H.q && !H.key) ||
+            (ck->n_checks && (H.nb == 0 || !ck->check_needed || !ck->signer_begin || !seen.ok || !seen.weight ||
+                              !seen.used)) ||
+            (ck->n_signers && (!ck->signer_type || !ck->signer_weight || !ck->signer_key)))
+          return fail(SV_ERR_INVALID_ARG, "tx checks: null pointer");
+        if (ck->protocol_version == 7) return fail(SV_ERR_INVALID_ARG, "tx checks: protocol 7 needs no engine");
+        if ((uint64_t)H.m >> 32 || (uint64_t)H.q >> 32)
+          return fail(SV_ERR_INVALID_ARG, "tx checks: 2^32 or more signatures or keys");
+        // the payload tables: with no candidate the call is the one without them
+        const sv_txchecks_payload* pt = sv_txchecks_tables(ck);
+        if (pt && pt->n_pkeys) {
+          if ((uint64_t)pt->n_pkeys >> 32 || !pt->pkey || !pt->pkey_payload || !pt->pkey_len)
+            return fail(SV_ERR_INVALID_ARG, "tx checks: null payload table, or 2^32 or more payload candidates");
+          if (!aligned16(pt->pkey) || !aligned16(pt->pkey_payload) || ((uintptr_t)pt->pkey_begin & 7u))
+            return fail(SV_ERR_ALIGN, "pkey/pkey_payload must be 16-byte aligned, pkey_begin naturally aligned");
+          pl = PayloadDev{pt->pkey_begin, pt->pkey, pt->pkey_payload, pt->pkey_len, pt->n_pkeys};
+        }
+        if (!aligned16(H.sig) || !aligned16(H.key) || !aligned16(d_digests) || ((uintptr_t)H.hint & 3u) ||
+            ((uintptr_t)ck->check_begin & 7u) || ((uintptr_t)ck->signer_begin & 7u) ||
+            ((uintptr_t)ck->check_needed & 3u) || ((uintptr_t)ck->signer_weight & 3u) ||
+            ((uintptr_t)ck->signer_key & 3u) || ((uintptr_t)seen.weight & 3u) || ((uintptr_t)seen.used & 7u))
+          return fail(SV_ERR_ALIGN,
+                      "sig/key/digests must be 16-byte aligned, hint and the check arrays naturally aligned");
+        *nc = ck->n_checks;
+        return (int)SV_OK;
+      },
+      [&](Device&, TxDev* T) {
+        T->c = CheckTabs{ck->sig_len,      ck->protocol_version >= 10, ck->check_begin,   ck->check_needed,
+                         ck->n_checks,     ck->signer_begin,           ck->signer_type,   ck->signer_weight,
+                         ck->signer_key,   ck->n_signers};
+        T->pl = pl;
+        return (int)SV_OK;
+      });
+}
+
+// sv_ed25519_check_txbodies_accounts_device and, with `res`, sv_ed25519_decide_txbodies_accounts_device.
+int accounts_device(int device, const HintDev& H, const sv_txaccounts* A, CheckPtrs p, const sv_txresults* res,
+                    void* d_digests, void* stream) {
+  return check_call_device(
+      device, H, p, res, d_digests, stream,
+      [&](CheckPtrs seen, size_t* n_checks) {
+        if (!H.nid || !A || A->struct_size < sizeof(sv_txaccounts))
+          return fail(SV_ERR_INVALID_ARG, "tx checks by account: null pointer or a struct_size that is too small");
+        const size_t na = A->n_accounts, ns = A->n_asigners, np = A->n_apayloads, ne = A->n_bacct, nc = A->n_checks;
+        if ((H.nb && (!H.bodies || !H.off || !H.len || !H.kind || !H.sb || !A->bacct_begin || !A->check_begin)) ||
+            (H.m && (!H.hint || !H.sig)) || (na && (!A->acct_key || !A->acct_thresholds || !A->asigner_begin)) ||
+            (ns && (!A->asigner_type || !A->asigner_weight || !A->asigner_key)) ||
+            (np && (!A->apayload || !A->apayload_len)) || (ne && !A->bacct) ||
+            (nc && (H.nb == 0 || !A->check_acct || !A->check_level || !seen.ok || !seen.weight || !seen.used)))
+          return fail(SV_ERR_INVALID_ARG, "tx checks by account: null pointer");
+        if (A->protocol_version == 7)
+          return fail(SV_ERR_INVALID_ARG, "tx checks by account: protocol 7 needs no engine");
+        if ((uint64_t)H.m >> 32 || (uint64_t)na >> 32 || (uint64_t)ns >> 32 || (uint64_t)np >> 32 ||
+            (uint64_t)ne >> 32 || (uint64_t)nc >> 32)
+          return fail(SV_ERR_INVALID_ARG, "tx checks by account: 2^32 or more rows");
+        if (!aligned16(H.sig) || !aligned16(d_digests) || !aligned16(A->acct_key) || !aligned16(A->asigner_key) ||
+            !aligned16(A->apayload) || ((uintptr_t)H.hint & 3u) || ((uintptr_t)A->asigner_begin & 7u) ||
+            ((uintptr_t)A->bacct_begin & 7u) || ((uintptr_t)A->check_begin & 7u) ||
+            ((uintptr_t)A->asigner_weight & 3u) || ((uintptr_t)A->asigner_payload & 3u) ||
+            ((uintptr_t)A->bacct & 3u) || ((uintptr_t)A->check_acct & 3u) || ((uintptr_t)A->check_needed & 3u) ||
+            ((uintptr_t)seen.weight & 3u) || ((uintptr_t)seen.used & 7u))
+          return fail(SV_ERR_ALIGN,
+                      "sig/digests/acct_key/asigner_key/apayload must be 16-byte aligned, the other arrays naturally "
+                      "aligned");
+        *n_checks = nc;
+        return (int)SV_OK;
+      },
+      // the explicit tables, expanded on the slot's stream from the caller's account table
+      [&](Device& D, TxDev* T) {
+        int rc;
+        const size_t na = A->n_accounts, ns = A->n_asigners, ne = A->n_bacct, nc = A->n_checks, k = H.nb;
+        const sv_acct_tab tab{A->acct_key,       A->acct_thresholds, A->asigner_begin,   A->asigner_type,
+                              A->asigner_weight, A->asigner_key,     A->asigner_payload, A->apayload,
+                              A->apayload_len,   na,                 ns,                 A->n_apayloads};
+        const sv_acct_use U{A->bacct_begin, A->bacct, A->check_begin, A->check_acct, A->check_level, A->check_needed,
+                            k,              ne,       nc};
+        // the per-account counts and ranks, the expansion's workspace and its CSR arrays (growing drains the
+        // kernel stream), and the pinned words the totals come back in
+        const size_t tws = al16(sv_acct_tab_ws_bytes(na, ns));
+        const AcctBufs Hd = acct_layout(sv_acct_ws_bytes(k, ne, nc), k, nc, true, 0, 0, 0);
+        if (tws + Hd.head > D.txaws.cap) {
+          SV_HIP(hipStreamSynchronize(D.stream));
+          if ((rc = D.txaws.ensure(tws + Hd.head))) return rc;
+        }
+        if ((rc = D.h_txcnt.ensure(64))) return rc;
+        uint8_t* tab_ws = (uint8_t*)D.txaws.p;
+        uint8_t* head = tab_ws + tws;
+        SV_HIP(hipEventRecord(D.dep_in, (hipStream_t)stream));
+        SV_HIP(hipStreamWaitEvent(D.stream, D.dep_in, 0));
+        sv_acct_out O = acct_out(Hd, head, nullptr, 0, 0, 0);
+        SV_HIP(sv_launch_acct_table(&tab, tab_ws, D.stream));
+        SV_HIP(sv_launch_acct_count(&tab, tab_ws, &U, &O, head, D.stream));
+        SV_HIP(hipMemcpyAsync(D.h_txcnt.p, sv_acct_totals(head, k, ne, nc), 24, hipMemcpyDeviceToHost, D.stream));
+        // the wait this form adds: the expansion's three row counts are only known on the device
+        SV_HIP(hipStreamSynchronize(D.stream));
+        const uint64_t* tot = (const uint64_t*)D.h_txcnt.p;
+        if (tot[0] >> 32 || tot[1] >> 32 || tot[2] >> 32)
+          return fail(SV_ERR_INVALID_ARG, "tx checks by account: the expansion has 2^32 or more rows");
+        const size_t nk = (size_t)tot[0], nq = (size_t)tot[1], ng = (size_t)tot[2];
+        const AcctBufs L = acct_layout(sv_acct_ws_bytes(k, ne, nc), k, nc, true, nk, nq, ng);
+        if ((rc = D.txarows.ensure(L.bytes))) return rc;  // (the stream is idle)
+        O = acct_out(L, head, (uint8_t*)D.txarows.p, nk, nq, ng);
+        SV_HIP(sv_launch_acct_fill(&tab, tab_ws, &U, &O, head, D.stream));
+        acct_tables(O, A->sig_len, A->protocol_version >= 10, A->check_begin, nc, T);
+        return (int)SV_OK;
+      });
 }
 }  // namespace
 
 extern "C" {
 
-// sv_ed25519_check_txbodies_device and, with `res`, sv_ed25519_decide_txbodies_device (the three check arrays are
-// then res's, or the slot's own where res has none).
-static int check_device(int device, const uint8_t* network_id, const void* d_bodies, const uint64_t* d_body_off,
-                        const uint32_t* d_body_len, const uint8_t* d_body_kind, size_t n_bodies,
-                        const uint64_t* d_sig_begin, const void* d_hint, const void* d_sig, size_t n_sigs,
-                        const uint64_t* d_key_begin, const void* d_key, size_t n_keys, const sv_txchecks* ck,
-                        void* d_check_ok, uint32_t* d_check_weight, uint64_t* d_check_used, const sv_txresults* res,
-                        void* d_digests, void* stream) {
-  LifeGuard life_;
-  int rc;
-  if (res) {
-    if ((rc = decide_device_args(res, n_bodies))) return rc;
-    d_check_ok = res->check_ok ? (void*)res->check_ok : (void*)&kPresent;
-    d_check_weight = res->check_weight ? res->check_weight : (uint32_t*)&kPresent;
-    d_check_used = res->check_used ? res->check_used : (uint64_t*)&kPresent;
-  }
-  if (!network_id || !ck || ck->struct_size < sizeof(sv_txchecks) ||
-      (n_bodies && (!d_bodies || !d_body_off || !d_body_len || !d_body_kind || !d_sig_begin || !d_key_begin ||
-                    !ck->check_begin)) ||
-      (n_sigs && (!d_hint || !d_sig)) || (n_keys && !d_key) ||
-      (ck->n_checks && (n_bodies == 0 || !ck->check_needed || !ck->signer_begin || !d_check_ok || !d_check_weight ||
-                        !d_check_used)) ||
-      (ck->n_signers && (!ck->signer_type || !ck->signer_weight || !ck->signer_key)))
-    return fail(SV_ERR_INVALID_ARG, "tx checks: null pointer");
-  if (ck->protocol_version == 7) return fail(SV_ERR_INVALID_ARG, "tx checks: protocol 7 needs no engine");
-  if ((uint64_t)n_sigs >> 32 || (uint64_t)n_keys >> 32)
-    return fail(SV_ERR_INVALID_ARG, "tx checks: 2^32 or more signatures or keys");
-  // the payload tables: with no candidate the call is the one without them
-  PayloadDev pl;
-  const sv_txchecks_payload* pt = sv_txchecks_tables(ck);
-  if (pt && pt->n_pkeys) {
-    pl.qb = pt->pkey_begin;
-    if ((uint64_t)pt->n_pkeys >> 32 || !pt->pkey || !pt->pkey_payload || !pt->pkey_len)
-      return fail(SV_ERR_INVALID_ARG, "tx checks: null payload table, or 2^32 or more payload candidates");
-    if (!aligned16(pt->pkey) || !aligned16(pt->pkey_payload) || ((uintptr_t)pl.qb & 7u))
-      return fail(SV_ERR_ALIGN, "pkey/pkey_payload must be 16-byte aligned, pkey_begin naturally aligned");
-    pl.key = pt->pkey;
-    pl.payload = pt->pkey_payload;
-    pl.len = pt->pkey_len;
-    pl.nq = pt->n_pkeys;
-  }
-  if (!aligned16(d_sig) || !aligned16(d_key) || !aligned16(d_digests) || ((uintptr_t)d_hint & 3u) ||
-      ((uintptr_t)ck->check_begin & 7u) || ((uintptr_t)ck->signer_begin & 7u) || ((uintptr_t)ck->check_needed & 3u) ||
-      ((uintptr_t)ck->signer_weight & 3u) || ((uintptr_t)ck->signer_key & 3u) || ((uintptr_t)d_check_weight & 3u) ||
-      ((uintptr_t)d_check_used & 7u))
-    return fail(SV_ERR_ALIGN, "sig/key/digests must be 16-byte aligned, hint and the check arrays naturally aligned");
-  if ((rc = debug_fail())) return rc;
-  Device* Dp;
-  if ((rc = slot_arg(device, Dp))) return rc;
-  Device& D = *Dp;
-  if (n_bodies == 0) return res ? decide_device_empty(res, stream) : SV_OK;
-  std::lock_guard<std::mutex> g(D.mu);
-  SV_HIP(hipSetDevice(D.phys));
-  if ((rc = ready_locked(D))) return rc;
-  DevDecide dec;
-  if (res && (rc = decide_device_bufs(D, res, n_bodies, ck->n_checks, &d_check_ok, &d_check_weight, &d_check_used,
-                                      &dec)))
-    return rc;
-  return check_device_locked(D, network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin,
-                             d_hint, d_sig, n_sigs, d_key_begin, d_key, n_keys, ck, pl, d_check_ok, d_check_weight,
-                             d_check_used, d_digests, stream, dec);
+int sv_ed25519_check_txbodies(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                              const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                              const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig, size_t n_sigs,
+                              const uint64_t* key_begin, const uint8_t* key, size_t n_keys, const sv_txchecks* checks,
+                              uint8_t* check_ok, uint32_t* check_weight, uint64_t* check_used, uint8_t* digests,
+                              const sv_opts* opts) {
+  return check_host({network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, key_begin, key},
+                    n_sigs, n_keys, checks, {check_ok, check_weight, check_used}, nullptr, digests, opts);
+}
+
+int sv_ed25519_decide_txbodies(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                               const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                               const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig, size_t n_sigs,
+                               const uint64_t* key_begin, const uint8_t* key, size_t n_keys, const sv_txchecks* checks,
+                               const sv_txresults* res, uint8_t* digests, const sv_opts* opts) {
+  return !res ? no_results()
+              : check_host({network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig,
+                            key_begin, key},
+                           n_sigs, n_keys, checks, decide_outputs(res), res, digests, opts);
 }
 
 int sv_ed25519_check_txbodies_device(int device, const uint8_t* network_id, const void* d_bodies,
@@ -1125,9 +1234,10 @@ int sv_ed25519_check_txbodies_device(int device, const uint8_t* network_id, cons
                                      const uint64_t* d_key_begin, const void* d_key, size_t n_keys,
                                      const sv_txchecks* ck, void* d_check_ok, uint32_t* d_check_weight,
                                      uint64_t* d_check_used, void* d_digests, void* stream) {
-  return check_device(device, network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin, d_hint,
-                      d_sig, n_sigs, d_key_begin, d_key, n_keys, ck, d_check_ok, d_check_weight, d_check_used, nullptr,
-                      d_digests, stream);
+  return check_device(device,
+                      {network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin, d_hint, d_sig,
+                       n_sigs, d_key_begin, d_key, n_keys},
+                      ck, {(uint8_t*)d_check_ok, d_check_weight, d_check_used}, nullptr, d_digests, stream);
 }
 
 int sv_ed25519_decide_txbodies_device(int device, const uint8_t* network_id, const void* d_bodies,
@@ -1136,68 +1246,11 @@ int sv_ed25519_decide_txbodies_device(int device, const uint8_t* network_id, con
                                       const void* d_hint, const void* d_sig, size_t n_sigs,
                                       const uint64_t* d_key_begin, const void* d_key, size_t n_keys,
                                       const sv_txchecks* ck, const sv_txresults* res, void* d_digests, void* stream) {
-  if (!res) return fail(SV_ERR_INVALID_ARG, "tx results: null struct");
-  return check_device(device, network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin, d_hint,
-                      d_sig, n_sigs, d_key_begin, d_key, n_keys, ck, nullptr, nullptr, nullptr, res, d_digests, stream);
-}
-
-// sv_ed25519_check_txbodies_accounts and, with `res`, sv_ed25519_decide_txbodies_accounts.
-static int accounts_host(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
-                         const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
-                         const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig, size_t n_sigs,
-                         const sv_txaccounts* A, uint8_t* check_ok, uint32_t* check_weight, uint64_t* check_used,
-                         const sv_txresults* res, uint8_t* digests, const sv_opts* opts) {
-  LifeGuard life_;
-  int rc = check_opts(opts);
-  if (rc) return rc;
-  if (res && (rc = results_args(res))) return rc;
-  // (the per-account row counts come out of the argument check: made once, used by every slot's planner)
-  std::vector<uint32_t> acnt(2);
-  if (A && A->struct_size >= sizeof(sv_txaccounts) && !((uint64_t)A->n_accounts >> 32)) {
-    try {
-      acnt.resize(2 * A->n_accounts + 2);
-    } catch (const std::bad_alloc&) {
-      return fail(SV_ERR_ALLOC, "tx checks by account: no memory for the per-account row counts");
-    }
-  }
-  if (sv_txaccounts_check(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, n_sigs, A,
-                          res ? (const uint8_t*)&kPresent : check_ok, res ? (const uint32_t*)&kPresent : check_weight,
-                          res ? &kPresent : check_used, acnt.data()))
-    return fail(SV_ERR_INVALID_ARG,
-                "tx checks by account: null pointer, body kind > 2, malformed CSR array, bacct entry >= n_accounts, "
-                "check_acct outside its body, level > 3, signer type > 3, payload index >= n_apayloads, apayload_len "
-                "or sig_len > 64, more than 64 signatures in a body with checks or signers in an account's expanded "
-                "list, protocol 7, 2^32 or more rows, or a struct_size that is too small");
-  if (res && (rc = results_check(res, n_bodies, A->n_checks))) return rc;
-  if (n_bodies == 0) {
-    if (res) sv_txresults_bad_list(res, 0);
-    return SV_OK;
-  }
-  if ((rc = debug_fail())) return rc;
-  if ((rc = ensure_init())) return rc;
-  std::vector<Device*> devs;
-  if ((rc = select_devices(opts, n_sigs, devs))) return rc;
-  const int path = path_from_flags(opts ? opts->flags : 0u);
-  const AcctIn in{{network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, nullptr, nullptr},
-                  A->sig_len,     A->bacct_begin,  A->bacct,   A->check_begin, A->check_acct,
-                  A->check_level, A->check_needed, acnt.data()};
-  const int clamp = A->protocol_version >= 10;
-  ResultOut ro{};
-  if (res) ro = ResultOut{res->check_role, res->body_flags, res->body_code, res->body_fail};
-  const CheckOut out{check_ok, check_weight, check_used, digests, res ? &ro : nullptr};
-  const size_t G = devs.size();
-  if (G == 1) {
-    rc = acct_slice(*devs[0], in, *A, 0, n_bodies, clamp, out, path);
-  } else {
-    // (slices of whole bodies as in sv_ed25519_check_txbodies; every slot takes the whole account table)
-    const std::vector<size_t> cut = pair_slices(sig_begin, n_bodies, G);
-    rc = shard(devs, G, [&](Device& D, size_t g, size_t) {
-      if (cut[g] == cut[g + 1]) return SV_OK;
-      return acct_slice(D, in, *A, cut[g], cut[g + 1], clamp, out, path);
-    });
-  }
-  if (rc == SV_OK && res) sv_txresults_bad_list(res, n_bodies);
-  return rc;
+  return !res ? no_results()
+              : check_device(device,
+                             {network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin, d_hint,
+                              d_sig, n_sigs, d_key_begin, d_key, n_keys},
+                             ck, decide_outputs(res), res, d_digests, stream);
 }
 
 int sv_ed25519_check_txbodies_accounts(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
@@ -1206,8 +1259,9 @@ int sv_ed25519_check_txbodies_accounts(const uint8_t* network_id, const uint8_t*
                                        size_t n_sigs, const sv_txaccounts* A, uint8_t* check_ok,
                                        uint32_t* check_weight, uint64_t* check_used, uint8_t* digests,
                                        const sv_opts* opts) {
-  return accounts_host(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, n_sigs, A,
-                       check_ok, check_weight, check_used, nullptr, digests, opts);
+  return accounts_host({network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, nullptr,
+                        nullptr},
+                       n_sigs, A, {check_ok, check_weight, check_used}, nullptr, digests, opts);
 }
 
 int sv_ed25519_decide_txbodies_accounts(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
@@ -1215,116 +1269,10 @@ int sv_ed25519_decide_txbodies_accounts(const uint8_t* network_id, const uint8_t
                                         const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig,
                                         size_t n_sigs, const sv_txaccounts* A, const sv_txresults* res,
                                         uint8_t* digests, const sv_opts* opts) {
-  if (!res) return fail(SV_ERR_INVALID_ARG, "tx results: null struct");
-  const bool whole = res->struct_size >= sizeof(sv_txresults);
-  return accounts_host(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, n_sigs, A,
-                       whole ? res->check_ok : nullptr, whole ? res->check_weight : nullptr,
-                       whole ? res->check_used : nullptr, res, digests, opts);
-}
-
-// sv_ed25519_check_txbodies_accounts_device and, with `res`, sv_ed25519_decide_txbodies_accounts_device.
-static int accounts_device(int device, const uint8_t* network_id, const void* d_bodies, const uint64_t* d_body_off,
-                           const uint32_t* d_body_len, const uint8_t* d_body_kind, size_t n_bodies,
-                           const uint64_t* d_sig_begin, const void* d_hint, const void* d_sig, size_t n_sigs,
-                           const sv_txaccounts* A, void* d_check_ok, uint32_t* d_check_weight, uint64_t* d_check_used,
-                           const sv_txresults* res, void* d_digests, void* stream) {
-  LifeGuard life_;
-  int rc;
-  if (res) {
-    if ((rc = decide_device_args(res, n_bodies))) return rc;
-    d_check_ok = res->check_ok ? (void*)res->check_ok : (void*)&kPresent;
-    d_check_weight = res->check_weight ? res->check_weight : (uint32_t*)&kPresent;
-    d_check_used = res->check_used ? res->check_used : (uint64_t*)&kPresent;
-  }
-  if (!network_id || !A || A->struct_size < sizeof(sv_txaccounts))
-    return fail(SV_ERR_INVALID_ARG, "tx checks by account: null pointer or a struct_size that is too small");
-  const size_t na = A->n_accounts, ns = A->n_asigners, np = A->n_apayloads, ne = A->n_bacct, nc = A->n_checks;
-  if ((n_bodies && (!d_bodies || !d_body_off || !d_body_len || !d_body_kind || !d_sig_begin || !A->bacct_begin ||
-                    !A->check_begin)) ||
-      (n_sigs && (!d_hint || !d_sig)) || (na && (!A->acct_key || !A->acct_thresholds || !A->asigner_begin)) ||
-      (ns && (!A->asigner_type || !A->asigner_weight || !A->asigner_key)) ||
-      (np && (!A->apayload || !A->apayload_len)) || (ne && !A->bacct) ||
-      (nc && (n_bodies == 0 || !A->check_acct || !A->check_level || !d_check_ok || !d_check_weight || !d_check_used)))
-    return fail(SV_ERR_INVALID_ARG, "tx checks by account: null pointer");
-  if (A->protocol_version == 7) return fail(SV_ERR_INVALID_ARG, "tx checks by account: protocol 7 needs no engine");
-  if ((uint64_t)n_sigs >> 32 || (uint64_t)na >> 32 || (uint64_t)ns >> 32 || (uint64_t)np >> 32 ||
-      (uint64_t)ne >> 32 || (uint64_t)nc >> 32)
-    return fail(SV_ERR_INVALID_ARG, "tx checks by account: 2^32 or more rows");
-  if (!aligned16(d_sig) || !aligned16(d_digests) || !aligned16(A->acct_key) || !aligned16(A->asigner_key) ||
-      !aligned16(A->apayload) || ((uintptr_t)d_hint & 3u) || ((uintptr_t)A->asigner_begin & 7u) ||
-      ((uintptr_t)A->bacct_begin & 7u) || ((uintptr_t)A->check_begin & 7u) || ((uintptr_t)A->asigner_weight & 3u) ||
-      ((uintptr_t)A->asigner_payload & 3u) || ((uintptr_t)A->bacct & 3u) || ((uintptr_t)A->check_acct & 3u) ||
-      ((uintptr_t)A->check_needed & 3u) || ((uintptr_t)d_check_weight & 3u) || ((uintptr_t)d_check_used & 7u))
-    return fail(SV_ERR_ALIGN,
-                "sig/digests/acct_key/asigner_key/apayload must be 16-byte aligned, the other arrays naturally aligned");
-  if ((rc = debug_fail())) return rc;
-  Device* Dp;
-  if ((rc = slot_arg(device, Dp))) return rc;
-  Device& D = *Dp;
-  if (n_bodies == 0) return res ? decide_device_empty(res, stream) : SV_OK;
-  hipStream_t user = (hipStream_t)stream;
-  std::lock_guard<std::mutex> g(D.mu);
-  SV_HIP(hipSetDevice(D.phys));
-  if ((rc = ready_locked(D))) return rc;
-  DevDecide dec;
-  if (res && (rc = decide_device_bufs(D, res, n_bodies, nc, &d_check_ok, &d_check_weight, &d_check_used, &dec)))
-    return rc;
-  const sv_acct_tab T{A->acct_key,       A->acct_thresholds, A->asigner_begin,   A->asigner_type,
-                      A->asigner_weight, A->asigner_key,     A->asigner_payload, A->apayload,
-                      A->apayload_len,   na,                 ns,                 np};
-  const sv_acct_use U{A->bacct_begin, A->bacct,        A->check_begin, A->check_acct,
-                      A->check_level, A->check_needed, n_bodies,       ne,           nc};
-  // the per-account counts and ranks, the expansion's workspace and its CSR arrays (growing drains the kernel
-  // stream), and the pinned words the totals come back in
-  const size_t tws = al16(sv_acct_tab_ws_bytes(na, ns));
-  const AcctBufs H = acct_layout(sv_acct_ws_bytes(n_bodies, ne, nc), n_bodies, nc, true, 0, 0, 0);
-  if (tws + H.head > D.txaws.cap) {
-    SV_HIP(hipStreamSynchronize(D.stream));
-    if ((rc = D.txaws.ensure(tws + H.head))) return rc;
-  }
-  if ((rc = D.h_txcnt.ensure(64))) return rc;
-  uint8_t* tab_ws = (uint8_t*)D.txaws.p;
-  uint8_t* head = tab_ws + tws;
-  SV_HIP(hipEventRecord(D.dep_in, user));
-  SV_HIP(hipStreamWaitEvent(D.stream, D.dep_in, 0));
-  sv_acct_out O = acct_out(H, head, nullptr, 0, 0, 0);
-  SV_HIP(sv_launch_acct_table(&T, tab_ws, D.stream));
-  SV_HIP(sv_launch_acct_count(&T, tab_ws, &U, &O, head, D.stream));
-  SV_HIP(hipMemcpyAsync(D.h_txcnt.p, sv_acct_totals(head, n_bodies, ne, nc), 24, hipMemcpyDeviceToHost, D.stream));
-  // the wait this form adds: the expansion's three row counts are only known on the device
-  SV_HIP(hipStreamSynchronize(D.stream));
-  const uint64_t* tot = (const uint64_t*)D.h_txcnt.p;
-  if (tot[0] >> 32 || tot[1] >> 32 || tot[2] >> 32)
-    return fail(SV_ERR_INVALID_ARG, "tx checks by account: the expansion has 2^32 or more rows");
-  const size_t nk = (size_t)tot[0], nq = (size_t)tot[1], ng = (size_t)tot[2];
-  const AcctBufs L = acct_layout(sv_acct_ws_bytes(n_bodies, ne, nc), n_bodies, nc, true, nk, nq, ng);
-  if ((rc = D.txarows.ensure(L.bytes))) return rc;  // (the stream is idle)
-  O = acct_out(L, head, (uint8_t*)D.txarows.p, nk, nq, ng);
-  SV_HIP(sv_launch_acct_fill(&T, tab_ws, &U, &O, head, D.stream));
-  // the explicit call over the expansion
-  sv_txchecks_payload P{};
-  P.checks.struct_size = sizeof(sv_txchecks_payload);
-  P.checks.protocol_version = A->protocol_version;
-  P.checks.sig_len = A->sig_len;
-  P.checks.check_begin = A->check_begin;
-  P.checks.check_needed = O.check_needed;
-  P.checks.signer_begin = O.signer_begin;
-  P.checks.signer_type = O.gtype;
-  P.checks.signer_weight = O.gweight;
-  P.checks.signer_key = O.gkey;
-  P.checks.n_checks = nc;
-  P.checks.n_signers = ng;
-  PayloadDev pl;
-  if (nq) {
-    pl.qb = O.pkey_begin;
-    pl.key = O.pkey;
-    pl.payload = O.ppay;
-    pl.len = O.plen;
-    pl.nq = nq;
-  }
-  return check_device_locked(D, network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin,
-                             d_hint, d_sig, n_sigs, O.key_begin, O.key, nk, &P.checks, pl, d_check_ok, d_check_weight,
-                             d_check_used, d_digests, stream, dec);
+  return !res ? no_results()
+              : accounts_host({network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig,
+                               nullptr, nullptr},
+                              n_sigs, A, decide_outputs(res), res, digests, opts);
 }
 
 int sv_ed25519_check_txbodies_accounts_device(int device, const uint8_t* network_id, const void* d_bodies,
@@ -1334,8 +1282,10 @@ int sv_ed25519_check_txbodies_accounts_device(int device, const uint8_t* network
                                               size_t n_sigs, const sv_txaccounts* A, void* d_check_ok,
                                               uint32_t* d_check_weight, uint64_t* d_check_used, void* d_digests,
                                               void* stream) {
-  return accounts_device(device, network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin,
-                         d_hint, d_sig, n_sigs, A, d_check_ok, d_check_weight, d_check_used, nullptr, d_digests, stream);
+  return accounts_device(device,
+                         {network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin, d_hint,
+                          d_sig, n_sigs, nullptr, nullptr, 0},
+                         A, {(uint8_t*)d_check_ok, d_check_weight, d_check_used}, nullptr, d_digests, stream);
 }
 
 int sv_ed25519_decide_txbodies_accounts_device(int device, const uint8_t* network_id, const void* d_bodies,
@@ -1344,9 +1294,11 @@ int sv_ed25519_decide_txbodies_accounts_device(int device, const uint8_t* networ
                                                const uint64_t* d_sig_begin, const void* d_hint, const void* d_sig,
                                                size_t n_sigs, const sv_txaccounts* A, const sv_txresults* res,
                                                void* d_digests, void* stream) {
-  if (!res) return fail(SV_ERR_INVALID_ARG, "tx results: null struct");
-  return accounts_device(device, network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin,
-                         d_hint, d_sig, n_sigs, A, nullptr, nullptr, nullptr, res, d_digests, stream);
+  return !res ? no_results()
+              : accounts_device(device,
+                                {network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin,
+                                 d_hint, d_sig, n_sigs, nullptr, nullptr, 0},
+                                A, decide_outputs(res), res, d_digests, stream);
 }
 
 int sv_ed25519_verify_device(int device, const void* d_pk, const void* d_sig, const void* d_msg,

@@ -12,14 +12,13 @@
 //            however many bodies and checks use it)
 //   count    blockIdx.y == 0, lane t: body t's key rows and payload candidates
 //            (sums over its account entries); blockIdx.y == 1, lane c: check
-//            c's signers and its needed weight (the check finds its body by an
-//            upper-bound search in check_begin, as sv_txcheck.hip does).  The
-//            block's sums go to psum
+//            c's signers and its needed weight (the check finds its body by
+//            scan.h's sv_csr_owner in check_begin, as sv_txcheck.hip does).
+//            The block's sums go to psum
 //   scan     one block per counted array: psum -> exclusive block offsets in
-//            place, 256 blocks per round with the running total carried from
-//            round to round (the second level of the scan; past 65 536 items
-//            it takes more than one round), the total to tot[] and to the
-//            array's last CSR word
+//            place (scan.h sv_scan_block_sums; past 65 536 items a lane sums
+//            more than one block), the total to tot[] and to the array's last
+//            CSR word
 //   begin    the count's geometry again: the block's counts scanned in LDS
 //            plus the block offset are key_begin / pkey_begin / signer_begin
 //   rows     SV_ACCT_GROUP lanes per body: the body's accounts in entry order
@@ -36,10 +35,12 @@
 #include <hip/hip_runtime.h>
 
 #include "launch.h"
+#include "scan.h"
 #include "sv_common.h"
 #include "txacct.h"
 
 #define SV_ACCTBLOCK 256
+static_assert(SV_ACCTBLOCK == SV_SCAN_BLOCK, "the shared scan (scan.h) is written for this block");
 #define SV_ACCT_GROUP 4
 
 struct sv_acctparams {
@@ -61,36 +62,6 @@ __host__ __device__ __forceinline__ uint64_t sv_acct_blocks(uint64_t n) {
   return (n + SV_ACCTBLOCK - 1) / SV_ACCTBLOCK;
 }
 
-// Exclusive scan of one value per lane over the block; *sum: the block's total.
-__device__ __forceinline__ uint64_t sv_acct_exscan(uint64_t v, uint64_t* sum) {
-  __shared__ uint64_t buf[2][SV_ACCTBLOCK];
-  const unsigned i = threadIdx.x;
-  int cur = 0;
-  buf[0][i] = v;
-  __syncthreads();
-  SV_UNROLL for (unsigned d = 1; d < SV_ACCTBLOCK; d <<= 1) {
-    const uint64_t x = buf[cur][i] + (i >= d ? buf[cur][i - d] : 0);
-    buf[cur ^ 1][i] = x;
-    cur ^= 1;
-    __syncthreads();
-  }
-  const uint64_t incl = buf[cur][i];
-  *sum = buf[cur][SV_ACCTBLOCK - 1];
-  __syncthreads();  // (the buffers are reused by the caller's next scan)
-  return incl - v;
-}
-
-// the body that owns check c: the first t with check_begin[t + 1] > c (nb: none)
-__device__ __forceinline__ uint64_t sv_acct_body_of(const sv_acct_use& U, uint64_t c) {
-  uint64_t lo = 0, hi = U.nb;
-  SV_NOUNROLL while (lo < hi) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (U.cbeg[mid + 1] <= c) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(SV_ACCTBLOCK) void sv_acct_account_kernel(sv_acctparams p) {
   const uint64_t a = (uint64_t)blockIdx.x * SV_ACCTBLOCK + threadIdx.x;
   if (a < p.T.na) sv_acct_count(p.T, a, p.acnt, p.rank);
@@ -108,23 +79,23 @@ __global__ __launch_bounds__(SV_ACCTBLOCK) void sv_acct_count_kernel(sv_acctpara
       p.cnt_k[i] = k;
       p.cnt_q[i] = q;
     }
-    (void)sv_acct_exscan(k, &sum);
+    (void)sv_block_exscan(k, &sum);
     if (threadIdx.x == 0) p.psum[blockIdx.x] = sum;
-    (void)sv_acct_exscan(q, &sum);
+    (void)sv_block_exscan(q, &sum);
     if (threadIdx.x == 0) p.psum[bb + blockIdx.x] = sum;
     return;
   }
   if (blockIdx.x >= sv_acct_blocks(p.U.nc)) return;
   uint32_t g = 0;
   if (i < p.U.nc) {
-    const uint64_t t = sv_acct_body_of(p.U, i);
+    const uint64_t t = sv_csr_owner(p.U.cbeg, p.U.nb, i);
     int32_t needed = 0;
     if (t < p.U.nb) g = sv_acct_check_count(p.T, p.U, p.acnt, t, i, &needed);
     p.cbody[i] = (uint32_t)(t < p.U.nb ? t : 0xffffffffu);
     p.cnt_g[i] = g;
     p.O.check_needed[i] = needed;
   }
-  (void)sv_acct_exscan(g, &sum);
+  (void)sv_block_exscan(g, &sum);
   if (threadIdx.x == 0) p.psum[2 * bb + blockIdx.x] = sum;
 }
 
@@ -132,16 +103,7 @@ __global__ __launch_bounds__(SV_ACCTBLOCK) void sv_acct_scan_kernel(sv_acctparam
   const uint64_t bb = sv_acct_blocks(p.U.nb), cb = sv_acct_blocks(p.U.nc);
   const unsigned w = blockIdx.x;  // 0: key rows, 1: payload candidates, 2: signers
   uint64_t* ps = p.psum + (w == 0 ? 0 : w == 1 ? bb : 2 * bb);
-  const uint64_t blocks = w == 2 ? cb : bb;
-  uint64_t carry = 0;
-  SV_NOUNROLL for (uint64_t base = 0; base < blocks; base += SV_ACCTBLOCK) {
-    const uint64_t i = base + threadIdx.x;
-    const uint64_t v = i < blocks ? ps[i] : 0;
-    uint64_t sum;
-    const uint64_t ex = sv_acct_exscan(v, &sum);
-    if (i < blocks) ps[i] = carry + ex;
-    carry += sum;
-  }
+  const uint64_t carry = sv_scan_block_sums(ps, w == 2 ? cb : bb);
   if (threadIdx.x == 0) {
     p.tot[w] = carry;
     if (w == 0) p.O.key_begin[p.U.nb] = carry;
@@ -157,8 +119,8 @@ __global__ __launch_bounds__(SV_ACCTBLOCK) void sv_acct_begin_kernel(sv_acctpara
   if (blockIdx.y == 0) {
     if (blockIdx.x >= bb) return;
     const bool live = i < p.U.nb;
-    const uint64_t k = p.psum[blockIdx.x] + sv_acct_exscan(live ? p.cnt_k[i] : 0, &sum);
-    const uint64_t q = p.psum[bb + blockIdx.x] + sv_acct_exscan(live ? p.cnt_q[i] : 0, &sum);
+    const uint64_t k = p.psum[blockIdx.x] + sv_block_exscan(live ? p.cnt_k[i] : 0, &sum);
+    const uint64_t q = p.psum[bb + blockIdx.x] + sv_block_exscan(live ? p.cnt_q[i] : 0, &sum);
     if (live) {
       p.O.key_begin[i] = k;
       p.O.pkey_begin[i] = q;
@@ -167,7 +129,7 @@ __global__ __launch_bounds__(SV_ACCTBLOCK) void sv_acct_begin_kernel(sv_acctpara
   }
   if (blockIdx.x >= sv_acct_blocks(p.U.nc)) return;
   const bool live = i < p.U.nc;
-  const uint64_t g = p.psum[2 * bb + blockIdx.x] + sv_acct_exscan(live ? p.cnt_g[i] : 0, &sum);
+  const uint64_t g = p.psum[2 * bb + blockIdx.x] + sv_block_exscan(live ? p.cnt_g[i] : 0, &sum);
   if (live) p.O.signer_begin[i] = g;
 }
 
@@ -209,10 +171,8 @@ __global__ __launch_bounds__(SV_ACCTBLOCK) void sv_acct_signers_kernel(sv_acctpa
 
 namespace {
 
-inline size_t a16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 // the table's workspace: acnt (8 na) | rank (4 ns)
-inline size_t tab_ws_bytes(uint64_t na, uint64_t ns) { return a16(8 * na) + a16(4 * ns) + 16; }
+inline size_t tab_ws_bytes(uint64_t na, uint64_t ns) { return sv_a16(8 * na) + sv_a16(4 * ns) + 16; }
 
 // a call's (or chunk's) workspace: cnt_k | cnt_q | cnt_g | cbody | erow | psum | tot, every section 16-byte aligned
 struct AcctWs {
@@ -220,12 +180,12 @@ struct AcctWs {
 };
 inline AcctWs acct_ws(uint64_t nb, uint64_t ne, uint64_t nc) {
   AcctWs w;
-  w.o_cq = a16(4 * nb);
-  w.o_cg = w.o_cq + a16(4 * nb);
-  w.o_cbody = w.o_cg + a16(4 * nc);
-  w.o_erow = w.o_cbody + a16(4 * nc);
-  w.o_psum = w.o_erow + a16(8 * ne);
-  w.o_tot = w.o_psum + a16(8 * (2 * sv_acct_blocks(nb) + sv_acct_blocks(nc)));
+  w.o_cq = sv_a16(4 * nb);
+  w.o_cg = w.o_cq + sv_a16(4 * nb);
+  w.o_cbody = w.o_cg + sv_a16(4 * nc);
+  w.o_erow = w.o_cbody + sv_a16(4 * nc);
+  w.o_psum = w.o_erow + sv_a16(8 * ne);
+  w.o_tot = w.o_psum + sv_a16(8 * (2 * sv_acct_blocks(nb) + sv_acct_blocks(nc)));
   w.bytes = w.o_tot + 32;
   return w;
 }
@@ -239,7 +199,7 @@ sv_acctparams acct_params(const sv_acct_tab& T, const void* tab_ws, const sv_acc
   p.U = U;
   p.O = O;
   p.acnt = (uint32_t*)tab_ws;
-  p.rank = (uint32_t*)((uint8_t*)tab_ws + a16(8 * T.na));
+  p.rank = (uint32_t*)((uint8_t*)tab_ws + sv_a16(8 * T.na));
   p.cnt_k = (uint32_t*)b;
   p.cnt_q = (uint32_t*)(b + w.o_cq);
   p.cnt_g = (uint32_t*)(b + w.o_cg);

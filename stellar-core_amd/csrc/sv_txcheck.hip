@@ -6,8 +6,7 @@
 // One lane per CHECK, not per body: a transaction has one check per operation
 // plus its source's, 1 to 100+, so a lane per body would repeat the imbalance
 // of the pairing kernels.  Lane c finds its body by an upper-bound binary
-// search in check_begin (bodies without checks are repeated entries and are
-// skipped by it), replays the check and writes check_ok[c], check_weight[c]
+// search in check_begin (scan.h sv_csr_owner), replays the check and writes check_ok[c], check_weight[c]
 // and check_used[c] with ordinary stores: checks are independent of one
 // another, a body's used set is the OR of its checks' masks (the caller's
 // job), so there are no atomics and no workgroup waits for another one.
@@ -28,6 +27,7 @@
 #include <hip/hip_runtime.h>
 
 #include "launch.h"
+#include "scan.h"
 #include "txcheck.h"
 
 #define SV_CHECKBLOCK 256
@@ -78,19 +78,12 @@ __device__ __forceinline__ void sv_txcheck_lane(const sv_checkparams& p) {
   const uint64_t c = (uint64_t)blockIdx.x * SV_CHECKBLOCK + threadIdx.x;
   if (c >= p.n_checks) return;
   if (SLOW && p.ok[c] != SV_TXCHECK_DEFER) return;
-  // the body: the first t with check_begin[t + 1] > c
-  uint64_t lo = 0, hi = p.n_bodies;
-  SV_NOUNROLL while (lo < hi) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (p.check_begin[mid + 1] <= c) lo = mid + 1;
-    else hi = mid;
-  }
+  const uint64_t t = sv_csr_owner(p.check_begin, p.n_bodies, c);
   sv_txcheck_result r;
   r.ok = 0;
   r.total = 0;
   r.used = 0;
-  if (lo < p.n_bodies) {  // (else: a check no body owns -- a malformed table -- is false)
-    const uint64_t t = lo;
+  if (t < p.n_bodies) {  // (else: a check no body owns -- a malformed table -- is false)
     sv_txcheck_body b;
     b.hint = p.hint;
     b.sig = p.sig;

@@ -8,8 +8,7 @@
 //          and keys, stores its number of pairs in cnt[t]; the block's sum goes
 //          to bsum[block]
 //   scan   ONE block turns bsum into exclusive block offsets and the total
-//          (each of its 256 lanes sums a contiguous run of blocks, the lane
-//          totals are scanned in LDS): no workgroup waits for another one
+//          (scan.h sv_scan_block_sums): no workgroup waits for another one
 //   fill   body t scans its block's cnt in LDS, adds the block offset: that is
 //          pair_begin[t]; it walks its signatures and keys again in the same
 //          order and writes each pair's indices and its gathered rows
@@ -34,10 +33,12 @@
 #include <hip/hip_runtime.h>
 
 #include "launch.h"
+#include "scan.h"
 #include "sv_common.h"
 #include "txcheck.h"
 
 #define SV_PAIRBLOCK 256
+static_assert(SV_PAIRBLOCK == SV_SCAN_BLOCK, "the shared scan (scan.h) is written for this block");
 
 struct sv_pairparams {
   const uint64_t* sig_begin;  // n_bodies + 1
@@ -81,26 +82,6 @@ __device__ __forceinline__ uint32_t sv_key_tail(const uint4* key, uint64_t k) {
   return ((const uint32_t*)key)[8 * k + 7];
 }
 
-// Exclusive scan of one value per lane over the block (blockDim.x ==
-// SV_PAIRBLOCK); *sum: the block's total.
-__device__ __forceinline__ uint64_t sv_block_exscan(uint64_t v, uint64_t* sum) {
-  __shared__ uint64_t buf[2][SV_PAIRBLOCK];
-  const unsigned i = threadIdx.x;
-  int cur = 0;
-  buf[0][i] = v;
-  __syncthreads();
-  SV_UNROLL for (unsigned d = 1; d < SV_PAIRBLOCK; d <<= 1) {
-    const uint64_t x = buf[cur][i] + (i >= d ? buf[cur][i - d] : 0);
-    buf[cur ^ 1][i] = x;
-    cur ^= 1;
-    __syncthreads();
-  }
-  const uint64_t incl = buf[cur][i];
-  *sum = buf[cur][SV_PAIRBLOCK - 1];
-  __syncthreads();  // (the buffers are reused by the caller's next scan)
-  return incl - v;
-}
-
 __global__ __launch_bounds__(SV_PAIRBLOCK) void sv_pair_count_kernel(sv_pairparams q) {
   const uint64_t t = (uint64_t)blockIdx.x * SV_PAIRBLOCK + threadIdx.x;
   uint64_t c = 0;
@@ -121,18 +102,7 @@ __global__ __launch_bounds__(SV_PAIRBLOCK) void sv_pair_count_kernel(sv_pairpara
 // One block: bsum[0 .. blocks) -> exclusive offsets in place, the total to
 // *total and pair_begin[n_bodies].
 __global__ __launch_bounds__(SV_PAIRBLOCK) void sv_pair_scan_kernel(sv_pairparams q, uint64_t blocks) {
-  const uint64_t per = (blocks + SV_PAIRBLOCK - 1) / SV_PAIRBLOCK;
-  const uint64_t a = per * threadIdx.x < blocks ? per * threadIdx.x : blocks;
-  const uint64_t b = a + per < blocks ? a + per : blocks;
-  uint64_t mine = 0;
-  SV_NOUNROLL for (uint64_t i = a; i < b; ++i) mine += q.bsum[i];
-  uint64_t sum;
-  uint64_t run = sv_block_exscan(mine, &sum);
-  SV_NOUNROLL for (uint64_t i = a; i < b; ++i) {
-    const uint64_t v = q.bsum[i];
-    q.bsum[i] = run;
-    run += v;
-  }
+  const uint64_t sum = sv_scan_block_sums(q.bsum, blocks);
   if (threadIdx.x == 0) {
     *q.total = sum;
     q.pair_begin[q.n_bodies] = sum;
@@ -278,16 +248,23 @@ __global__ __launch_bounds__(SV_PAIRBLOCK) void sv_ppair_fill_kernel(sv_pfillpar
 
 static unsigned sv_pair_blocks(uint64_t n_bodies) { return (unsigned)((n_bodies + SV_PAIRBLOCK - 1) / SV_PAIRBLOCK); }
 
+// the pairing workspace: cnt (8 n_bodies) | bsum (8 blocks) | total (16), each 16-byte aligned
+struct sv_pair_ws {
+  size_t o_bsum, o_total, bytes;
+};
+static sv_pair_ws sv_pair_layout(uint64_t n_bodies) {
+  sv_pair_ws w;
+  w.o_bsum = (size_t)sv_a16(8 * n_bodies);
+  w.o_total = w.o_bsum + (size_t)sv_a16(8 * (uint64_t)sv_pair_blocks(n_bodies));
+  w.bytes = w.o_total + 16;
+  return w;
+}
+
 extern "C" {
 
 int sv_pair_block(void) { return SV_PAIRBLOCK; }
 
-// cnt (8 n_bodies) | bsum (8 blocks) | total (8), each 16-byte aligned
-size_t sv_pair_ws_bytes(uint64_t n_bodies) {
-  const size_t a = (size_t)((8 * n_bodies + 15) & ~(uint64_t)15);
-  const size_t b = (size_t)((8 * (uint64_t)sv_pair_blocks(n_bodies) + 15) & ~(uint64_t)15);
-  return a + b + 16;
-}
+size_t sv_pair_ws_bytes(uint64_t n_bodies) { return sv_pair_layout(n_bodies).bytes; }
 
 static sv_pairparams sv_pair_params(const uint64_t* sig_begin, const void* hint, const void* sig, uint64_t n_sigs,
                                     const uint64_t* key_begin, const void* key, uint64_t n_keys, uint64_t n_bodies,
@@ -301,12 +278,10 @@ static sv_pairparams sv_pair_params(const uint64_t* sig_begin, const void* hint,
   q.n_bodies = n_bodies;
   q.n_sigs = n_sigs;
   q.n_keys = n_keys;
-  uint8_t* w = (uint8_t*)ws;
-  q.cnt = (uint64_t*)w;
-  w += (8 * n_bodies + 15) & ~(uint64_t)15;
-  q.bsum = (uint64_t*)w;
-  w += (8 * (uint64_t)sv_pair_blocks(n_bodies) + 15) & ~(uint64_t)15;
-  q.total = (uint64_t*)w;
+  const sv_pair_ws w = sv_pair_layout(n_bodies);
+  q.cnt = (uint64_t*)ws;
+  q.bsum = (uint64_t*)((uint8_t*)ws + w.o_bsum);
+  q.total = (uint64_t*)((uint8_t*)ws + w.o_total);
   q.pair_begin = pair_begin;
   return q;
 }
@@ -327,7 +302,7 @@ hipError_t sv_launch_pair_count(const uint64_t* sig_begin, const void* hint, con
 }
 
 const uint64_t* sv_pair_total(const void* ws, uint64_t n_bodies) {
-  return sv_pair_params(nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, n_bodies, (void*)ws, nullptr).total;
+  return (const uint64_t*)((const uint8_t*)ws + sv_pair_layout(n_bodies).o_total);
 }
 
 // Fill, after sv_launch_pair_count on the same arguments and stream and after
@@ -353,7 +328,7 @@ hipError_t sv_launch_pair_fill(const uint64_t* sig_begin, const void* hint, cons
 
 // ---- payload pairing: its workspace is cnt (8 n_bodies) | bsum (8 blocks), each 16-byte aligned; its total is the
 // second word of the ed25519 pairing's total slot in `ws` (sv_pair_total(ws, n_bodies)[1])
-size_t sv_ppair_ws_bytes(uint64_t n_bodies) { return sv_pair_ws_bytes(n_bodies) - 16; }
+size_t sv_ppair_ws_bytes(uint64_t n_bodies) { return sv_pair_layout(n_bodies).o_total; }
 
 static sv_ppairparams sv_ppair_params(const uint64_t* sig_begin, const void* hint, const void* sig, uint64_t n_sigs,
                                       const uint64_t* pkey_begin, const void* pkey, const void* payload,

@@ -15,18 +15,20 @@
 //           workgroup's number of non-OK bodies -- __ballot and popcount per
 //           wave, summed through LDS -- goes to psum
 //   scan    (only with a bad list or its count) one workgroup: psum ->
-//           exclusive block offsets in place, 256 per round with the running
-//           total carried from round to round; the exact total to *n_bad
+//           exclusive block offsets in place (scan.h sv_scan_block_sums); the
+//           exact total to *n_bad
 //   fill    (only with a bad list) a wave per result workgroup: it re-reads
 //           that workgroup's body_code, ranks the non-OK bodies by __ballot and
 //           stores bad_body[offset + rank] = t where that index is < bad_cap
 #include <hip/hip_runtime.h>
 
 #include "launch.h"
+#include "scan.h"
 #include "sv_common.h"
 #include "txresult.h"
 
 #define SV_TXRBLOCK 256
+static_assert(SV_TXRBLOCK == SV_SCAN_BLOCK, "the shared scan (scan.h) is written for this block");
 #define SV_TXR_GROUP 4
 #define SV_TXR_BODIES (SV_TXRBLOCK / SV_TXR_GROUP)  // 64: one fill wave per result workgroup
 
@@ -80,36 +82,9 @@ __global__ __launch_bounds__(SV_TXRBLOCK) void sv_txresult_kernel(sv_txrparams p
   }
 }
 
-// Exclusive scan of one value per lane over the workgroup; *sum: its total.
-__device__ __forceinline__ uint64_t sv_txr_exscan(uint64_t v, uint64_t* sum) {
-  __shared__ uint64_t buf[2][SV_TXRBLOCK];
-  const unsigned i = threadIdx.x;
-  int cur = 0;
-  buf[0][i] = v;
-  __syncthreads();
-  SV_UNROLL for (unsigned d = 1; d < SV_TXRBLOCK; d <<= 1) {
-    const uint64_t x = buf[cur][i] + (i >= d ? buf[cur][i - d] : 0);
-    buf[cur ^ 1][i] = x;
-    cur ^= 1;
-    __syncthreads();
-  }
-  const uint64_t incl = buf[cur][i];
-  *sum = buf[cur][SV_TXRBLOCK - 1];
-  __syncthreads();  // (the buffers are reused by the next round)
-  return incl - v;
-}
-
 __global__ __launch_bounds__(SV_TXRBLOCK) void sv_txresult_scan_kernel(sv_txrparams p) {
   const uint64_t blocks = sv_txr_blocks(p.I.nb);
-  uint64_t carry = 0;
-  SV_NOUNROLL for (uint64_t base = 0; base < blocks; base += SV_TXRBLOCK) {
-    const uint64_t i = base + threadIdx.x;
-    const uint64_t v = i < blocks ? p.psum[i] : 0;
-    uint64_t sum;
-    const uint64_t ex = sv_txr_exscan(v, &sum);
-    if (i < blocks) p.psum[i] = carry + ex;
-    carry += sum;
-  }
+  const uint64_t carry = sv_scan_block_sums(p.psum, blocks);
   if (threadIdx.x == 0) {
     p.psum[blocks] = carry;
     if (p.n_bad) *p.n_bad = carry;
@@ -128,15 +103,11 @@ __global__ __launch_bounds__(SV_TXRBLOCK) void sv_txresult_fill_kernel(sv_txrpar
   if (at < p.cap) p.bad[at] = (uint32_t)t;
 }
 
-namespace {
-inline size_t a16(size_t x) { return (x + 15) & ~(size_t)15; }
-}  // namespace
-
 extern "C" {
 
 int sv_txresult_block(void) { return SV_TXR_BODIES; }
 
-size_t sv_txresult_ws_bytes(uint64_t n_bodies) { return a16(8 * (sv_txr_blocks(n_bodies) + 1)) + 16; }
+size_t sv_txresult_ws_bytes(uint64_t n_bodies) { return sv_a16(8 * (sv_txr_blocks(n_bodies) + 1)) + 16; }
 
 hipError_t sv_launch_txresult(const sv_txresult_in* I, uint8_t* body_code, uint32_t* body_fail, void* ws,
                               uint32_t* bad_body, uint64_t bad_cap, uint64_t* n_bad, hipStream_t s) {
