@@ -763,6 +763,62 @@ typedef struct sv_key_cache_stats {
 } sv_key_cache_stats;
 int sv_key_cache_get_stats(int device, sv_key_cache_stats* out);
 
+/* ---- Verdict cache (csrc/vcache.h, csrc/sv_vcache.hip) --------------------
+ * The twin of stellar-core's gVerifySigCache (PubKeyUtils::verifySig) for the
+ * calls whose signatures are paired and verified on the device: every
+ * sv_ed25519_verify_txbodies_hinted*, sv_ed25519_check_txbodies* and
+ * sv_ed25519_decide_txbodies* form, and sv_ed25519_verify_device_cached.  Each
+ * device slot keeps a 4-way set-associative table of verdicts in HBM, keyed by
+ * all 32 bytes of BLAKE2b-256(pk || sig || msg) (sv_verify_cache_keys); accepts
+ * and rejects are both cached.  A launch looks every item up first, verifies
+ * only the misses and inserts their verdicts.  Verdicts and every other output
+ * are the same for any capacity and any history; only the work changes.
+ *
+ *   OFF BY DEFAULT (capacity 0, or the SV_VERDICT_CACHE environment variable):
+ *   then no call allocates, launches or waits for anything more than before.
+ *   Cost: 52 bytes of device memory per entry and slot, plus a compaction
+ *   workspace of about 170 bytes per item of the largest cached launch.
+ *   While it is on, every cached launch WAITS once on the slot's kernel stream
+ *   for its miss count; the host-buffer chunk loops wait once more per chunk.
+ *   Per slot: a table only knows what its own slot verified, so a repeated
+ *   batch hits only where it is sliced over the slots the same way.
+ *   The raw host-buffer batch calls and the latency lane are not cached.
+ *
+ * sv_set_verdict_cache: entries per slot, rounded up to a power of two >= 4;
+ * 0 turns the cache off.  Drains and clears every slot (tables, workspace and
+ * counters are freed).  Above SV_VERDICT_CACHE_MAX: SV_ERR_INVALID_ARG.
+ * sv_verdict_cache_clear: empties every slot's table (clearVerifySigCache);
+ * the counters stay.  sv_verdict_cache_get_stats waits for the slot's kernel
+ * stream; the counters count since the capacity was last set
+ * (flushVerifySigCacheCounts, without the reset). */
+#define SV_VERDICT_CACHE_MAX ((size_t)1 << 24)
+int sv_set_verdict_cache(size_t entries);
+int sv_verdict_cache_clear(void);
+typedef struct sv_verdict_cache_stats {
+  uint64_t struct_size; /* in: sizeof(sv_verdict_cache_stats) of the caller */
+  uint64_t entries;     /* the capacity in force (0: off) */
+  uint64_t lookups;     /* items probed */
+  uint64_t hits;        /* ... whose verdict came from the table */
+  uint64_t inserted;    /* verdicts stored (an eviction where the set was full) */
+  uint64_t dropped;     /* misses not stored: another item of the batch won the slot */
+  uint64_t bytes;       /* device memory the slot's cache holds now */
+  double kernel_ms;     /* time of the cache's own kernels (only while sv_timing_enable is on) */
+  double wait_ms;       /* host time spent waiting for miss counts */
+} sv_verdict_cache_stats;
+int sv_verdict_cache_get_stats(int device, sv_verdict_cache_stats* out);
+/* sv_ed25519_verify_device behind the slot's verdict cache: the same inputs
+ * (d_pk, d_sig 16-byte aligned), the same d_verdict bytes and d_bitmap.
+ * d_hit (optional, n bytes): 1 where the verdict came from the table, all 0
+ * with the cache off.  d_keys (optional, n x 32, 16-byte aligned): the cache
+ * keys.  Stream semantics as sv_ed25519_verify_txbodies_hinted_device: with the
+ * cache on the call WAITS once on `stream`, for the miss count.  Always the bulk
+ * route, at any n (the latency lane is not cached). */
+int sv_ed25519_verify_device_cached(int device, const void* d_pk, const void* d_sig, const void* d_msg,
+                                    const uint64_t* d_msg_off, const uint32_t* d_msg_len,
+                                    uint32_t fixed_msg_len, size_t n, void* d_verdict, void* d_bitmap,
+                                    void* d_hit /* optional, n bytes */, void* d_keys /* optional, n x 32 */,
+                                    void* stream);
+
 /* Host-side stages of the calling thread's last latency-lane batch (a batch of
  * at most one staging chunk on one slot), in microseconds: out[0] plan + pack,
  * [1] the H2D call (0 while the kernels read the image in place), [2] the kernel launch, [3] the D2H / event record calls,

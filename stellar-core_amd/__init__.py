@@ -79,6 +79,8 @@ EXPORTED_SYMBOLS = (
     "sv_ed25519_decide_txbodies", "sv_ed25519_decide_txbodies_device", "sv_ed25519_decide_txbodies_cpu",
     "sv_ed25519_decide_txbodies_accounts", "sv_ed25519_decide_txbodies_accounts_device",
     "sv_ed25519_decide_txbodies_accounts_cpu",
+    "sv_set_verdict_cache", "sv_verdict_cache_clear", "sv_verdict_cache_get_stats",
+    "sv_ed25519_verify_device_cached",
 )
 
 # per-body result codes, check roles and body flags of the decide entry points (include/stellar_sigverify.h)
@@ -157,6 +159,12 @@ class KeyCacheStats(ctypes.Structure):
                                                 "table_clears", "table_slots")]
 
 
+class VerdictCacheStats(ctypes.Structure):
+    _fields_ = ([(f, ctypes.c_uint64) for f in ("struct_size", "entries", "lookups", "hits", "inserted", "dropped",
+                                                 "bytes")]
+                + [("kernel_ms", ctypes.c_double), ("wait_ms", ctypes.c_double)])
+
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -212,6 +220,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.sv_set_key_tables.argtypes = [ctypes.c_int, sz]
     lib.sv_key_cache_wait.argtypes = [ctypes.c_int]
     lib.sv_key_cache_get_stats.argtypes = [ctypes.c_int, ctypes.POINTER(KeyCacheStats)]
+    lib.sv_set_verdict_cache.argtypes = [sz]
+    lib.sv_verdict_cache_get_stats.argtypes = [ctypes.c_int, ctypes.POINTER(VerdictCacheStats)]
+    lib.sv_ed25519_verify_device_cached.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_uint32, sz, vp, vp,
+                                                    vp, vp, vp]
     lib.sv_lat_last_trace.argtypes = [ctypes.POINTER(ctypes.c_double)]
     lib.sv_host_feed_probe.argtypes = [vp, vp, vp, ctypes.c_uint32, sz, ctypes.c_uint32, ctypes.c_int,
                                        ctypes.POINTER(FeedStats)]
@@ -1125,6 +1137,54 @@ def key_cache_stats(device: int = 0) -> dict:
     st = KeyCacheStats()
     _check(load_library().sv_key_cache_get_stats(device, ctypes.byref(st)))
     return {f: int(getattr(st, f)) for f, _ in KeyCacheStats._fields_}
+
+
+VERDICT_CACHE_MAX = 1 << 24
+
+
+def set_verdict_cache(entries: int) -> None:
+    """Entries of every slot's verdict cache (include/stellar_sigverify.h sv_set_verdict_cache): rounded up to a
+    power of two >= 4, 0 (the default) off.  Drains and clears every slot."""
+    entries = int(entries)
+    if entries < 0 or entries > VERDICT_CACHE_MAX:
+        raise ValueError("verdict cache entries must be in [0, 2^24]")
+    _check(load_library().sv_set_verdict_cache(entries))
+
+
+def verdict_cache_clear() -> None:
+    """Empties every slot's verdict cache (the twin of clearVerifySigCache); the counters stay."""
+    _check(load_library().sv_verdict_cache_clear())
+
+
+def verdict_cache_stats(device: int = 0) -> dict:
+    """The slot's verdict-cache counters since the capacity was last set; waits for the slot's kernel stream."""
+    st = VerdictCacheStats()
+    st.struct_size = ctypes.sizeof(VerdictCacheStats)
+    _check(load_library().sv_verdict_cache_get_stats(device, ctypes.byref(st)))
+    out = {f: int(getattr(st, f)) for f, _ in VerdictCacheStats._fields_[:7]}
+    out["kernel_ms"], out["wait_ms"] = float(st.kernel_ms), float(st.wait_ms)
+    return out
+
+
+def verify_device_cached(device: int, d_pk: int, d_sig: int, d_msg: int, n: int, d_verdict: int,
+                         d_bitmap: int = 0, d_hit: int = 0, d_keys: int = 0, stream: int = 0,
+                         fixed_msg_len: int = 32, d_msg_off: int = 0, d_msg_len: int = 0) -> None:
+    """verify_device behind the slot's verdict cache (raw device pointers).  d_hit (optional, n bytes): 1 where
+    the verdict came from the cache; d_keys (optional, n x 32, 16-byte aligned): the cache keys.  With the cache
+    on the call waits once on `stream`, for the miss count."""
+    n, fixed_msg_len = int(n), int(fixed_msg_len)
+    if n < 0 or fixed_msg_len < 0 or fixed_msg_len >> 32:
+        raise ValueError("n and fixed_msg_len must be non-negative (fixed_msg_len below 2^32)")
+    if n and not (d_pk and d_sig and d_msg and d_verdict):
+        raise ValueError("d_pk, d_sig, d_msg and d_verdict must be device pointers")
+    if n and fixed_msg_len == 0 and not (d_msg_off and d_msg_len):
+        raise ValueError("variable-length messages need d_msg_off and d_msg_len")
+    if (d_pk | d_sig | d_keys) & 15:
+        raise ValueError("d_pk, d_sig and d_keys must be 16-byte aligned")
+    lib = load_library()
+    _check(lib.sv_ed25519_verify_device_cached(device, d_pk, d_sig, d_msg, d_msg_off or None, d_msg_len or None,
+                                               fixed_msg_len, n, d_verdict, d_bitmap or None, d_hit or None,
+                                               d_keys or None, stream or None))
 
 
 LAT_TRACE_FIELDS = ("plan_pack_us", "h2d_call_us", "launch_us", "d2h_rec_us", "build_us", "sync_us", "total_us", "warm")

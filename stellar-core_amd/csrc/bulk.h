@@ -3,6 +3,13 @@
 // pipeline (host_slice), its kernel-less probe (feed_slice), SHA-256 batches
 // (sha_slice), tx-body batches (tx_slice) and hinted tx-body batches, paired
 // by hint on the device (hinted_slice).  Included by sv_api.cpp.
+//
+// The pairs of the hinted, check and decide forms are verified behind the
+// slot's verdict cache (launch_cached_locked; off by default).  While it is on,
+// every verify launch of those forms waits once more on the kernel stream, for
+// its miss count: in the host-buffer chunk loops that is one more wait per
+// chunk (two where the chunk has payload pairs), behind the one for its pair
+// count, and it also waits out the previous chunk's verify launch.
 #pragma once
 
 #include <chrono>
@@ -15,6 +22,7 @@
 #include "host_image.h"
 #include "txacct.h"
 #include "txresult.h"
+#include "vcache.h"
 
 namespace sv {
 namespace {
@@ -185,6 +193,153 @@ inline int presize_ws(Device& D, int path, size_t m) {
   const int rp = resolve_path(path, m);
   return ensure_ws(D, std::max(sv_verify_ws_bytes(rp, grid_for(D, m), m),
                                sv_verify_ws_bytes(launch_geometry(rp, m), grid_for(D, m), m)));
+}
+
+// ---------------------------------------------------- verdict cache
+// sv_set_verdict_cache: entries per slot, 0 (the default) off; ~0: SV_VERDICT_CACHE, read once.  Rounded up to
+// a power of two >= 4 (one set), at most SV_VC_MAX_ENTRIES.
+inline std::atomic<size_t> g_vc_entries{~(size_t)0};
+inline size_t vc_round(size_t v) {
+  if (!v) return 0;
+  size_t p = SV_VC_WAYS;
+  while (p < v && p < SV_VC_MAX_ENTRIES) p <<= 1;
+  return p;
+}
+inline size_t vc_entries() {
+  const size_t v = g_vc_entries.load();
+  if (v != ~(size_t)0) return v;
+  static const size_t e = vc_round(env_size("SV_VERDICT_CACHE", 0));
+  return e;
+}
+
+// An empty table: all-zero entries, every claim word SV_VC_UNCLAIMED (on D.stream; the counters stay).
+inline int vc_clear_locked(Device& D) {
+  VerdictCache& C = D.vc;
+  if (!C.entries) return SV_OK;
+  SV_HIP(hipMemsetAsync(C.tab.p, 0, C.entries * sizeof(sv_vc_entry), D.stream));
+  SV_HIP(hipMemsetAsync(C.claim.p, 0xFF, C.entries * 4, D.stream));
+  return SV_OK;
+}
+// The slot's table at the capacity in force (caller holds D.mu, device set): a changed capacity drains the kernel
+// stream, frees the old table with its workspace and counters, and allocates an empty one.
+inline int vc_prepare(Device& D) {
+  VerdictCache& C = D.vc;
+  const size_t want = vc_entries();
+  if (C.entries == want) return SV_OK;
+  SV_HIP(hipStreamSynchronize(D.stream));
+  C.release();
+  if (!want) return SV_OK;
+  int rc;
+  if ((rc = C.tab.ensure(want * sizeof(sv_vc_entry))) || (rc = C.claim.ensure(want * 4)) ||
+      (rc = C.counters.ensure(32)) || (rc = C.h_cnt.ensure(64))) {
+    C.release();
+    return rc;
+  }
+  C.entries = want;
+  if ((rc = vc_clear_locked(D)) || hipMemsetAsync(C.counters.p, 0, 32, D.stream) != hipSuccess) {
+    C.release();
+    return rc ? rc : fail(SV_ERR_HIP, "verdict cache: clearing the counters");
+  }
+  return SV_OK;
+}
+
+// The compaction workspace of a cached launch of n in C.ws: keys (32 n, unless the caller has an array for
+// them) | miss list | candidate slots (4 n each) | block sums | missed bytes | compacted verdicts (n each) |
+// compacted keys (32 n) | signatures (64 n) | messages (32 n; fixed 32-byte messages) or offsets (8 n) and
+// lengths (4 n), every section 16-byte aligned.
+struct VcBufs {
+  size_t o_keys, o_miss, o_slot, o_psum, o_missed, o_cv, o_pk, o_sig, o_msg, o_len, bytes;
+};
+inline VcBufs vc_layout(size_t n, bool own_keys, bool fixed32) {
+  VcBufs b;
+  b.o_keys = 0;
+  b.o_miss = own_keys ? 32 * n : 0;
+  b.o_slot = b.o_miss + al16(4 * n);
+  b.o_psum = b.o_slot + al16(4 * n);
+  b.o_missed = b.o_psum + al16(sv_vc_psum_bytes(n));
+  b.o_cv = b.o_missed + al16(n);
+  b.o_pk = b.o_cv + al16(n);
+  b.o_sig = b.o_pk + 32 * n;
+  b.o_msg = b.o_sig + 64 * n;
+  b.o_len = b.o_msg + (fixed32 ? 32 * n : al16(8 * n));
+  b.bytes = b.o_len + (fixed32 ? 0 : al16(4 * n)) + 16;
+  return b;
+}
+
+// launch_locked behind the slot's verdict cache (vcache.h): the same arguments, the same verdict bytes and
+// bitmap.  With the cache off -- the default -- or under SV_DBG_PREP_ONLY (no verdicts exist, so nothing may be
+// inserted) it IS launch_locked: no allocation, no kernel and no wait of its own.  With it on, all on D.stream:
+// cache keys -> probe -> scan, fill, gather -> the miss count back in an 8-byte copy and ONE WAIT on D.stream
+// (as tx_counted's callers wait for the pair count) -> launch_locked over the compacted misses, skipped when
+// there are none -> scatter and claim -> store -> bitmap.  Always the bulk route: the latency lane neither reads
+// nor writes the table.  Nothing before the claim kernel writes the table or its claim words, so an error return
+// up to there leaves the cache as it was.  hit (optional): n bytes, 1 where the verdict came from the table (all 0
+// with the cache off); keys (optional, 16-byte aligned): n x 32, the cache keys (written with the cache off too).
+inline int launch_cached_locked(Device& D, int mode, int path, const void* pk, const void* sig, const void* msg,
+                                const uint64_t* off, const uint32_t* len, uint32_t fixed_len, uint64_t n,
+                                void* verdict, void* bitmap, bool tables = false, uint32_t kp = 0,
+                                void* hit = nullptr, void* keys = nullptr) {
+  int rc;
+  if (!vc_entries() || (g_dbg.load() & SV_DBG_PREP_ONLY) || n == 0 || n > SV_VC_MAX_ITEMS) {
+    if (hit && n) SV_HIP(hipMemsetAsync(hit, 0, n, D.stream));
+    if (keys && n) SV_HIP(sv_launch_hash(0, D.grid * 2, pk, sig, msg, off, len, fixed_len, n, keys, D.stream));
+    return launch_locked(D, mode, path, pk, sig, msg, off, len, fixed_len, n, verdict, bitmap, tables, kp);
+  }
+  VerdictCache& C = D.vc;
+  if ((rc = vc_prepare(D))) return rc;
+  const bool f32 = fixed_len == 32;
+  const VcBufs L = vc_layout(n, !keys, f32);
+  if (L.bytes > C.ws.cap) {
+    SV_HIP(hipStreamSynchronize(D.stream));  // (a running pass reads the old one)
+    if ((rc = C.ws.ensure(L.bytes))) return rc;
+  }
+  uint8_t* w = (uint8_t*)C.ws.p;
+  sv_vc_args A;
+  A.tab = (sv_vc_entry*)C.tab.p;
+  A.claim = (uint32_t*)C.claim.p;
+  A.sets = C.entries / SV_VC_WAYS;
+  A.counters = (uint64_t*)C.counters.p;
+  A.pk = pk;
+  A.sig = sig;
+  A.msg = msg;
+  A.off = off;
+  A.len = len;
+  A.fixed_len = fixed_len;
+  A.n = n;
+  A.keys = (const uint32_t*)(keys ? keys : w + L.o_keys);
+  A.verdict = (uint8_t*)verdict;
+  A.hit = (uint8_t*)hit;
+  A.missed = w + L.o_missed;
+  A.psum = (uint64_t*)(w + L.o_psum);
+  A.miss = (uint32_t*)(w + L.o_miss);
+  A.slot = (uint32_t*)(w + L.o_slot);
+  A.cpk = w + L.o_pk;
+  A.csig = w + L.o_sig;
+  A.cmsg = f32 ? w + L.o_msg : nullptr;
+  A.coff = f32 ? nullptr : (uint64_t*)(w + L.o_msg);
+  A.clen = f32 ? nullptr : (uint32_t*)(w + L.o_len);
+  A.cverdict = w + L.o_cv;
+  if ((rc = C.timer.begin(D.stream))) return rc;
+  SV_HIP(sv_launch_hash(0, D.grid * 2, pk, sig, msg, off, len, fixed_len, n, (void*)A.keys, D.stream));
+  SV_HIP(sv_launch_vc_probe(&A, D.stream));
+  if ((rc = C.timer.end(D.stream, n))) return rc;
+  SV_HIP(hipMemcpyAsync(C.h_cnt.p, A.counters + 3, 8, hipMemcpyDeviceToHost, D.stream));
+  // the one wait: how many items the verify launch has is only known on the device
+  const auto t0 = std::chrono::steady_clock::now();
+  SV_HIP(hipStreamSynchronize(D.stream));
+  C.wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  C.lookups += n;
+  const uint64_t nm = *(const uint64_t*)C.h_cnt.p;
+  if (nm > n) return fail(SV_ERR_HIP, "verdict cache: miss count beyond the batch");
+  // (the compacted arrays are device memory: the in-place hints of kp do not apply to them)
+  if (nm && (rc = launch_locked(D, f32 ? 0 : 1, path, A.cpk, A.csig, f32 ? (const void*)A.cmsg : msg, A.coff, A.clen,
+                                f32 ? 32 : 0, nm, A.cverdict, nullptr, tables, 0)))
+    return rc;
+  if (!nm && !bitmap) return SV_OK;
+  if ((rc = C.timer.begin(D.stream))) return rc;
+  SV_HIP(sv_launch_vc_insert(&A, nm, D.stream));
+  if (bitmap) SV_HIP(sv_launch_vc_bitmap(verdict, n, bitmap, D.stream));
+  return C.timer.end(D.stream, 0);
 }
 
 // H2D of a whole packed image.  While latency-lane batches are live (shared
@@ -801,8 +956,8 @@ inline int tx_enqueue_pairs(Device& D, const TxDev& T, const TxBufs& B, size_t n
   SV_HIP(sv_launch_pair_fill(h.sb, h.hint, h.sig, h.m, h.kb, h.key, h.q, h.nb, B.ws, B.pair_begin, np, pair_sig,
                              pair_key, D.txpk.p, D.txsg.p, D.txmsg.p, T.digests, D.stream));
   if (!np || !verdict) return SV_OK;
-  return launch_locked(D, 0, path, D.txpk.p, D.txsg.p, D.txmsg.p, nullptr, nullptr, 32, np, verdict, bitmap,
-                       kt_mode() == 1);
+  return launch_cached_locked(D, 0, path, D.txpk.p, D.txsg.p, D.txmsg.p, nullptr, nullptr, 32, np, verdict, bitmap,
+                              kt_mode() == 1);
 }
 
 // Enqueue-decide, on D.stream after the counts came back: the fill and the verify launch, the payload pairs' fill
@@ -824,8 +979,8 @@ inline int tx_enqueue_decide(Device& D, const TxDev& T, const TxBufs& B, size_t 
     SV_HIP(sv_launch_ppair_fill(h.sb, h.hint, h.sig, h.m, T.pl.qb, T.pl.key, T.pl.payload, T.pl.len, T.pl.nq, h.nb, B.ws,
                                 B.pws, B.ppair_begin, npp, d_pps, d_pps + npp, b + L.o_key, b + L.o_sig, b + L.o_msg,
                                 (uint64_t*)(b + L.o_off), (uint32_t*)(b + L.o_len), D.stream));
-    if ((rc = launch_locked(D, 1, path, b + L.o_key, b + L.o_sig, b + L.o_msg, (const uint64_t*)(b + L.o_off),
-                            (const uint32_t*)(b + L.o_len), 0, npp, b, nullptr)))
+    if ((rc = launch_cached_locked(D, 1, path, b + L.o_key, b + L.o_sig, b + L.o_msg, (const uint64_t*)(b + L.o_off),
+                                   (const uint32_t*)(b + L.o_len), 0, npp, b, nullptr)))
       return rc;
   }
   SV_HIP(sv_launch_txcheck_payload(h.sb, h.hint, h.sig, c.sig_len, h.m, h.kb, h.key, h.q, h.nb, B.pair_begin, d_ps, d_pk,

@@ -1,5 +1,5 @@
 // State of the engine: error reporting, device and pinned buffers, the
-// staging slots, the latency lane's contexts, the per-key tables, the Device
+// staging slots, the latency lane's contexts, the per-key tables, the verdict cache, the Device
 // slot with the creation and release of its resources, the slot table and the
 // process-wide settings.  Included by sv_api.cpp (and by bulk.h and latlane.h,
 // which work on this state).
@@ -270,6 +270,29 @@ struct KeyTabs {
   uint64_t launches = 0, clears = 0, claims = 0;
 };
 
+// The verdict cache of a slot (vcache.h, sv_vcache.hip; bulk.h launch_cached_locked): the table, its claim words,
+// the device counters (hits | inserted | dropped | the pass's miss count), the pinned word the miss count comes
+// back in and the compaction workspace of the largest cached launch so far.  Allocated on the first cached launch
+// after a non-zero capacity was set (sv_set_verdict_cache); touched only by kernels on D.stream, under D.mu.
+struct VerdictCache {
+  DevBuf tab, claim, counters, ws;
+  HostBuf h_cnt;
+  size_t entries = 0;    // entries of `tab` (0: not allocated)
+  uint64_t lookups = 0;  // items probed
+  double wait_ms = 0;    // host time spent waiting for miss counts
+  KernelTimer timer;     // the cache's own kernels (keys, probe, scan, fill, gather; claim, store, bitmap)
+  size_t bytes() const { return tab.cap + claim.cap + counters.cap + ws.cap; }
+  // (D.stream is drained)
+  void release() {
+    tab.release(); claim.release(); counters.release(); ws.release(); h_cnt.release();
+    timer.release();
+    timer.reset();
+    entries = 0;
+    lookups = 0;
+    wait_ms = 0;
+  }
+};
+
 struct Device {
   int slot = -1;
   int phys = -1;
@@ -301,6 +324,7 @@ struct Device {
   KernelTimer timer;  // the bulk launches (launch_locked)
   LatLane lat;
   KeyTabs kt;  // (under mu)
+  VerdictCache vc;  // (under mu)
   std::atomic<int64_t> lat_last_ns{INT64_MIN / 2};  // steady clock of the last latency-lane batch
   std::atomic<uint64_t> shared_launches{0};          // bulk launches in shared mode
   // The slot's own staging workers for multi-slot calls (shard): its slice is
@@ -422,6 +446,7 @@ inline void release_device(Device& D) {
   if (D.kt.copied) (void)hipEventDestroy(D.kt.copied);
   D.kt.copied = nullptr;
   D.kt.slots = 0;
+  D.vc.release();
   if (D.btab) (void)hipFree(D.btab);
   if (D.dep_in) (void)hipEventDestroy(D.dep_in);
   if (D.dep_out) (void)hipEventDestroy(D.dep_out);

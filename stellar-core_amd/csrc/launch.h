@@ -1,6 +1,6 @@
 // The one declaration of every extern "C" launcher and size query that
 // crosses between the kernel files (sv_kernels.hip, sv_comb.hip, sv_hash.hip,
-// sv_txhash.hip, sv_txpair.hip, sv_txcheck.hip, sv_txacct.hip, sv_txresult.hip), sv_cpu.cpp and the engine (sv_api.cpp and its modules).
+// sv_txhash.hip, sv_txpair.hip, sv_txcheck.hip, sv_txacct.hip, sv_txresult.hip, sv_vcache.hip), sv_cpu.cpp and the engine (sv_api.cpp and its modules).
 // Included by the callers and by every definer, so a changed parameter list
 // is a compile error instead of arguments corrupted at run time.
 #pragma once
@@ -174,6 +174,18 @@ int sv_txresult_block(void);
 size_t sv_txresult_ws_bytes(uint64_t n_bodies);
 hipError_t sv_launch_txresult(const struct sv_txresult_in* I, uint8_t* body_code, uint32_t* body_fail, void* ws,
                               uint32_t* bad_body, uint64_t bad_cap, uint64_t* n_bad, hipStream_t s);
+// the verdict cache (sv_vcache.hip, vcache.h), every stage on the slot's one stream.  probe: after
+// sv_launch_hash kind 0 wrote A->keys -- the lookups (verdict and hit bytes of the hits), the scan and the fill of
+// the miss list and the compacted arrays; the miss count lands in A->counters[3].  insert: behind the verify
+// launch over the n_miss compacted rows -- the scatter of their verdicts with the claims, then the winners'
+// stores.  bitmap: the layout of sv_launch_verify's, from n final verdict bytes (bits past n are 0).  The struct
+// is host memory.
+struct sv_vc_args;
+int sv_vc_block(void);
+size_t sv_vc_psum_bytes(uint64_t n);
+hipError_t sv_launch_vc_probe(const struct sv_vc_args* A, hipStream_t s);
+hipError_t sv_launch_vc_insert(const struct sv_vc_args* A, uint64_t n_miss, hipStream_t s);
+hipError_t sv_launch_vc_bitmap(const void* verdict, uint64_t n, void* bitmap, hipStream_t s);
 // warm-key latency path (sv_comb.hip)
 size_t sv_comb_btab_bytes(void);
 size_t sv_key_slot_bytes(void);

@@ -1535,6 +1535,98 @@ int sv_key_cache_get_stats(int device, sv_key_cache_stats* out) {
   return SV_OK;
 }
 
+int sv_set_verdict_cache(size_t entries) {
+  LifeGuard life_;
+  if (entries > SV_VERDICT_CACHE_MAX) return fail(SV_ERR_INVALID_ARG, "verdict cache above 2^24 entries");
+  static_assert(SV_VERDICT_CACHE_MAX == SV_VC_MAX_ENTRIES, "the header's limit is the table's");
+  std::lock_guard<std::mutex> g0(g_mu);
+  g_vc_entries.store(vc_round(entries));
+  for (Device* D : g_devs) {
+    std::lock_guard<std::mutex> g(D->mu);
+    if (!D->ready) continue;
+    (void)hipSetDevice(D->phys);
+    (void)hipStreamSynchronize(D->stream);
+    D->vc.release();  // (the next cached launch allocates an empty table of the new size)
+  }
+  return SV_OK;
+}
+
+int sv_verdict_cache_clear(void) {
+  LifeGuard life_;
+  std::lock_guard<std::mutex> g0(g_mu);
+  for (Device* D : g_devs) {
+    std::lock_guard<std::mutex> g(D->mu);
+    if (!D->ready) continue;
+    SV_HIP(hipSetDevice(D->phys));
+    int rc;
+    if ((rc = vc_clear_locked(*D))) return rc;
+  }
+  return SV_OK;
+}
+
+int sv_verdict_cache_get_stats(int device, sv_verdict_cache_stats* out) {
+  LifeGuard life_;
+  if (!out || out->struct_size < offsetof(sv_verdict_cache_stats, kernel_ms))
+    return fail(SV_ERR_INVALID_ARG, "verdict cache stats: null struct or struct_size too small");
+  const bool timed = out->struct_size >= sizeof(sv_verdict_cache_stats);
+  Device* Dp;
+  int rc = slot_arg(device, Dp);
+  if (rc) return rc;
+  Device& D = *Dp;
+  std::lock_guard<std::mutex> g(D.mu);
+  VerdictCache& C = D.vc;
+  out->entries = vc_entries();
+  out->lookups = out->hits = out->inserted = out->dropped = out->bytes = 0;
+  if (timed) out->kernel_ms = out->wait_ms = 0;
+  if (!D.ready || !C.entries) return SV_OK;
+  SV_HIP(hipSetDevice(D.phys));
+  uint64_t* h = (uint64_t*)C.h_cnt.p + 1;  // (word 0: a pass's miss count)
+  SV_HIP(hipMemcpyAsync(h, C.counters.p, 24, hipMemcpyDeviceToHost, D.stream));
+  SV_HIP(hipStreamSynchronize(D.stream));
+  if ((rc = C.timer.harvest())) return rc;
+  out->lookups = C.lookups;
+  out->hits = h[0];
+  out->inserted = h[1];
+  out->dropped = h[2];
+  out->bytes = C.bytes();
+  if (timed) {
+    out->kernel_ms = C.timer.total_ms;
+    out->wait_ms = C.wait_ms;
+  }
+  return SV_OK;
+}
+
+int sv_ed25519_verify_device_cached(int device, const void* d_pk, const void* d_sig, const void* d_msg,
+                                    const uint64_t* d_msg_off, const uint32_t* d_msg_len, uint32_t fixed_msg_len,
+                                    size_t n, void* d_verdict, void* d_bitmap, void* d_hit, void* d_keys,
+                                    void* stream) {
+  LifeGuard life_;
+  Device* Dp;
+  int rc = slot_arg(device, Dp);
+  if (rc) return rc;
+  if (n == 0) return SV_OK;
+  if (!d_pk || !d_sig || !d_verdict || !d_msg) return fail(SV_ERR_INVALID_ARG, "null device buffer");
+  if (!aligned16(d_pk) || !aligned16(d_sig) || !aligned16(d_keys))
+    return fail(SV_ERR_ALIGN, "pk/sig/keys must be 16-byte aligned");
+  if (fixed_msg_len == 0 && (!d_msg_off || !d_msg_len)) return fail(SV_ERR_INVALID_ARG, "null msg_off/msg_len");
+  const int mode = verify_mode(fixed_msg_len == 0, fixed_msg_len, aligned16(d_msg));
+  if ((rc = debug_fail())) return rc;
+  Device& D = *Dp;
+  hipStream_t user = (hipStream_t)stream;
+  // (the call waits on the host in mid-call, so it queues its own stream dependencies: slot_call's pattern)
+  std::lock_guard<std::mutex> g(D.mu);
+  SV_HIP(hipSetDevice(D.phys));
+  if ((rc = ready_locked(D))) return rc;
+  SV_HIP(hipEventRecord(D.dep_in, user));
+  SV_HIP(hipStreamWaitEvent(D.stream, D.dep_in, 0));
+  if ((rc = launch_cached_locked(D, mode, SV_PATH_AUTO, d_pk, d_sig, d_msg, d_msg_off, d_msg_len, fixed_msg_len, n,
+                                 d_verdict, d_bitmap, kt_mode() == 1, 0, d_hit, d_keys)))
+    return rc;
+  SV_HIP(hipEventRecord(D.dep_out, D.stream));
+  SV_HIP(hipStreamWaitEvent(user, D.dep_out, 0));
+  return SV_OK;
+}
+
 int sv_workspace_bytes(int device, size_t* bytes) {
   LifeGuard life_;
   int rc = ensure_init();
@@ -1545,7 +1637,7 @@ int sv_workspace_bytes(int device, size_t* bytes) {
   std::lock_guard<std::mutex> gl(Dp->lat.mu);
   std::lock_guard<std::mutex> g(Dp->mu);
   size_t b = Dp->ws.cap + Dp->txmsg.cap + Dp->txpk.cap + Dp->txsg.cap + Dp->txpair.cap + Dp->txchk.cap + Dp->txpp.cap;
-  b += Dp->txatab.cap + Dp->txaws.cap + Dp->txarows.cap + Dp->txres.cap;
+  b += Dp->txatab.cap + Dp->txaws.cap + Dp->txarows.cap + Dp->txres.cap + Dp->vc.bytes();
   for (const LatCtx& c : Dp->lat.ctx) b += c.ws.cap + c.d_in.cap + c.d_out.cap + c.d_keys.cap;
   *bytes = b;
   return SV_OK;
