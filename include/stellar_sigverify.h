@@ -782,7 +782,12 @@ int sv_key_cache_get_stats(int device, sv_key_cache_stats* out);
  *   for its miss count; the host-buffer chunk loops wait once more per chunk.
  *   Per slot: a table only knows what its own slot verified, so a repeated
  *   batch hits only where it is sliced over the slots the same way.
- *   The raw host-buffer batch calls and the latency lane are not cached.
+ *   The raw host-buffer batch calls and the latency lane look nothing up and,
+ *   by default, store nothing.  sv_set_verdict_cache_feed (below) lets keyed
+ *   batches FEED the table: what the latency lane verified is journaled and
+ *   inserted ahead of the next cached launch, so a tx-body call over pairs
+ *   that sv_ed25519_verify_batch_keyed / _gather* already verified on this
+ *   slot is a warm pass; keyed bulk-route batches can go behind the cache.
  *
  * sv_set_verdict_cache: entries per slot, rounded up to a power of two >= 4;
  * 0 turns the cache off.  Drains and clears every slot (tables, workspace and
@@ -804,8 +809,64 @@ typedef struct sv_verdict_cache_stats {
   uint64_t bytes;       /* device memory the slot's cache holds now */
   double kernel_ms;     /* time of the cache's own kernels (only while sv_timing_enable is on) */
   double wait_ms;       /* host time spent waiting for miss counts */
+  /* the feed (sv_set_verdict_cache_feed); written only where struct_size covers them.  Journal drains move
+   * none of lookups / hits / inserted / dropped. */
+  uint64_t fed_rows;     /* rows appended to the slot's journal */
+  uint64_t fed_overflow; /* rows not appended because the journal was full */
+  uint64_t fed_present;  /* drained rows whose key the table already held */
+  uint64_t fed_inserted; /* drained rows stored */
+  uint64_t fed_dropped;  /* drained rows that lost their claim to another row of the drain */
 } sv_verdict_cache_stats;
 int sv_verdict_cache_get_stats(int device, sv_verdict_cache_stats* out);
+
+/* Feeding the verdict cache from keyed batches.  OFF BY DEFAULT (sources 0, or
+ * the SV_VERDICT_CACHE_FEED / SV_VERDICT_CACHE_JOURNAL environment variables):
+ * then every call allocates, launches, waits and returns exactly as without it.
+ * No verdict ever depends on the feed, and the table still holds only verdict
+ * bytes that a completed verify launch of this engine wrote: there is no call
+ * that inserts a verdict by key.
+ *   SV_VC_FEED_LANE  a keyed latency-lane batch (sv_ed25519_verify_batch_keyed
+ *     / _gather* with keys, at most 12,288 signatures on one slot) that returned
+ *     SV_OK appends its (key, verdict) rows to the slot's journal: a bounded
+ *     array in ordinary host memory, journal_rows rows of 33 bytes per slot
+ *     (0: 65,536 rows, 2.1 MB; at most 2^24).  A batch that does not fit
+ *     appends its leading rows, the rest counts as fed_overflow and is simply
+ *     not cached.  An error return appends nothing; an unkeyed batch appends
+ *     nothing.  The journal is DRAINED into the table -- an upload and two
+ *     kernels on the slot's bulk stream, nothing when it is empty -- ahead of
+ *     the probe of every cached launch, by sv_verdict_cache_sync and by the
+ *     lookups below.  The latency lane itself never reads or writes the table.
+ *     A drained row whose key the table holds changes nothing (fed_present);
+ *     the others are inserted by the policy of csrc/vcache.h, in journal order.
+ *   SV_VC_FEED_BULK  keyed host-buffer batches on the bulk route (more than
+ *     12,288 signatures, or a forced throughput path) run behind the cache as
+ *     the tx-body forms do: probe, verify the misses, insert.  One more wait
+ *     per chunk; verdicts, keys and the keys-ready callbacks are unchanged.
+ * sv_set_verdict_cache_feed is process-wide; it drops what the journals hold.
+ * Unknown bits, or journal_rows above 2^24: SV_ERR_INVALID_ARG.  With the cache
+ * off the setting is remembered and nothing else happens.  The journals are
+ * also dropped by sv_set_verdict_cache, sv_verdict_cache_clear,
+ * sv_set_device_map and sv_shutdown.
+ * sv_verdict_cache_sync: drains the slot's journal now and returns when the
+ * inserts are done.  With the cache off it does nothing.
+ * sv_verdict_cache_lookup*: drain, then per key the verdict the slot's table
+ * holds (0 or 1) or SV_VC_MISS.  They change nothing in the table and nothing
+ * in lookups / hits.  With the cache off every byte is SV_VC_MISS.  The host
+ * form returns when `out` is written; n == 0 is SV_OK, a null pointer
+ * SV_ERR_INVALID_ARG, and on a host without a GPU it returns the error every
+ * host form returns there (SV_ERR_NO_DEVICE), cache on or off.  The device
+ * form (d_keys n x 32 and 16-byte aligned, else SV_ERR_ALIGN; d_out n bytes)
+ * is ordered on `stream` like sv_ed25519_verify_device, does not wait for the
+ * result or for anything `stream` holds (its drain may wait on the host for the
+ * slot's own earlier work: a growing workspace, the previous drain's upload)
+ * and writes nothing outside d_out[0, n). */
+#define SV_VC_FEED_LANE 1u /* keyed latency-lane batches are journaled */
+#define SV_VC_FEED_BULK 2u /* keyed host-buffer batches on the bulk route are cached */
+int sv_set_verdict_cache_feed(uint32_t sources, size_t journal_rows);
+int sv_verdict_cache_sync(int device);
+#define SV_VC_MISS 0xFFu
+int sv_verdict_cache_lookup(int device, const uint8_t* keys /* n x 32 */, size_t n, uint8_t* out /* n */);
+int sv_verdict_cache_lookup_device(int device, const void* d_keys, size_t n, void* d_out, void* stream);
 /* sv_ed25519_verify_device behind the slot's verdict cache: the same inputs
  * (d_pk, d_sig 16-byte aligned), the same d_verdict bytes and d_bitmap.
  * d_hit (optional, n bytes): 1 where the verdict came from the table, all 0

@@ -81,6 +81,7 @@ EXPORTED_SYMBOLS = (
     "sv_ed25519_decide_txbodies_accounts_cpu",
     "sv_set_verdict_cache", "sv_verdict_cache_clear", "sv_verdict_cache_get_stats",
     "sv_ed25519_verify_device_cached",
+    "sv_set_verdict_cache_feed", "sv_verdict_cache_sync", "sv_verdict_cache_lookup", "sv_verdict_cache_lookup_device",
 )
 
 # per-body result codes, check roles and body flags of the decide entry points (include/stellar_sigverify.h)
@@ -162,7 +163,9 @@ class KeyCacheStats(ctypes.Structure):
 class VerdictCacheStats(ctypes.Structure):
     _fields_ = ([(f, ctypes.c_uint64) for f in ("struct_size", "entries", "lookups", "hits", "inserted", "dropped",
                                                  "bytes")]
-                + [("kernel_ms", ctypes.c_double), ("wait_ms", ctypes.c_double)])
+                + [("kernel_ms", ctypes.c_double), ("wait_ms", ctypes.c_double)]
+                + [(f, ctypes.c_uint64) for f in ("fed_rows", "fed_overflow", "fed_present", "fed_inserted",
+                                                  "fed_dropped")])
 
 
 _lib: Optional[ctypes.CDLL] = None
@@ -224,6 +227,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.sv_verdict_cache_get_stats.argtypes = [ctypes.c_int, ctypes.POINTER(VerdictCacheStats)]
     lib.sv_ed25519_verify_device_cached.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_uint32, sz, vp, vp,
                                                     vp, vp, vp]
+    lib.sv_set_verdict_cache_feed.argtypes = [ctypes.c_uint32, sz]
+    lib.sv_verdict_cache_sync.argtypes = [ctypes.c_int]
+    lib.sv_verdict_cache_lookup.argtypes = [ctypes.c_int, vp, sz, vp]
+    lib.sv_verdict_cache_lookup_device.argtypes = [ctypes.c_int, vp, sz, vp, vp]
     lib.sv_lat_last_trace.argtypes = [ctypes.POINTER(ctypes.c_double)]
     lib.sv_host_feed_probe.argtypes = [vp, vp, vp, ctypes.c_uint32, sz, ctypes.c_uint32, ctypes.c_int,
                                        ctypes.POINTER(FeedStats)]
@@ -1163,7 +1170,54 @@ def verdict_cache_stats(device: int = 0) -> dict:
     _check(load_library().sv_verdict_cache_get_stats(device, ctypes.byref(st)))
     out = {f: int(getattr(st, f)) for f, _ in VerdictCacheStats._fields_[:7]}
     out["kernel_ms"], out["wait_ms"] = float(st.kernel_ms), float(st.wait_ms)
+    out.update({f: int(getattr(st, f)) for f, _ in VerdictCacheStats._fields_[9:]})
     return out
+
+
+VC_FEED_LANE, VC_FEED_BULK = 1, 2
+VC_MISS = 0xFF
+
+
+def set_verdict_cache_feed(sources: int, journal_rows: int = 0) -> None:
+    """Which keyed batches feed the verdict cache (include/stellar_sigverify.h sv_set_verdict_cache_feed):
+    VC_FEED_LANE journals keyed latency-lane batches, VC_FEED_BULK runs keyed bulk-route host batches behind the
+    cache; 0 (the default) neither.  journal_rows: rows of a slot's journal (0: 65,536).  Drops what the journals
+    hold."""
+    sources, journal_rows = int(sources), int(journal_rows)
+    if sources < 0 or sources >> 32 or journal_rows < 0:
+        raise ValueError("sources must fit 32 bits and journal_rows must be non-negative")
+    _check(load_library().sv_set_verdict_cache_feed(sources, journal_rows))
+
+
+def verdict_cache_sync(device: int = 0) -> None:
+    """Drains the slot's journal into its verdict cache and waits for the inserts."""
+    _check(load_library().sv_verdict_cache_sync(device))
+
+
+def verdict_cache_lookup(keys, device: int = 0) -> np.ndarray:
+    """Per 32-byte cache key the verdict the slot's table holds (0 or 1) or VC_MISS; drains the journal first and
+    changes nothing in the table or its lookup counters."""
+    keys = np.ascontiguousarray(keys).view(np.uint8).reshape(-1)
+    if keys.size % 32:
+        raise ValueError("keys must be n x 32 bytes")
+    n = keys.size // 32
+    out = np.empty(n, np.uint8)
+    _check(load_library().sv_verdict_cache_lookup(device, keys.ctypes.data if n else None, n,
+                                                  out.ctypes.data if n else None))
+    return out
+
+
+def verdict_cache_lookup_device(device: int, d_keys: int, n: int, d_out: int, stream: int = 0) -> None:
+    """verdict_cache_lookup over device memory (raw pointers; d_keys n x 32 and 16-byte aligned, d_out n bytes),
+    ordered on `stream`; does not wait for the result."""
+    n = int(n)
+    if n < 0:
+        raise ValueError("n must be non-negative")
+    if n and not (d_keys and d_out):
+        raise ValueError("d_keys and d_out must be device pointers")
+    if d_keys & 15:
+        raise ValueError("d_keys must be 16-byte aligned")
+    _check(load_library().sv_verdict_cache_lookup_device(device, d_keys or None, n, d_out or None, stream or None))
 
 
 def verify_device_cached(device: int, d_pk: int, d_sig: int, d_msg: int, n: int, d_verdict: int,

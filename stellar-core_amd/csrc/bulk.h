@@ -10,6 +10,10 @@
 // its miss count: in the host-buffer chunk loops that is one more wait per
 // chunk (two where the chunk has payload pairs), behind the one for its pair
 // count, and it also waits out the previous chunk's verify launch.
+//
+// sv_set_verdict_cache_feed (off by default): what the slot's latency lane journaled (vjournal.h) is drained into
+// the table ahead of every cached launch's probe (vc_drain_locked), and with SV_VC_FEED_BULK the keyed chunks of
+// host_slice_locked go behind the cache too.
 #pragma once
 
 #include <chrono>
@@ -196,21 +200,7 @@ inline int presize_ws(Device& D, int path, size_t m) {
 }
 
 // ---------------------------------------------------- verdict cache
-// sv_set_verdict_cache: entries per slot, 0 (the default) off; ~0: SV_VERDICT_CACHE, read once.  Rounded up to
-// a power of two >= 4 (one set), at most SV_VC_MAX_ENTRIES.
-inline std::atomic<size_t> g_vc_entries{~(size_t)0};
-inline size_t vc_round(size_t v) {
-  if (!v) return 0;
-  size_t p = SV_VC_WAYS;
-  while (p < v && p < SV_VC_MAX_ENTRIES) p <<= 1;
-  return p;
-}
-inline size_t vc_entries() {
-  const size_t v = g_vc_entries.load();
-  if (v != ~(size_t)0) return v;
-  static const size_t e = vc_round(env_size("SV_VERDICT_CACHE", 0));
-  return e;
-}
+// (the capacity and feed settings: engine_state.h vc_entries, vc_feed)
 
 // An empty table: all-zero entries, every claim word SV_VC_UNCLAIMED (on D.stream; the counters stay).
 inline int vc_clear_locked(Device& D) {
@@ -231,12 +221,12 @@ inline int vc_prepare(Device& D) {
   if (!want) return SV_OK;
   int rc;
   if ((rc = C.tab.ensure(want * sizeof(sv_vc_entry))) || (rc = C.claim.ensure(want * 4)) ||
-      (rc = C.counters.ensure(32)) || (rc = C.h_cnt.ensure(64))) {
+      (rc = C.counters.ensure(64)) || (rc = C.h_cnt.ensure(128))) {
     C.release();
     return rc;
   }
   C.entries = want;
-  if ((rc = vc_clear_locked(D)) || hipMemsetAsync(C.counters.p, 0, 32, D.stream) != hipSuccess) {
+  if ((rc = vc_clear_locked(D)) || hipMemsetAsync(C.counters.p, 0, 64, D.stream) != hipSuccess) {
     C.release();
     return rc ? rc : fail(SV_ERR_HIP, "verdict cache: clearing the counters");
   }
@@ -266,6 +256,47 @@ inline VcBufs vc_layout(size_t n, bool own_keys, bool fixed32) {
   return b;
 }
 
+// The slot's journal (vjournal.h) into its table, on D.stream (caller holds D.mu, device set): the held rows are
+// taken, copied into the pinned h_feed and from there into the head of C.ws -- keys (32 n) | verdict bytes |
+// candidate slots (4 n) -- and the two feed kernels run over them (vcache.h Feed).  An empty journal, or the cache
+// off, enqueues nothing.  Nothing is waited for but the previous drain's upload out of h_feed (and, where C.ws
+// grows, the kernel stream); work queued on D.stream behind the drain sees the rows in the table.
+inline int vc_drain_locked(Device& D) {
+  if (!vc_entries() || !D.vj.held()) return SV_OK;
+  VerdictCache& C = D.vc;
+  int rc;
+  if ((rc = vc_prepare(D))) return rc;
+  if (!C.fed_up) SV_HIP(hipEventCreateWithFlags(&C.fed_up, hipEventDisableTiming));
+  D.vj.take(C.taken);
+  const size_t n = C.taken.rows;
+  if (!n) return SV_OK;
+  const size_t o_v = 32 * n, o_slot = o_v + al16(n), bytes = o_slot + al16(4 * n);
+  if (bytes > C.ws.cap) {
+    SV_HIP(hipStreamSynchronize(D.stream));  // (a running pass reads the old one)
+    if ((rc = C.ws.ensure(bytes))) return rc;
+  }
+  SV_HIP(hipEventSynchronize(C.fed_up));  // (never recorded: success at once)
+  if ((rc = C.h_feed.ensure(o_v + n))) return rc;
+  uint8_t* h = (uint8_t*)C.h_feed.p;
+  std::memcpy(h, C.taken.keys.data(), 32 * n);
+  std::memcpy(h + o_v, C.taken.verdicts.data(), n);
+  uint8_t* w = (uint8_t*)C.ws.p;
+  SV_HIP(hipMemcpyAsync(w, h, o_v + n, hipMemcpyHostToDevice, D.stream));
+  SV_HIP(hipEventRecord(C.fed_up, D.stream));
+  sv_vc_feed_args A;
+  A.tab = (sv_vc_entry*)C.tab.p;
+  A.claim = (uint32_t*)C.claim.p;
+  A.sets = C.entries / SV_VC_WAYS;
+  A.counters = (uint64_t*)C.counters.p + 4;
+  A.keys = (const uint32_t*)w;
+  A.verdict = w + o_v;
+  A.slot = (uint32_t*)(w + o_slot);
+  A.n = n;
+  if ((rc = C.timer.begin(D.stream))) return rc;
+  SV_HIP(sv_launch_vc_feed(&A, D.stream));
+  return C.timer.end(D.stream, 0);
+}
+
 // launch_locked behind the slot's verdict cache (vcache.h): the same arguments, the same verdict bytes and
 // bitmap.  With the cache off -- the default -- or under SV_DBG_PREP_ONLY (no verdicts exist, so nothing may be
 // inserted) it IS launch_locked: no allocation, no kernel and no wait of its own.  With it on, all on D.stream:
@@ -274,19 +305,22 @@ inline VcBufs vc_layout(size_t n, bool own_keys, bool fixed32) {
 // there are none -> scatter and claim -> store -> bitmap.  Always the bulk route: the latency lane neither reads
 // nor writes the table.  Nothing before the claim kernel writes the table or its claim words, so an error return
 // up to there leaves the cache as it was.  hit (optional): n bytes, 1 where the verdict came from the table (all 0
-// with the cache off); keys (optional, 16-byte aligned): n x 32, the cache keys (written with the cache off too).
+// with the cache off); keys (optional, 16-byte aligned): n x 32, the cache keys (written with the cache off too;
+// keys_done: the caller's hash launch, queued on D.stream, has written them already).  With the cache on the
+// slot's journal is drained first (vc_drain_locked), so the probe sees what the latency lane verified.
 inline int launch_cached_locked(Device& D, int mode, int path, const void* pk, const void* sig, const void* msg,
                                 const uint64_t* off, const uint32_t* len, uint32_t fixed_len, uint64_t n,
                                 void* verdict, void* bitmap, bool tables = false, uint32_t kp = 0,
-                                void* hit = nullptr, void* keys = nullptr) {
+                                void* hit = nullptr, void* keys = nullptr, bool keys_done = false) {
   int rc;
   if (!vc_entries() || (g_dbg.load() & SV_DBG_PREP_ONLY) || n == 0 || n > SV_VC_MAX_ITEMS) {
     if (hit && n) SV_HIP(hipMemsetAsync(hit, 0, n, D.stream));
-    if (keys && n) SV_HIP(sv_launch_hash(0, D.grid * 2, pk, sig, msg, off, len, fixed_len, n, keys, D.stream));
+    if (keys && n && !keys_done) SV_HIP(sv_launch_hash(0, D.grid * 2, pk, sig, msg, off, len, fixed_len, n, keys, D.stream));
     return launch_locked(D, mode, path, pk, sig, msg, off, len, fixed_len, n, verdict, bitmap, tables, kp);
   }
   VerdictCache& C = D.vc;
   if ((rc = vc_prepare(D))) return rc;
+  if ((rc = vc_drain_locked(D))) return rc;
   const bool f32 = fixed_len == 32;
   const VcBufs L = vc_layout(n, !keys, f32);
   if (L.bytes > C.ws.cap) {
@@ -320,7 +354,8 @@ inline int launch_cached_locked(Device& D, int mode, int path, const void* pk, c
   A.clen = f32 ? nullptr : (uint32_t*)(w + L.o_len);
   A.cverdict = w + L.o_cv;
   if ((rc = C.timer.begin(D.stream))) return rc;
-  SV_HIP(sv_launch_hash(0, D.grid * 2, pk, sig, msg, off, len, fixed_len, n, (void*)A.keys, D.stream));
+  if (!(keys && keys_done))
+    SV_HIP(sv_launch_hash(0, D.grid * 2, pk, sig, msg, off, len, fixed_len, n, (void*)A.keys, D.stream));
   SV_HIP(sv_launch_vc_probe(&A, D.stream));
   if ((rc = C.timer.end(D.stream, n))) return rc;
   SV_HIP(hipMemcpyAsync(C.h_cnt.p, A.counters + 3, 8, hipMemcpyDeviceToHost, D.stream));
@@ -571,9 +606,15 @@ inline int host_slice_locked(Device& D, const HostIn& in, size_t n, uint8_t* ver
       if (tables < 0)
         tables = launch_geometry(resolve_path(path, chunk), chunk) == SV_PATH_THROUGHPUT &&
                  (ktm == 1 || (ktm == 2 && repeated_keys(in, n)));
-      if ((rc = launch_locked(D, mode, path, d, d + im.o_sig, d + im.o_msg, d_off, d_len, in.fixed, m,
-                              zc_out ? D.z_out.dp : s.d_verdict.p, nullptr, tables != 0,
-                              in_place && decode_first() ? SV_KP_IN_PLACE : 0u)))
+      // a keyed chunk with SV_VC_FEED_BULK set goes behind the slot's verdict cache, its keys being on the device
+      // already (launch_cached_locked's cache-off test makes the two calls the same launch where the cache is off)
+      const bool cached = keys && (vc_feed() & SV_VC_FEED_BULK) && vc_entries();
+      void* dv = zc_out ? D.z_out.dp : s.d_verdict.p;
+      const uint32_t kp = in_place && decode_first() ? SV_KP_IN_PLACE : 0u;
+      if ((rc = cached ? launch_cached_locked(D, mode, path, d, d + im.o_sig, d + im.o_msg, d_off, d_len, in.fixed, m,
+                                              dv, nullptr, tables != 0, kp, nullptr, s.d_keys.p, true)
+                       : launch_locked(D, mode, path, d, d + im.o_sig, d + im.o_msg, d_off, d_len, in.fixed, m, dv,
+                                       nullptr, tables != 0, kp)))
         return rc;
       trace_at("launched");
     }

@@ -21,6 +21,8 @@
 #include "keytab.h"
 #include "launch.h"
 #include "pool.h"
+#include "vcache.h"
+#include "vjournal.h"
 
 namespace sv {
 namespace {
@@ -274,9 +276,15 @@ struct KeyTabs {
 // the device counters (hits | inserted | dropped | the pass's miss count), the pinned word the miss count comes
 // back in and the compaction workspace of the largest cached launch so far.  Allocated on the first cached launch
 // after a non-zero capacity was set (sv_set_verdict_cache); touched only by kernels on D.stream, under D.mu.
+// The feed (sv_set_verdict_cache_feed): `counters` continues with present | inserted | dropped of the journal's
+// drains (words 4-6); a drain moves the taken rows through the pinned `h_feed` into `ws` (`fed_up`: the upload
+// has left h_feed, which the next drain rewrites).
 struct VerdictCache {
   DevBuf tab, claim, counters, ws;
   HostBuf h_cnt;
+  HostBuf h_feed;
+  hipEvent_t fed_up = nullptr;
+  JournalRows taken;  // the rows of the drain in progress (its buffers go back to the journal at the next take)
   size_t entries = 0;    // entries of `tab` (0: not allocated)
   uint64_t lookups = 0;  // items probed
   double wait_ms = 0;    // host time spent waiting for miss counts
@@ -285,6 +293,10 @@ struct VerdictCache {
   // (D.stream is drained)
   void release() {
     tab.release(); claim.release(); counters.release(); ws.release(); h_cnt.release();
+    h_feed.release();
+    if (fed_up) (void)hipEventDestroy(fed_up);
+    fed_up = nullptr;
+    taken = JournalRows();
     timer.release();
     timer.reset();
     entries = 0;
@@ -325,6 +337,7 @@ struct Device {
   LatLane lat;
   KeyTabs kt;  // (under mu)
   VerdictCache vc;  // (under mu)
+  Journal vj;       // keyed latency-lane batches on their way into vc (its own mutex: vjournal.h)
   std::atomic<int64_t> lat_last_ns{INT64_MIN / 2};  // steady clock of the last latency-lane batch
   std::atomic<uint64_t> shared_launches{0};          // bulk launches in shared mode
   // The slot's own staging workers for multi-slot calls (shard): its slice is
@@ -345,6 +358,41 @@ inline std::atomic<int> g_path{SV_PATH_AUTO};   // sv_set_kernel_path
 inline std::atomic<uint32_t> g_dbg{0};          // sv_set_debug_flags
 inline std::atomic<size_t> g_min_shard{0};      // sv_set_min_shard (0: default)
 inline std::atomic<uint64_t> g_rr{0};           // round-robin slot for single-slot calls
+
+// sv_set_verdict_cache: entries per slot, 0 (the default) off; ~0: SV_VERDICT_CACHE, read once.  Rounded up to
+// a power of two >= 4 (one set), at most SV_VC_MAX_ENTRIES.
+inline std::atomic<size_t> g_vc_entries{~(size_t)0};
+inline size_t vc_round(size_t v) {
+  if (!v) return 0;
+  size_t p = SV_VC_WAYS;
+  while (p < v && p < SV_VC_MAX_ENTRIES) p <<= 1;
+  return p;
+}
+inline size_t vc_entries() {
+  const size_t v = g_vc_entries.load();
+  if (v != ~(size_t)0) return v;
+  static const size_t e = vc_round(env_size("SV_VERDICT_CACHE", 0));
+  return e;
+}
+// sv_set_verdict_cache_feed: the SV_VC_FEED_* sources (~0: SV_VERDICT_CACHE_FEED, resolved at the first read) and
+// the rows of a slot's journal (0: SV_VERDICT_CACHE_JOURNAL or kJournalDefaultRows).
+inline std::atomic<uint32_t> g_vc_feed{~0u};
+inline std::atomic<size_t> g_vc_journal{0};
+inline uint32_t vc_feed() {
+  uint32_t v = g_vc_feed.load(std::memory_order_relaxed);
+  if (v != ~0u) return v;
+  const uint32_t e = (uint32_t)env_size("SV_VERDICT_CACHE_FEED", 0) & (SV_VC_FEED_LANE | SV_VC_FEED_BULK);
+  g_vc_feed.compare_exchange_strong(v, e);
+  return g_vc_feed.load(std::memory_order_relaxed);
+}
+inline size_t vc_journal_rows() {
+  const size_t v = g_vc_journal.load(std::memory_order_relaxed);
+  if (v) return std::min(v, kJournalMaxRows);
+  // (read once: this sits on the return path of every fed lane batch)
+  static const size_t e =
+      std::max<size_t>(1, std::min(env_size("SV_VERDICT_CACHE_JOURNAL", kJournalDefaultRows), kJournalMaxRows));
+  return e;
+}
 
 constexpr uint32_t kKernelDbgMask =
     SV_DBG_TRIVIAL_PAIR | SV_DBG_MAX_WINDOWS | SV_DBG_PREP_ONLY | SV_DBG_KEY_COLLIDE | SV_DBG_DROP_HANDOVER;

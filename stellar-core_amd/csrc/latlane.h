@@ -526,6 +526,14 @@ inline int lat_slice(Device& D, const HostIn& in, size_t n, uint8_t* verdict, ui
   lk.unlock();
   rc = lat_finish(*c, pd, verdict, keys, kcb, cb_done);
   release.completed = rc == SV_OK;
+  // A keyed batch's keys and verdicts into the slot's journal (sv_set_verdict_cache_feed; one relaxed load while
+  // the bit is clear): the next drain on the bulk stream inserts them.  The rows come from the context's own
+  // pinned copies, which the kernels wrote and only this batch holds -- not from the caller's arrays, which the
+  // keys-ready callback has already handed to the caller -- so the context stays busy for the copy.  The lane
+  // itself still never touches the table.  An error appended nothing.
+  if (rc == SV_OK && (vc_feed() & SV_VC_FEED_LANE) && keys && verdict && vc_entries() &&
+      !(g_dbg.load() & SV_DBG_PREP_ONLY))
+    D.vj.append(pd.kho, pd.vho, n, vc_journal_rows());
   return rc;
 }
 

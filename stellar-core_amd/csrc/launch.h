@@ -186,6 +186,11 @@ size_t sv_vc_psum_bytes(uint64_t n);
 hipError_t sv_launch_vc_probe(const struct sv_vc_args* A, hipStream_t s);
 hipError_t sv_launch_vc_insert(const struct sv_vc_args* A, uint64_t n_miss, hipStream_t s);
 hipError_t sv_launch_vc_bitmap(const void* verdict, uint64_t n, void* bitmap, hipStream_t s);
+// The drain of a slot's journal (vcache.h Feed): the claim and the store kernel over A->n rows with their
+// verdicts.  lookup: out[i] = the verdict the table holds for key i (keys n x 32, 16-byte aligned), or 0xFF.
+struct sv_vc_feed_args;
+hipError_t sv_launch_vc_feed(const struct sv_vc_feed_args* A, hipStream_t s);
+hipError_t sv_launch_vc_lookup(const void* tab, uint64_t sets, const void* keys, uint64_t n, void* out, hipStream_t s);
 // warm-key latency path (sv_comb.hip)
 size_t sv_comb_btab_bytes(void);
 size_t sv_key_slot_bytes(void);

@@ -1543,6 +1543,7 @@ int sv_set_verdict_cache(size_t entries) {
   g_vc_entries.store(vc_round(entries));
   for (Device* D : g_devs) {
     std::lock_guard<std::mutex> g(D->mu);
+    D->vj.reset();  // (journaled rows and the feed's counters go with the table)
     if (!D->ready) continue;
     (void)hipSetDevice(D->phys);
     (void)hipStreamSynchronize(D->stream);
@@ -1551,11 +1552,105 @@ int sv_set_verdict_cache(size_t entries) {
   return SV_OK;
 }
 
+int sv_set_verdict_cache_feed(uint32_t sources, size_t journal_rows) {
+  LifeGuard life_;
+  if (sources & ~(SV_VC_FEED_LANE | SV_VC_FEED_BULK))
+    return fail(SV_ERR_INVALID_ARG, "verdict cache feed: unknown source bits");
+  if (journal_rows > kJournalMaxRows) return fail(SV_ERR_INVALID_ARG, "verdict cache feed: journal above 2^24 rows");
+  std::lock_guard<std::mutex> g0(g_mu);
+  g_vc_feed.store(sources);
+  g_vc_journal.store(journal_rows);
+  // (a batch finishing on the lane right now may still append under the old setting: its rows are verdicts of
+  // this engine all the same)
+  for (Device* D : g_devs) D->vj.drop();
+  return SV_OK;
+}
+
+int sv_verdict_cache_sync(int device) {
+  LifeGuard life_;
+  Device* Dp;
+  int rc = slot_arg(device, Dp);
+  if (rc) return rc;
+  Device& D = *Dp;
+  std::lock_guard<std::mutex> g(D.mu);
+  if (!vc_entries()) return SV_OK;
+  SV_HIP(hipSetDevice(D.phys));
+  if ((rc = ready_locked(D))) return rc;
+  if ((rc = vc_drain_locked(D))) return rc;
+  // (also with nothing held: an earlier drain, queued by a device-form lookup, may still be running)
+  SV_HIP(hipStreamSynchronize(D.stream));
+  return SV_OK;
+}
+
+int sv_verdict_cache_lookup(int device, const uint8_t* keys, size_t n, uint8_t* out) {
+  LifeGuard life_;
+  if (n == 0) return SV_OK;
+  if (!keys || !out) return fail(SV_ERR_INVALID_ARG, "null buffer");
+  if (n > SV_VC_MAX_ITEMS) return fail(SV_ERR_INVALID_ARG, "verdict cache lookup: too many keys");
+  int rc;
+  if ((rc = debug_fail())) return rc;
+  Device* Dp;
+  if ((rc = slot_arg(device, Dp))) return rc;
+  Device& D = *Dp;
+  std::lock_guard<std::mutex> g(D.mu);
+  if (!vc_entries()) {
+    std::memset(out, (int)SV_VC_MISS, n);
+    return SV_OK;
+  }
+  SV_HIP(hipSetDevice(D.phys));
+  if ((rc = ready_locked(D)) || (rc = vc_prepare(D)) || (rc = vc_drain_locked(D))) return rc;
+  VerdictCache& C = D.vc;
+  // the keys and the answers behind the drain's rows in the workspace: everything here runs on D.stream in order
+  const size_t bytes = 32 * n + al16(n);
+  if (bytes > C.ws.cap) {
+    SV_HIP(hipStreamSynchronize(D.stream));
+    if ((rc = C.ws.ensure(bytes))) return rc;
+  }
+  uint8_t* w = (uint8_t*)C.ws.p;
+  SV_HIP(hipMemcpyAsync(w, keys, 32 * n, hipMemcpyHostToDevice, D.stream));
+  SV_HIP(sv_launch_vc_lookup(C.tab.p, C.entries / SV_VC_WAYS, w, n, w + 32 * n, D.stream));
+  SV_HIP(hipMemcpyAsync(out, w + 32 * n, n, hipMemcpyDeviceToHost, D.stream));
+  SV_HIP(hipStreamSynchronize(D.stream));
+  return SV_OK;
+}
+
+int sv_verdict_cache_lookup_device(int device, const void* d_keys, size_t n, void* d_out, void* stream) {
+  LifeGuard life_;
+  Device* Dp;
+  int rc = slot_arg(device, Dp);
+  if (rc) return rc;
+  if (n == 0) return SV_OK;
+  if (!d_keys || !d_out) return fail(SV_ERR_INVALID_ARG, "null device buffer");
+  if (n > SV_VC_MAX_ITEMS) return fail(SV_ERR_INVALID_ARG, "verdict cache lookup: too many keys");
+  if (!aligned16(d_keys)) return fail(SV_ERR_ALIGN, "keys must be 16-byte aligned");
+  if ((rc = debug_fail())) return rc;
+  Device& D = *Dp;
+  // The drain goes in prep(), ahead of the bracket's wait for the caller's stream: where it has to wait on the host
+  // (its workspace grows, or the previous drain's upload still holds the staging) it waits for the slot's own
+  // earlier work only, never for what the caller's stream holds.  The rows need nothing of the caller's.
+  return device_call(
+      D, stream,
+      [&]() -> int {
+        if (!vc_entries()) return SV_OK;
+        int rc2 = vc_prepare(D);
+        return rc2 ? rc2 : vc_drain_locked(D);
+      },
+      [&]() -> int {
+        if (!vc_entries()) {
+          SV_HIP(hipMemsetAsync(d_out, (int)SV_VC_MISS, n, D.stream));
+          return SV_OK;
+        }
+        SV_HIP(sv_launch_vc_lookup(D.vc.tab.p, D.vc.entries / SV_VC_WAYS, d_keys, n, d_out, D.stream));
+        return SV_OK;
+      });
+}
+
 int sv_verdict_cache_clear(void) {
   LifeGuard life_;
   std::lock_guard<std::mutex> g0(g_mu);
   for (Device* D : g_devs) {
     std::lock_guard<std::mutex> g(D->mu);
+    D->vj.drop();  // (rows journaled before the clear do not come back after it)
     if (!D->ready) continue;
     SV_HIP(hipSetDevice(D->phys));
     int rc;
@@ -1568,7 +1663,8 @@ int sv_verdict_cache_get_stats(int device, sv_verdict_cache_stats* out) {
   LifeGuard life_;
   if (!out || out->struct_size < offsetof(sv_verdict_cache_stats, kernel_ms))
     return fail(SV_ERR_INVALID_ARG, "verdict cache stats: null struct or struct_size too small");
-  const bool timed = out->struct_size >= sizeof(sv_verdict_cache_stats);
+  const bool timed = out->struct_size >= offsetof(sv_verdict_cache_stats, fed_rows);
+  const bool fed = out->struct_size >= sizeof(sv_verdict_cache_stats);
   Device* Dp;
   int rc = slot_arg(device, Dp);
   if (rc) return rc;
@@ -1578,10 +1674,14 @@ int sv_verdict_cache_get_stats(int device, sv_verdict_cache_stats* out) {
   out->entries = vc_entries();
   out->lookups = out->hits = out->inserted = out->dropped = out->bytes = 0;
   if (timed) out->kernel_ms = out->wait_ms = 0;
+  if (fed) {
+    out->fed_present = out->fed_inserted = out->fed_dropped = 0;
+    D.vj.counters(&out->fed_rows, &out->fed_overflow);
+  }
   if (!D.ready || !C.entries) return SV_OK;
   SV_HIP(hipSetDevice(D.phys));
   uint64_t* h = (uint64_t*)C.h_cnt.p + 1;  // (word 0: a pass's miss count)
-  SV_HIP(hipMemcpyAsync(h, C.counters.p, 24, hipMemcpyDeviceToHost, D.stream));
+  SV_HIP(hipMemcpyAsync(h, C.counters.p, 56, hipMemcpyDeviceToHost, D.stream));
   SV_HIP(hipStreamSynchronize(D.stream));
   if ((rc = C.timer.harvest())) return rc;
   out->lookups = C.lookups;
@@ -1592,6 +1692,11 @@ int sv_verdict_cache_get_stats(int device, sv_verdict_cache_stats* out) {
   if (timed) {
     out->kernel_ms = C.timer.total_ms;
     out->wait_ms = C.wait_ms;
+  }
+  if (fed) {  // (words 4-6 of the device counters; word 3 is a pass's miss count)
+    out->fed_present = h[4];
+    out->fed_inserted = h[5];
+    out->fed_dropped = h[6];
   }
   return SV_OK;
 }

@@ -28,6 +28,11 @@
 //   store    the row whose item stands in its claim word writes the whole entry
 //            and resets the claim word; every other row is dropped this pass
 //   bitmap   a ballot per wave over the final verdict bytes
+//   feed     the drain of the slot's journal (vjournal.h), one lane per row that
+//            arrives with its verdict: feed claim (present rows name no slot,
+//            the others atomicMin their row index) and feed store (the winner
+//            writes the entry); their counters are one atomic add per wave
+//   lookup   one lane per key: the held verdict or SV_VC_MISS; reads only
 #include <hip/hip_runtime.h>
 
 #include "launch.h"
@@ -177,6 +182,61 @@ __global__ __launch_bounds__(SV_VCBLOCK) void sv_vc_bitmap_kernel(const uint8_t*
   if ((threadIdx.x & 63) == 0 && base < n) bitmap[base >> 6] = m;
 }
 
+// one atomic add per wave of the wave's count of `flag` (every lane of the block calls)
+__device__ __forceinline__ void sv_vc_wave_add(uint64_t* counter, bool flag) {
+  const uint64_t m = __ballot(flag);
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd((unsigned long long*)counter, (unsigned long long)__popcll(m));
+}
+
+// The drain of the slot's journal (vcache.h Feed), one lane per row.  claim: a row the table holds is present; any
+// other names its candidate slot and claims it with its row index.
+__global__ __launch_bounds__(SV_VCBLOCK) void sv_vc_feed_claim_kernel(sv_vc_feed_args a) {
+  const uint64_t j = (uint64_t)blockIdx.x * SV_VCBLOCK + threadIdx.x;
+  bool present = false;
+  if (j < a.n) {
+    uint32_t k[8];
+    sv_vc_load_key(a.keys, j, k);
+    const uint32_t s = sv_vc_feed_slot(a.tab, a.sets, k, a.verdict[j], &present);
+    if (s != SV_VC_NO_SLOT) atomicMin(&a.claim[s], (uint32_t)j);
+    a.slot[j] = s;
+  }
+  sv_vc_wave_add(&a.counters[0], present);
+}
+
+// store: the row whose index stands in its claim word writes the entry and resets the word; a row that named a
+// slot and lost it is dropped
+__global__ __launch_bounds__(SV_VCBLOCK) void sv_vc_feed_store_kernel(sv_vc_feed_args a) {
+  const uint64_t j = (uint64_t)blockIdx.x * SV_VCBLOCK + threadIdx.x;
+  bool won = false, lost = false;
+  if (j < a.n) {
+    const uint32_t s = a.slot[j];
+    if (s != SV_VC_NO_SLOT) {
+      won = a.claim[s] == (uint32_t)j;
+      lost = !won;
+      if (won) {
+        uint32_t k[8];
+        sv_vc_load_key(a.keys, j, k);
+        sv_vc_store(a.tab, s, k, a.verdict[j]);
+        a.claim[s] = SV_VC_UNCLAIMED;
+      }
+    }
+  }
+  sv_vc_wave_add(&a.counters[1], won);
+  sv_vc_wave_add(&a.counters[2], lost);
+}
+
+// out[i]: the verdict the table holds for key i (0 or 1), or SV_VC_MISS_BYTE; the table is only read
+#define SV_VC_MISS_BYTE 0xFFu
+__global__ __launch_bounds__(SV_VCBLOCK) void sv_vc_lookup_kernel(const sv_vc_entry* tab, uint64_t sets,
+                                                                  const uint32_t* keys, uint64_t n, uint8_t* out) {
+  const uint64_t i = (uint64_t)blockIdx.x * SV_VCBLOCK + threadIdx.x;
+  if (i >= n) return;
+  uint32_t k[8];
+  sv_vc_load_key(keys, i, k);
+  const int v = sv_vc_lookup(tab, sets, k);
+  out[i] = v < 0 ? (uint8_t)SV_VC_MISS_BYTE : (uint8_t)v;
+}
+
 extern "C" {
 
 int sv_vc_block(void) { return SV_VCBLOCK; }
@@ -199,6 +259,24 @@ hipError_t sv_launch_vc_insert(const sv_vc_args* A, uint64_t n_miss, hipStream_t
   const unsigned blocks = (unsigned)sv_vc_blocks(n_miss);
   hipLaunchKernelGGL(sv_vc_claim_kernel, dim3(blocks), dim3(SV_VCBLOCK), 0, s, *A, n_miss);
   hipLaunchKernelGGL(sv_vc_store_kernel, dim3(blocks), dim3(SV_VCBLOCK), 0, s, *A, n_miss);
+  return hipGetLastError();
+}
+
+hipError_t sv_launch_vc_feed(const sv_vc_feed_args* A, hipStream_t s) {
+  if (!A->n) return hipSuccess;
+  if (A->n >= SV_VC_UNCLAIMED || !A->sets) return hipErrorInvalidValue;
+  const unsigned blocks = (unsigned)sv_vc_blocks(A->n);
+  hipLaunchKernelGGL(sv_vc_feed_claim_kernel, dim3(blocks), dim3(SV_VCBLOCK), 0, s, *A);
+  hipLaunchKernelGGL(sv_vc_feed_store_kernel, dim3(blocks), dim3(SV_VCBLOCK), 0, s, *A);
+  return hipGetLastError();
+}
+
+hipError_t sv_launch_vc_lookup(const void* tab, uint64_t sets, const void* keys, uint64_t n, void* out,
+                               hipStream_t s) {
+  if (!n) return hipSuccess;
+  if (n > SV_VC_MAX_ITEMS || !sets) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(sv_vc_lookup_kernel, dim3((unsigned)sv_vc_blocks(n)), dim3(SV_VCBLOCK), 0, s,
+                     (const sv_vc_entry*)tab, sets, (const uint32_t*)keys, n, (uint8_t*)out);
   return hipGetLastError();
 }
 

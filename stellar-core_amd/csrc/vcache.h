@@ -131,3 +131,35 @@ SV_HD void sv_vc_store(sv_vc_entry* tab, uint64_t s, const uint32_t* k, uint32_t
   tab[s].state = SV_VC_HOLDS0 + v;
   SV_UNROLL for (int w = 0; w < 3; ++w) tab[s].unused[w] = 0;
 }
+
+// Feed     Rows that arrive WITH their verdicts (vjournal.h: what the slot's
+//          latency lane verified) take the insert half of a pass alone, in
+//          journal order: a row whose key the table holds is `present` and
+//          changes nothing (it evicts nothing and names no slot); every other
+//          row names its candidate slot and claims it with its row index, and
+//          in a second kernel the winner stores the entry; a loser is dropped.
+//          The same one-writer rule, so the table after a drain is a function of
+//          the table before it and of the rows in journal order.
+//
+// What the two feed kernels work on (host memory; the arrays device memory, 16-byte aligned).
+struct sv_vc_feed_args {
+  sv_vc_entry* tab;
+  uint32_t* claim;
+  uint64_t sets;
+  uint64_t* counters;      // present | inserted | dropped of the drains
+  const uint32_t* keys;    // n x 8 words
+  const uint8_t* verdict;  // n
+  uint32_t* slot;          // n: row j's candidate slot (SV_VC_NO_SLOT: present, or no verdict byte)
+  uint64_t n;
+};
+
+// the slot a fed row with verdict byte v names: none if v is no verdict or the table holds the key
+SV_HD uint32_t sv_vc_feed_slot(const sv_vc_entry* tab, uint64_t sets, const uint32_t* k, uint8_t v, bool* present) {
+  *present = false;
+  if (v > 1) return SV_VC_NO_SLOT;
+  if (sv_vc_lookup(tab, sets, k) >= 0) {
+    *present = true;
+    return SV_VC_NO_SLOT;
+  }
+  return (uint32_t)sv_vc_candidate(tab, sets, k);
+}
