@@ -730,6 +730,171 @@ int sv_ed25519_decide_txbodies_accounts_cpu(const uint8_t* network_id, const uin
                                             size_t n_sigs, const sv_txaccounts* accts, const sv_txresults* res,
                                             uint8_t* digests /* optional */, int threads);
 
+/* ---- Accounts that stay on the device; checks that name them by ID ---------
+ * The by-account calls above take the account table per call, and the caller
+ * turns every account ID it reads out of a transaction into an index into the
+ * table it built for that call.  The reference never rebuilds account state per
+ * batch: its checks read ledger entries that live from one ledger to the next
+ * (TransactionFrame::loadSourceAccount, OperationFrame::loadSourceAccount,
+ * stellar::loadAccount) and change by deltas at ledger close.  The account
+ * store is that state for the engine: a host-authoritative table of accounts
+ * (csrc/acctstore.h) with one read-only replica per device slot
+ * (csrc/sv_txstore.hip), off by default -- nothing is allocated and no new code
+ * runs until sv_set_account_store turns it on.
+ *
+ * sv_set_account_store(accounts, payloads, local_accounts): capacity in
+ * accounts (0: off, everything freed), in 64-byte payload rows for type-3
+ * signers, and the rows past the capacity a ledger call may borrow for its own
+ * local accounts (below).  Process-wide; replaces (and empties) an existing
+ * store.  An account has at most 20 signers (MAX_SIGNERS).  Memory: 948 bytes
+ * per account, 65 per payload row and 4 per index slot (a power of two of slots
+ * >= 2 x accounts, at least 8), on the host and on every slot that has used the
+ * store -- there for accounts + local_accounts rows and payloads +
+ * 20 x local_accounts payload rows; sv_workspace_bytes and the stats count it.
+ * The index is seeded from std::random_device (SV_ACCT_STORE_SEED fixes the
+ * seed).
+ * sv_account_store_upsert: reads only acct_*, asigner_*, apayload*, n_accounts,
+ * n_asigners and n_apayloads of `table`.  An ID the store holds is replaced in
+ * place (no stale signer stays visible, its payload rows are freed); within one
+ * call the last row of a duplicate ID wins.  sv_account_store_erase: an absent
+ * ID is no error (it is counted).  Both are all-or-nothing: SV_ERR_INVALID_ARG
+ * for a batch that breaks a per-account rule of the by-account host forms (type
+ * > 3, payload index >= n_apayloads, apayload_len > 64, malformed
+ * asigner_begin) or has an account with more than 20 signers, or with the store
+ * off; SV_ERR_ALLOC when the new accounts or payload rows do not fit; in both
+ * cases nothing changes, on the host or on any replica, the counters included.
+ * A write returns when every replica holds it (each slot: staged rows up, one
+ * scatter kernel on the slot's stream under its lock, wait), so no check call
+ * sees half of it; a slot that first uses the store later starts from the host
+ * copy.  Writers are serialised.  sv_set_device_map and sv_shutdown drop the
+ * replicas AND the store.
+ * sv_account_store_read: n accounts by ID in a fixed layout (absent: found 0,
+ * zeros), from the host copy (device -1) or from slot `device`'s replica by its
+ * lookup kernel and a gather -- how a caller (and the tests) see what the device
+ * holds.  Any output may be NULL.  The host side (set, upsert, erase, clear,
+ * read with device -1, stats with device -1, the _cpu forms) needs no GPU. */
+int sv_set_account_store(size_t accounts, size_t payloads, size_t local_accounts);
+int sv_account_store_upsert(const sv_txaccounts* table);
+int sv_account_store_erase(const uint8_t* ids /* n x 32 */, size_t n);
+int sv_account_store_clear(void);
+typedef struct sv_account_store_stats {
+  uint64_t struct_size;      /* in: sizeof(sv_account_store_stats) of the caller */
+  uint64_t capacity;         /* accounts (0: off) */
+  uint64_t accounts;         /* held now */
+  uint64_t payload_capacity; /* payload rows */
+  uint64_t payloads;         /* in use now */
+  uint64_t local_accounts;
+  uint64_t index_slots;
+  uint64_t max_probe;        /* the bound every lookup's loop gets */
+  uint64_t upsert_calls, inserted, replaced; /* accepted upserts; accounts new / overwritten */
+  uint64_t erase_calls, erased, erase_absent;
+  uint64_t host_bytes;
+  /* of slot `device` (0 with device -1, or before the slot's first use of the store) */
+  uint64_t device_bytes;
+  uint64_t replica_current;  /* 1: the replica holds every write so far */
+  uint64_t lookups;          /* entries its lookup kernel resolved */
+  double lookup_ms;          /* ... and that kernel's device time (sv_timing_enable) */
+} sv_account_store_stats;
+int sv_account_store_get_stats(int device /* -1: the host side only */, sv_account_store_stats* out);
+int sv_account_store_read(int device /* -1: the host copy */, const uint8_t* ids /* n x 32 */, size_t n,
+                          uint8_t* found /* n */, uint8_t* thresholds /* n x 4 */, uint32_t* n_signers /* n */,
+                          uint8_t* signer_type /* n x 20 */, uint32_t* signer_weight /* n x 20 */,
+                          uint8_t* signer_key /* n x 20 x 32 */, uint8_t* signer_payload /* n x 20 x 64 */,
+                          uint8_t* signer_payload_len /* n x 20 */);
+
+/* Checks that name store accounts by ID.  Each entry point has the argument
+ * list of its _accounts twin with `const sv_txledger*` in place of
+ * `const sv_txaccounts*`.  accts is exactly the twin's struct; its account
+ * table is this call's LOCAL accounts (may be empty): the pseudo-accounts of
+ * checkSignatureNoAccount and checkExtraSigners, as today.  A bacct entry is
+ * a local account's index, or SV_BACCT_BY_ID: the store account whose ID is
+ * bacct_id[32 e .. 32 e + 31].
+ *
+ * The expansion stays the definition.  Let the twin's table be the local
+ * accounts followed by the store's accounts; replace every SV_BACCT_BY_ID entry
+ * by the index of the account with that ID, and an ID the store does not hold
+ * by an empty account (master weight 0, no signers, thresholds 0).  The results
+ * are byte for byte the twin's on that input.  An entry that is not found
+ * contributes no candidate row and a check that names it has no signer and is
+ * 0; bacct_found lets the caller turn that into txNO_ACCOUNT / opNO_ACCOUNT,
+ * which the reference decides before it looks at a signature.
+ *
+ * Host forms (host buffers): a third source of the chunk pipeline beside the
+ * explicit and the by-account one.  Before any device work the call's entries
+ * are resolved on the HOST index into replica rows, with the per-account row
+ * counts read from the host copy, so the planner knows the expanded counts
+ * exactly and the form waits no more often than its twin does.  Each slot
+ * uploads only the local accounts, once per call, into the borrowed rows; a
+ * chunk carries 4 bytes per entry as in the by-account form; the IDs never
+ * cross PCIe.  The store cannot be written while such a call runs (a writer
+ * waits for it).  opts->device == -1 slices the bodies as in the twin.
+ * CPU forms: the expansion on the host over the host copy, then the twin's CPU
+ * path; no device is touched.
+ * The host and CPU forms refuse (SV_ERR_INVALID_ARG) a call with the store off,
+ * more than local_accounts local accounts, a local account with more than 20
+ * signers, a bacct entry that is neither SV_BACCT_BY_ID nor a local index, an
+ * entry by ID with bacct_id NULL, and everything the twin refuses.  bacct_found
+ * is written only by a call that is accepted.
+ * Device forms: every array, bacct_id and bacct_found included, is device
+ * memory (bacct_id 16-byte aligned); the structs are host memory.  The slot's
+ * replica is the account table: the local accounts are written into the
+ * borrowed rows by a small kernel, a lookup kernel (one lane per entry, at most
+ * max_probe slots probed, all 32 bytes compared) resolves every entry to a row,
+ * and the twin's sequence runs unchanged on that table -- no store row is
+ * copied per call, and the call waits exactly as often as its twin.  Nothing is
+ * validated beyond the store being on (off: SV_ERR_INVALID_ARG): local
+ * accounts past local_accounts and signers past an account's first 20 are not
+ * read, a bacct entry that is neither by ID nor a local index names no account
+ * (found 0), with bacct_id NULL no ID is found, and every other clamp is the
+ * twin's.  A write to the store and a
+ * device-form call exclude each other by the slot's lock: a call queued after
+ * sv_account_store_upsert returned sees the new rows. */
+#define SV_BACCT_BY_ID 0xFFFFFFFFu
+typedef struct sv_txledger {
+  uint32_t struct_size;        /* sizeof(sv_txledger) */
+  uint32_t reserved;           /* 0 */
+  const sv_txaccounts* accts;
+  const uint8_t* bacct_id;     /* n_bacct x 32; read for the entries whose bacct[e] == SV_BACCT_BY_ID */
+  uint8_t* bacct_found;        /* out, optional, n_bacct: 1 = local entry or ID held by the store, 0 = not held */
+} sv_txledger;
+int sv_ed25519_check_txbodies_ledger(const uint8_t* network_id /* 32 B */, const uint8_t* bodies,
+                                     const uint64_t* body_off, const uint32_t* body_len, const uint8_t* body_kind,
+                                     size_t n_bodies, const uint64_t* sig_begin, const uint8_t* hint,
+                                     const uint8_t* sig, size_t n_sigs, const sv_txledger* ledger, uint8_t* check_ok,
+                                     uint32_t* check_weight, uint64_t* check_used,
+                                     uint8_t* digests /* optional, n_bodies x 32 */, const sv_opts* opts);
+int sv_ed25519_decide_txbodies_ledger(const uint8_t* network_id /* 32 B */, const uint8_t* bodies,
+                                      const uint64_t* body_off, const uint32_t* body_len, const uint8_t* body_kind,
+                                      size_t n_bodies, const uint64_t* sig_begin, const uint8_t* hint,
+                                      const uint8_t* sig, size_t n_sigs, const sv_txledger* ledger,
+                                      const sv_txresults* res, uint8_t* digests /* optional, n_bodies x 32 */,
+                                      const sv_opts* opts);
+int sv_ed25519_check_txbodies_ledger_device(int device, const uint8_t* network_id /* host, 32 B */,
+                                            const void* d_bodies, const uint64_t* d_body_off,
+                                            const uint32_t* d_body_len, const uint8_t* d_body_kind, size_t n_bodies,
+                                            const uint64_t* d_sig_begin, const void* d_hint, const void* d_sig,
+                                            size_t n_sigs, const sv_txledger* ledger /* host structs, device arrays */,
+                                            void* d_check_ok, uint32_t* d_check_weight, uint64_t* d_check_used,
+                                            void* d_digests, void* stream);
+int sv_ed25519_check_txbodies_ledger_cpu(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                         const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                         const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig,
+                                         size_t n_sigs, const sv_txledger* ledger, uint8_t* check_ok,
+                                         uint32_t* check_weight, uint64_t* check_used,
+                                         uint8_t* digests /* optional */, int threads);
+int sv_ed25519_decide_txbodies_ledger_device(int device, const uint8_t* network_id /* host, 32 B */,
+                                             const void* d_bodies, const uint64_t* d_body_off,
+                                             const uint32_t* d_body_len, const uint8_t* d_body_kind, size_t n_bodies,
+                                             const uint64_t* d_sig_begin, const void* d_hint, const void* d_sig,
+                                             size_t n_sigs, const sv_txledger* ledger /* host structs, device arrays */,
+                                             const sv_txresults* res /* host struct, device arrays */,
+                                             void* d_digests, void* stream);
+int sv_ed25519_decide_txbodies_ledger_cpu(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                          const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                          const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig,
+                                          size_t n_sigs, const sv_txledger* ledger, const sv_txresults* res,
+                                          uint8_t* digests /* optional */, int threads);
+
 /* ---- Warm-key latency path (csrc/comb.h, csrc/sv_comb.hip) ---------------
  * Each device slot keeps a bounded cache of per-public-key tables
  * ({0..8} * 16^j * (-A), 108 KiB per key) in HBM.  A latency-path host batch

@@ -82,7 +82,16 @@ EXPORTED_SYMBOLS = (
     "sv_set_verdict_cache", "sv_verdict_cache_clear", "sv_verdict_cache_get_stats",
     "sv_ed25519_verify_device_cached",
     "sv_set_verdict_cache_feed", "sv_verdict_cache_sync", "sv_verdict_cache_lookup", "sv_verdict_cache_lookup_device",
+    "sv_set_account_store", "sv_account_store_upsert", "sv_account_store_erase", "sv_account_store_clear",
+    "sv_account_store_get_stats", "sv_account_store_read",
+    "sv_ed25519_check_txbodies_ledger", "sv_ed25519_decide_txbodies_ledger",
+    "sv_ed25519_check_txbodies_ledger_device", "sv_ed25519_check_txbodies_ledger_cpu",
+    "sv_ed25519_decide_txbodies_ledger_device", "sv_ed25519_decide_txbodies_ledger_cpu",
 )
+
+# a bacct entry of the ledger forms that names a store account by its ID (include/stellar_sigverify.h)
+BACCT_BY_ID = 0xFFFFFFFF
+ACCT_MAX_SIGNERS = 20
 
 # per-body result codes, check roles and body flags of the decide entry points (include/stellar_sigverify.h)
 TXRESULT_OK, TXRESULT_BAD_AUTH, TXRESULT_OP_BAD_AUTH, TXRESULT_BAD_AUTH_EXTRA = 0, 1, 2, 3
@@ -139,6 +148,19 @@ class sv_txaccounts(ctypes.Structure):
                     "asigner_key", "asigner_payload", "apayload", "apayload_len", "bacct_begin", "bacct",
                     "check_begin", "check_acct", "check_level", "check_needed")]
                 + [(f, ctypes.c_size_t) for f in ("n_accounts", "n_asigners", "n_apayloads", "n_bacct", "n_checks")])
+
+
+class sv_txledger(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("accts", ctypes.POINTER(sv_txaccounts)), ("bacct_id", ctypes.c_void_p),
+                ("bacct_found", ctypes.c_void_p)]
+
+
+class AccountStoreStats(ctypes.Structure):
+    _fields_ = ([(f, ctypes.c_uint64) for f in (
+        "struct_size", "capacity", "accounts", "payload_capacity", "payloads", "local_accounts", "index_slots",
+        "max_probe", "upsert_calls", "inserted", "replaced", "erase_calls", "erased", "erase_absent", "host_bytes",
+        "device_bytes", "replica_current", "lookups")] + [("lookup_ms", ctypes.c_double)])
 
 
 class sv_txresults(ctypes.Structure):
@@ -263,6 +285,19 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.sv_ed25519_decide_txbodies_accounts.argtypes = decided_acct + [vp]
     lib.sv_ed25519_decide_txbodies_accounts_cpu.argtypes = decided_acct + [ctypes.c_int]
     lib.sv_ed25519_decide_txbodies_accounts_device.argtypes = [ctypes.c_int] + decided_acct + [vp]
+    by_ledger = by_acct[:10] + [ctypes.POINTER(sv_txledger)] + by_acct[11:]
+    lib.sv_ed25519_check_txbodies_ledger.argtypes = by_ledger + [vp]
+    lib.sv_ed25519_check_txbodies_ledger_cpu.argtypes = by_ledger + [ctypes.c_int]
+    lib.sv_ed25519_check_txbodies_ledger_device.argtypes = [ctypes.c_int] + by_ledger + [vp]
+    decided_ledger = by_ledger[:-4] + [resp, vp]
+    lib.sv_ed25519_decide_txbodies_ledger.argtypes = decided_ledger + [vp]
+    lib.sv_ed25519_decide_txbodies_ledger_cpu.argtypes = decided_ledger + [ctypes.c_int]
+    lib.sv_ed25519_decide_txbodies_ledger_device.argtypes = [ctypes.c_int] + decided_ledger + [vp]
+    lib.sv_set_account_store.argtypes = [sz, sz, sz]
+    lib.sv_account_store_upsert.argtypes = [ctypes.POINTER(sv_txaccounts)]
+    lib.sv_account_store_erase.argtypes = [vp, sz]
+    lib.sv_account_store_get_stats.argtypes = [ctypes.c_int, ctypes.POINTER(AccountStoreStats)]
+    lib.sv_account_store_read.argtypes = [ctypes.c_int, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.sv_txresult_block.restype = ctypes.c_int
     lib.sv_txresult_ws_bytes.argtypes = [ctypes.c_uint64]
     lib.sv_txresult_ws_bytes.restype = sz
@@ -273,7 +308,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
 def _check(rc: int) -> None:
     if rc != SV_OK:
         msg = _lib.sv_last_error_string().decode(errors="replace") if _lib else ""
-        raise SigVerifyError("%s: %s" % (SV_ERRORS.get(rc, rc), msg))
+        raise SigVerifyError("%s: %s" % (SV_ERRORS.get(rc, rc), msg), code=rc)
 
 
 def _ptr(a: np.ndarray) -> ctypes.c_void_p:
@@ -803,7 +838,9 @@ def _accounts_desc(protocol_version, sig_len, acct_key, acct_thresholds, asigner
 def _accounts_host(fn, last, network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, acct_key,
                    acct_thresholds, asigner_begin, asigner_type, asigner_weight, asigner_key, asigner_payload,
                    apayload, apayload_len, bacct_begin, bacct, check_begin, check_acct, check_level, check_needed,
-                   sig_len, protocol_version, results=None):
+                   sig_len, protocol_version, results=None, ledger=None):
+    """ledger: None, or a dict for the ledger forms -- in: bacct_id (n_bacct x 32, or None); out: "found", the
+    call's bacct_found; the struct passed is then an sv_txledger over the sv_txaccounts."""
     nid = np.ascontiguousarray(np.frombuffer(bytes(network_id), np.uint8))
     if nid.size != 32:
         raise ValueError("network_id must be 32 bytes")
@@ -849,9 +886,29 @@ def _accounts_host(fn, last, network_id, bodies, body_off, body_len, body_kind, 
     ac = _accounts_desc(protocol_version, a(sl), a(ak), a(th), gb.__array_interface__["data"][0], a(gt), a(gw), a(gk),
                         a(gp), a(pay), a(pl), a(eb), a(ea), a(cb), a(ca), a(lv), a(need), na, ng, npay, ea.shape[0],
                         nc)
+    table = ac
+    if ledger is not None:
+        ids = ledger.get("bacct_id")
+        if ids is not None:
+            ids = _u8(ids, 32)
+            if ids.shape[0] != ea.shape[0]:
+                raise ValueError("bacct_id must hold one 32-byte row per bacct entry")
+        ledger["found"] = np.zeros(ea.shape[0], np.uint8)
+        table = ledger_desc(ac, a(ids), a(ledger["found"]))
     head = (_ptr(nid), _ptr(bodies), _ptr(off), _ptr(ln), _ptr(kind), nb, _ptr(sb), _ptr(hint), _ptr(sig), ns,
-            ctypes.byref(ac))
+            ctypes.byref(table))
     return _checked_call(fn, head, nb, nc, last, results)
+
+
+def ledger_desc(accts, bacct_id=0, bacct_found=0, struct_size=None):
+    """sv_txledger over an sv_txaccounts and raw addresses (host arrays' or device pointers; 0: NULL).  The
+    returned struct keeps `accts` alive."""
+    lg = sv_txledger()
+    lg.struct_size = ctypes.sizeof(sv_txledger) if struct_size is None else int(struct_size)
+    lg.accts = ctypes.pointer(accts)
+    lg.bacct_id = bacct_id or None
+    lg.bacct_found = bacct_found or None
+    return lg
 
 
 def check_txbodies_accounts(network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, acct_key,
@@ -1040,6 +1097,199 @@ def decide_txbodies_accounts_device(device: int, network_id, d_bodies: int, d_bo
         device, _ptr(nid), d_bodies or None, d_body_off or None, d_body_len or None, d_body_kind or None, n_bodies,
         d_sig_begin or None, d_hint or None, d_sig or None, n_sigs, ctypes.byref(ac), ctypes.byref(res),
         d_digests or None, stream or None))
+
+
+def check_txbodies_ledger_cpu(network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, acct_key,
+                              acct_thresholds, asigner_begin, asigner_type, asigner_weight, asigner_key,
+                              asigner_payload, apayload, apayload_len, bacct_begin, bacct, bacct_id, check_begin,
+                              check_acct, check_level, check_needed=None, sig_len=None, protocol_version: int = 21,
+                              threads: int = 0):
+    """Signature checks that name the account store's accounts by ID
+    (sv_ed25519_check_txbodies_ledger_cpu): the arguments of
+    check_txbodies_accounts_cpu, whose account table is this call's LOCAL
+    accounts, plus bacct_id (n_bacct x 32), read where bacct[e] == BACCT_BY_ID.
+    Returns ((check_ok, check_weight, check_used, digests), bacct_found)."""
+    lib = load_library()
+    lg = {"bacct_id": bacct_id}
+    r = _accounts_host(lib.sv_ed25519_check_txbodies_ledger_cpu, int(threads), network_id, bodies, body_off, body_len,
+                       body_kind, sig_begin, hint, sig, acct_key, acct_thresholds, asigner_begin, asigner_type,
+                       asigner_weight, asigner_key, asigner_payload, apayload, apayload_len, bacct_begin, bacct,
+                       check_begin, check_acct, check_level, check_needed, sig_len, protocol_version, ledger=lg)
+    return r, lg["found"]
+
+
+def decide_txbodies_ledger_cpu(network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, acct_key,
+                               acct_thresholds, asigner_begin, asigner_type, asigner_weight, asigner_key,
+                               asigner_payload, apayload, apayload_len, bacct_begin, bacct, bacct_id, check_begin,
+                               check_acct, check_level, check_needed=None, check_role=None, body_flags=None,
+                               sig_len=None, protocol_version: int = 21, threads: int = 0, want_checks=False,
+                               want_fail=True, bad_cap=None, res=None):
+    """One result per body over the same input (sv_ed25519_decide_txbodies_ledger_cpu).
+    Returns (TxResults as decide_txbodies_accounts_cpu, bacct_found)."""
+    lib = load_library()
+    lg = {"bacct_id": bacct_id}
+    r = _accounts_host(lib.sv_ed25519_decide_txbodies_ledger_cpu, int(threads), network_id, bodies, body_off, body_len,
+                       body_kind, sig_begin, hint, sig, acct_key, acct_thresholds, asigner_begin, asigner_type,
+                       asigner_weight, asigner_key, asigner_payload, apayload, apayload_len, bacct_begin, bacct,
+                       check_begin, check_acct, check_level, check_needed, sig_len, protocol_version,
+                       results=_results_spec(res, check_role, body_flags, want_checks, want_fail, bad_cap), ledger=lg)
+    return r, lg["found"]
+
+
+def check_txbodies_ledger(network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, acct_key,
+                          acct_thresholds, asigner_begin, asigner_type, asigner_weight, asigner_key, asigner_payload,
+                          apayload, apayload_len, bacct_begin, bacct, bacct_id, check_begin, check_acct, check_level,
+                          check_needed=None, sig_len=None, protocol_version: int = 21, device: int = -1,
+                          max_devices: int = 0, path=None):
+    """The same from host buffers on the GPU (sv_ed25519_check_txbodies_ledger): the
+    IDs are resolved on the host index, only the local accounts go up.  Returns
+    ((check_ok, check_weight, check_used, digests), bacct_found)."""
+    lib = load_library()
+    lg = {"bacct_id": bacct_id}
+    r = _accounts_host(lib.sv_ed25519_check_txbodies_ledger, _opts(device, max_devices, path), network_id, bodies,
+                       body_off, body_len, body_kind, sig_begin, hint, sig, acct_key, acct_thresholds, asigner_begin,
+                       asigner_type, asigner_weight, asigner_key, asigner_payload, apayload, apayload_len, bacct_begin,
+                       bacct, check_begin, check_acct, check_level, check_needed, sig_len, protocol_version, ledger=lg)
+    return r, lg["found"]
+
+
+def decide_txbodies_ledger(network_id, bodies, body_off, body_len, body_kind, sig_begin, hint, sig, acct_key,
+                           acct_thresholds, asigner_begin, asigner_type, asigner_weight, asigner_key, asigner_payload,
+                           apayload, apayload_len, bacct_begin, bacct, bacct_id, check_begin, check_acct, check_level,
+                           check_needed=None, check_role=None, body_flags=None, sig_len=None,
+                           protocol_version: int = 21, device: int = -1, max_devices: int = 0, path=None,
+                           want_checks=False, want_fail=True, bad_cap=None, res=None):
+    """One result per body from host buffers (sv_ed25519_decide_txbodies_ledger).
+    Returns (TxResults as decide_txbodies_accounts, bacct_found)."""
+    lib = load_library()
+    lg = {"bacct_id": bacct_id}
+    r = _accounts_host(lib.sv_ed25519_decide_txbodies_ledger, _opts(device, max_devices, path), network_id, bodies,
+                       body_off, body_len, body_kind, sig_begin, hint, sig, acct_key, acct_thresholds, asigner_begin,
+                       asigner_type, asigner_weight, asigner_key, asigner_payload, apayload, apayload_len, bacct_begin,
+                       bacct, check_begin, check_acct, check_level, check_needed, sig_len, protocol_version,
+                       results=_results_spec(res, check_role, body_flags, want_checks, want_fail, bad_cap), ledger=lg)
+    return r, lg["found"]
+
+
+def check_txbodies_ledger_device(device: int, network_id, d_bodies: int, d_body_off: int, d_body_len: int,
+                                 d_body_kind: int, n_bodies: int, d_sig_begin: int, d_hint: int, d_sig: int,
+                                 n_sigs: int, d_acct_key: int, d_acct_thresholds: int, d_asigner_begin: int,
+                                 d_asigner_type: int, d_asigner_weight: int, d_asigner_key: int,
+                                 d_asigner_payload: int, d_apayload: int, d_apayload_len: int, n_accounts: int,
+                                 n_asigners: int, n_apayloads: int, d_bacct_begin: int, d_bacct: int, n_bacct: int,
+                                 d_bacct_id: int, d_bacct_found: int, d_check_begin: int, d_check_acct: int,
+                                 d_check_level: int, d_check_needed: int, n_checks: int, d_check_ok: int,
+                                 d_check_weight: int, d_check_used: int, d_sig_len: int = 0,
+                                 protocol_version: int = 21, d_digests: int = 0, stream: int = 0) -> None:
+    """Device-resident form (raw device pointers; network_id is 32 host bytes):
+    check_txbodies_accounts_device's arguments, the account table being the
+    call's local accounts, plus d_bacct_id (n_bacct x 32, 16-byte aligned) and
+    the optional d_bacct_found (n_bacct bytes).  Waits as its twin does."""
+    lib = load_library()
+    nid = np.ascontiguousarray(np.frombuffer(bytes(network_id), np.uint8))
+    if nid.size != 32:
+        raise ValueError("network_id must be 32 bytes")
+    ac = _accounts_desc(protocol_version, d_sig_len, d_acct_key, d_acct_thresholds, d_asigner_begin, d_asigner_type,
+                        d_asigner_weight, d_asigner_key, d_asigner_payload, d_apayload, d_apayload_len, d_bacct_begin,
+                        d_bacct, d_check_begin, d_check_acct, d_check_level, d_check_needed, n_accounts, n_asigners,
+                        n_apayloads, n_bacct, n_checks)
+    lg = ledger_desc(ac, d_bacct_id, d_bacct_found)
+    _check(lib.sv_ed25519_check_txbodies_ledger_device(
+        device, _ptr(nid), d_bodies or None, d_body_off or None, d_body_len or None, d_body_kind or None, n_bodies,
+        d_sig_begin or None, d_hint or None, d_sig or None, n_sigs, ctypes.byref(lg), d_check_ok or None,
+        d_check_weight or None, d_check_used or None, d_digests or None, stream or None))
+
+
+def decide_txbodies_ledger_device(device: int, network_id, d_bodies: int, d_body_off: int, d_body_len: int,
+                                  d_body_kind: int, n_bodies: int, d_sig_begin: int, d_hint: int, d_sig: int,
+                                  n_sigs: int, d_acct_key: int, d_acct_thresholds: int, d_asigner_begin: int,
+                                  d_asigner_type: int, d_asigner_weight: int, d_asigner_key: int,
+                                  d_asigner_payload: int, d_apayload: int, d_apayload_len: int, n_accounts: int,
+                                  n_asigners: int, n_apayloads: int, d_bacct_begin: int, d_bacct: int, n_bacct: int,
+                                  d_bacct_id: int, d_bacct_found: int, d_check_begin: int, d_check_acct: int,
+                                  d_check_level: int, d_check_needed: int, n_checks: int, res, d_sig_len: int = 0,
+                                  protocol_version: int = 21, d_digests: int = 0, stream: int = 0) -> None:
+    """Device-resident decide form (res: results_desc over device pointers)."""
+    lib = load_library()
+    nid = np.ascontiguousarray(np.frombuffer(bytes(network_id), np.uint8))
+    if nid.size != 32:
+        raise ValueError("network_id must be 32 bytes")
+    ac = _accounts_desc(protocol_version, d_sig_len, d_acct_key, d_acct_thresholds, d_asigner_begin, d_asigner_type,
+                        d_asigner_weight, d_asigner_key, d_asigner_payload, d_apayload, d_apayload_len, d_bacct_begin,
+                        d_bacct, d_check_begin, d_check_acct, d_check_level, d_check_needed, n_accounts, n_asigners,
+                        n_apayloads, n_bacct, n_checks)
+    lg = ledger_desc(ac, d_bacct_id, d_bacct_found)
+    _check(lib.sv_ed25519_decide_txbodies_ledger_device(
+        device, _ptr(nid), d_bodies or None, d_body_off or None, d_body_len or None, d_body_kind or None, n_bodies,
+        d_sig_begin or None, d_hint or None, d_sig or None, n_sigs, ctypes.byref(lg), ctypes.byref(res),
+        d_digests or None, stream or None))
+
+
+def set_account_store(accounts: int, payloads: int = 0, local_accounts: int = 0) -> None:
+    """The account store (sv_set_account_store): capacity in accounts (0: off),
+    in 64-byte payload rows for type-3 signers, and the rows a ledger call may
+    borrow for its local accounts.  Replaces (and empties) an existing store."""
+    _check(load_library().sv_set_account_store(int(accounts), int(payloads), int(local_accounts)))
+
+
+def account_store_upsert(acct_key, acct_thresholds, asigner_begin, asigner_type, asigner_weight, asigner_key,
+                         asigner_payload=None, apayload=None, apayload_len=None) -> None:
+    """Inserts or replaces accounts (sv_account_store_upsert): the account-table
+    arrays of check_txbodies_accounts.  All of the batch or none of it."""
+    def arr(x, dt):
+        return np.ascontiguousarray(np.asarray(x if x is not None else [], dtype=dt).reshape(-1))
+    ak, th = _u8(acct_key, 32), _u8(acct_thresholds, 4)
+    na = ak.shape[0]
+    gb = np.ascontiguousarray(np.asarray(asigner_begin, dtype=np.uint64).reshape(-1))
+    if th.shape[0] != na or gb.shape[0] != na + 1:
+        raise ValueError("acct_key / acct_thresholds / asigner_begin row mismatch")
+    gt, gw, gk = arr(asigner_type, np.uint8), arr(asigner_weight, np.uint32), _u8(asigner_key, 32)
+    ng = gt.shape[0]
+    gp = arr(asigner_payload, np.uint32) if asigner_payload is not None else None
+    if gw.shape[0] != ng or gk.shape[0] != ng or (gp is not None and gp.shape[0] != ng):
+        raise ValueError("asigner_type / asigner_weight / asigner_key / asigner_payload row mismatch")
+    pay, pl = _u8(apayload if apayload is not None else [], 64), arr(apayload_len, np.uint8)
+    if pl.shape[0] != pay.shape[0]:
+        raise ValueError("apayload / apayload_len row mismatch")
+    a = lambda x: x.__array_interface__["data"][0] if x is not None and x.size else 0  # noqa: E731
+    ac = _accounts_desc(0, 0, a(ak), a(th), gb.__array_interface__["data"][0], a(gt), a(gw), a(gk), a(gp), a(pay),
+                        a(pl), 0, 0, 0, 0, 0, 0, na, ng, pay.shape[0], 0, 0)
+    _check(load_library().sv_account_store_upsert(ctypes.byref(ac)))
+
+
+def account_store_erase(ids) -> None:
+    """Erases accounts by ID (n x 32); an ID the store does not hold is counted, not refused."""
+    ids = _u8(ids, 32)
+    _check(load_library().sv_account_store_erase(_ptr(ids), ids.shape[0]))
+
+
+def account_store_clear() -> None:
+    _check(load_library().sv_account_store_clear())
+
+
+def account_store_stats(device: int = -1) -> dict:
+    """sv_account_store_get_stats; device -1: the host side only."""
+    st = AccountStoreStats()
+    st.struct_size = ctypes.sizeof(AccountStoreStats)
+    _check(load_library().sv_account_store_get_stats(int(device), ctypes.byref(st)))
+    return {f: getattr(st, f) for f, _ in AccountStoreStats._fields_ if f != "struct_size"}
+
+
+AccountRows = collections.namedtuple(
+    "AccountRows", "found thresholds n_signers signer_type signer_weight signer_key signer_payload signer_payload_len")
+
+
+def account_store_read(ids, device: int = -1) -> AccountRows:
+    """n accounts by ID as the store holds them (sv_account_store_read): from the
+    host copy (device -1) or from a slot's replica, by its lookup kernel.  Rows
+    of 20 signers; an ID that is not held reads as found 0 and zeros."""
+    ids = _u8(ids, 32)
+    n = ids.shape[0]
+    r = AccountRows(np.zeros(n, np.uint8), np.zeros((n, 4), np.uint8), np.zeros(n, np.uint32),
+                    np.zeros((n, 20), np.uint8), np.zeros((n, 20), np.uint32), np.zeros((n, 20, 32), np.uint8),
+                    np.zeros((n, 20, 64), np.uint8), np.zeros((n, 20), np.uint8))
+    _check(load_library().sv_account_store_read(int(device), _ptr(ids), n, *[_ptr(x) for x in r]))
+    return r
 
 
 def verify_gather(items, keys: bool = False, device: int = -1, max_devices: int = 0):

@@ -21,6 +21,7 @@
 #include "keytab.h"
 #include "launch.h"
 #include "pool.h"
+#include "txstore.h"
 #include "vcache.h"
 #include "vjournal.h"
 
@@ -305,6 +306,34 @@ struct VerdictCache {
   }
 };
 
+// A slot's replica of the account store (acctstore.h, txstore.h, sv_txstore.hip): one allocation for the arrays,
+// allocated at the slot's first use of the store; `version` is the host store's version the replica holds (0: none,
+// or stale after a failed write -- the next use copies the host's arrays up again).  At `version` the replica's
+// first `accounts` rows, payload rows and index words are the host copy's, byte for byte (an erased row's zeroed
+// counts are scattered too, and a clear zeroes every row's counts on both sides).  Written only by the scatter
+// and local kernels on D.stream, under D.mu.  `ws`: a lookup's IDs, rows and gathered accounts (sv_account_store_
+// read); `d_stage` / `h_stage`: a write's records on their way up.
+struct AcctReplica {
+  DevBuf buf, ws, d_stage;
+  HostBuf h_stage;
+  sv_store_tab tab{};
+  uint64_t version = 0;
+  uint32_t max_probe = 1;  // the host's bound as of `version`
+  uint64_t lookups = 0;
+  KernelTimer timer;  // the lookup kernel
+  size_t bytes() const { return buf.cap + ws.cap + d_stage.cap; }
+  // (D.stream is drained)
+  void release() {
+    buf.release(); ws.release(); d_stage.release(); h_stage.release();
+    tab = sv_store_tab{};
+    version = 0;
+    max_probe = 1;
+    lookups = 0;
+    timer.release();
+    timer.reset();
+  }
+};
+
 struct Device {
   int slot = -1;
   int phys = -1;
@@ -337,6 +366,7 @@ struct Device {
   LatLane lat;
   KeyTabs kt;  // (under mu)
   VerdictCache vc;  // (under mu)
+  AcctReplica as;   // (under mu)
   Journal vj;       // keyed latency-lane batches on their way into vc (its own mutex: vjournal.h)
   std::atomic<int64_t> lat_last_ns{INT64_MIN / 2};  // steady clock of the last latency-lane batch
   std::atomic<uint64_t> shared_launches{0};          // bulk launches in shared mode
@@ -495,6 +525,7 @@ inline void release_device(Device& D) {
   D.kt.copied = nullptr;
   D.kt.slots = 0;
   D.vc.release();
+  D.as.release();
   if (D.btab) (void)hipFree(D.btab);
   if (D.dep_in) (void)hipEventDestroy(D.dep_in);
   if (D.dep_out) (void)hipEventDestroy(D.dep_out);

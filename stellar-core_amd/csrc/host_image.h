@@ -636,6 +636,9 @@ struct AcctIn {
   const uint8_t* clevel;
   const int32_t* cneed;    // may be null (no level-0 check)
   const uint32_t* acnt;    // per account, made once: rows it adds to a key list [2a], payload candidates [2a + 1]
+  // The ledger forms (accounts named by ID, resolved on the host index): the same two counts per ENTRY, made by
+  // the resolve; eacct then holds rows of the account store's replica and acnt is not read (acct_plan<true>).
+  const uint32_t* ecnt = nullptr;
 };
 
 // The rows body t expands to: key rows, payload candidates, signers of its checks.
@@ -649,6 +652,23 @@ inline void acct_body_rows(const AcctIn& in, size_t t, size_t* nk, size_t* nq, s
   for (uint64_t c = in.cb[t]; c < in.cb[t + 1]; ++c) {
     const size_t a = in.eacct[e0 + in.cacct[c]];
     g += in.acnt[2 * a] + in.acnt[2 * a + 1];
+  }
+  *nk = k;
+  *nq = q;
+  *ng = g;
+}
+
+// ... of a ledger call, from the per-entry counts its resolve made (AcctIn::ecnt).
+inline void acct_entry_rows(const AcctIn& in, size_t t, size_t* nk, size_t* nq, size_t* ng) {
+  size_t k = 0, q = 0, g = 0;
+  const uint64_t e0 = in.eb[t];
+  for (uint64_t e = e0; e < in.eb[t + 1]; ++e) {
+    k += in.ecnt[2 * e];
+    q += in.ecnt[2 * e + 1];
+  }
+  for (uint64_t c = in.cb[t]; c < in.cb[t + 1]; ++c) {
+    const uint64_t e = e0 + in.cacct[c];
+    g += in.ecnt[2 * e] + in.ecnt[2 * e + 1];
   }
   *nk = k;
   *nq = q;
@@ -670,14 +690,19 @@ struct AcctChunk {
 
 // The chunks of bodies [B0, B1): check_plan's bounds with the EXPANDED key,
 // payload-candidate and signer counts standing in for the explicit ones (a
-// body over a bound is a chunk alone).
+// body over a bound is a chunk alone).  kEntry: the counts are per entry (acct_entry_rows); the by-account
+// instantiation is the code it was without that case.
+template <bool kEntry = false>
 inline std::vector<AcctChunk> acct_plan(const AcctIn& in, size_t B0, size_t B1, size_t max_s, size_t max_k,
                                         size_t max_b, size_t max_c, size_t max_g) {
   std::vector<AcctChunk> out;
   const HintIn& hi = in.h;
   size_t t = B0;
   size_t k1 = 0, q1 = 0, g1 = 0;  // body t's rows
-  if (t < B1) acct_body_rows(in, t, &k1, &q1, &g1);
+  auto rows_of = [&](size_t b) {
+    kEntry ? acct_entry_rows(in, b, &k1, &q1, &g1) : acct_body_rows(in, b, &k1, &q1, &g1);
+  };
+  if (t < B1) rows_of(t);
   while (t < B1) {
     const size_t b0 = t, s0 = (size_t)hi.sb[t], c0 = (size_t)in.cb[t];
     size_t bytes = 0, nk = 0, nq = 0, ng = 0;
@@ -687,7 +712,7 @@ inline std::vector<AcctChunk> acct_plan(const AcctIn& in, size_t B0, size_t B1, 
       nq += q1;
       ng += g1;
       ++t;
-      if (t < B1) acct_body_rows(in, t, &k1, &q1, &g1);
+      if (t < B1) rows_of(t);
     } while (t < B1 && hi.sb[t + 1] - s0 <= max_s && nk + k1 + nq + q1 <= max_k && in.cb[t + 1] - c0 <= max_c &&
              ng + g1 <= max_g && bytes + al16(hi.len[t]) <= max_b);
     AcctChunk c{};

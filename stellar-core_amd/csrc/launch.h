@@ -165,6 +165,30 @@ hipError_t sv_launch_acct_count(const struct sv_acct_tab* T, const void* tab_ws,
                                 const struct sv_acct_out* O, void* ws, hipStream_t s);
 hipError_t sv_launch_acct_fill(const struct sv_acct_tab* T, const void* tab_ws, const struct sv_acct_use* U,
                                const struct sv_acct_out* O, void* ws, hipStream_t s);
+// ... with T an account store's replica (txacct.h sv_acct_tab::scnt): the rows and signers kernels' stride
+// instantiations.  The count launch above serves both layouts (it reads the counts in tab_ws alone).
+hipError_t sv_launch_acct_fill_stride(const struct sv_acct_tab* T, const void* tab_ws, const struct sv_acct_use* U,
+                                      const struct sv_acct_out* O, void* ws, hipStream_t s);
+// the account store's replica (sv_txstore.hip, txstore.h), every launch on the slot's one stream.  scatter: the
+// staged records of a host write (acctstore.h stage(): n_rows row records | n_pays payload records | n_slots
+// index records) into the replica.  lookup: per entry the row of bacct_id[e] (bacct[e] == SV_BACCT_BY_ID or bacct
+// null), of local account bacct[e] < n_local, or R->rows for none; `found` optional.  local: the caller's CSR
+// accounts [0, n_local) into the borrowed rows.  gather: the looked-up rows in sv_account_store_read's layout
+// (sv_store_read_offsets) into `out` (sv_store_read_bytes).
+struct sv_store_tab;
+int sv_store_block(void);
+size_t sv_store_read_bytes(uint64_t n);
+void sv_store_read_offsets(uint64_t n, size_t off[7]);
+void sv_store_tab_as_acct(const struct sv_store_tab* R, struct sv_acct_tab* T);
+hipError_t sv_launch_store_scatter(const struct sv_store_tab* R, const void* rec, uint32_t n_rows, uint32_t n_pays,
+                                   uint32_t n_slots, hipStream_t s);
+hipError_t sv_launch_store_lookup(const struct sv_store_tab* R, const uint32_t* bacct, const void* ids, uint64_t n,
+                                  uint32_t n_local, uint32_t max_probe, uint32_t* row_out, void* found,
+                                  hipStream_t s);
+hipError_t sv_launch_store_local(const struct sv_store_tab* R, const struct sv_acct_tab* L, uint32_t n_local,
+                                 hipStream_t s);
+hipError_t sv_launch_store_gather(const struct sv_store_tab* R, const uint32_t* rows, uint64_t n, void* out,
+                                  hipStream_t s);
 // one result per body (sv_txresult.hip, txresult.h), after the check kernel on the same stream: body_code (and
 // body_fail, optional) from I's check_ok / check_used; with bad_body or n_bad also the scan and, with bad_body and
 // bad_cap > 0, the fill of the ascending non-OK bodies (entries at or past bad_cap are never written, *n_bad is

@@ -46,6 +46,7 @@
 #include <condition_variable>
 #include <cstdlib>
 #include <mutex>
+#include <shared_mutex>
 #include <string>
 #include <vector>
 
@@ -55,6 +56,8 @@
 #include "host_image.h"
 #include "latlane.h"
 #include "launch.h"
+#include "sv_txledger.h"
+#include "txstore.h"
 
 namespace {
 using namespace sv;
@@ -329,6 +332,7 @@ void shutdown_locked() {
   for (Device* D : g_devs) delete D;
   g_devs.clear();
   g_inited = false;
+  (void)acct_store().configure(0, 0, 0, 0);  // (the account store goes with its replicas)
 }
 
 // Lifetime of the slot table.  Every entry point that reaches a Device holds
@@ -1130,6 +1134,48 @@ int check_device(int device, const HintDev& H, const sv_txchecks* ck, CheckPtrs 
       });
 }
 
+// The expansion of a device-resident by-account call on slot D (caller holds D.mu), ahead of the pipeline: D.txaws
+// holds `pre` bytes of the form's own and then the expansion's workspace and CSR arrays (growing drains the kernel
+// stream).  before(own, &tab, &tab_ws, &U), queued behind the caller's stream: the form's account table, its
+// per-account counts and ranks, and whatever it launches ahead of the count.  Then count + scan, the wait for the
+// three totals, the row arrays sized from them, and the fill (`stride`: txacct.h's instantiations for an account
+// store's replica).
+template <class Before>
+int acct_expand_device(Device& D, void* stream, sv_acct_use U, size_t pre, bool stride, const uint8_t* sig_len,
+                       bool clamp, Before before, TxDev* T) {
+  int rc;
+  const size_t k = U.nb, ne = U.ne, nc = U.nc;
+  const AcctBufs Hd = acct_layout(sv_acct_ws_bytes(k, ne, nc), k, nc, true, 0, 0, 0);
+  if (pre + Hd.head > D.txaws.cap) {
+    SV_HIP(hipStreamSynchronize(D.stream));
+    if ((rc = D.txaws.ensure(pre + Hd.head))) return rc;
+  }
+  if ((rc = D.h_txcnt.ensure(64))) return rc;
+  uint8_t* own = (uint8_t*)D.txaws.p;
+  uint8_t* head = own + pre;
+  SV_HIP(hipEventRecord(D.dep_in, (hipStream_t)stream));
+  SV_HIP(hipStreamWaitEvent(D.stream, D.dep_in, 0));
+  sv_acct_tab tab{};
+  const void* tab_ws = nullptr;
+  if ((rc = before(own, &tab, &tab_ws, &U))) return rc;
+  sv_acct_out O = acct_out(Hd, head, nullptr, 0, 0, 0);
+  SV_HIP(sv_launch_acct_count(&tab, tab_ws, &U, &O, head, D.stream));
+  SV_HIP(hipMemcpyAsync(D.h_txcnt.p, sv_acct_totals(head, k, ne, nc), 24, hipMemcpyDeviceToHost, D.stream));
+  // the wait this form adds: the expansion's three row counts are only known on the device
+  SV_HIP(hipStreamSynchronize(D.stream));
+  const uint64_t* tot = (const uint64_t*)D.h_txcnt.p;
+  if (tot[0] >> 32 || tot[1] >> 32 || tot[2] >> 32)
+    return fail(SV_ERR_INVALID_ARG, "tx checks by account: the expansion has 2^32 or more rows");
+  const size_t nk = (size_t)tot[0], nq = (size_t)tot[1], ng = (size_t)tot[2];
+  const AcctBufs L = acct_layout(sv_acct_ws_bytes(k, ne, nc), k, nc, true, nk, nq, ng);
+  if ((rc = D.txarows.ensure(L.bytes))) return rc;  // (the stream is idle)
+  O = acct_out(L, head, (uint8_t*)D.txarows.p, nk, nq, ng);
+  if (stride) SV_HIP(sv_launch_acct_fill_stride(&tab, tab_ws, &U, &O, head, D.stream));
+  else SV_HIP(sv_launch_acct_fill(&tab, tab_ws, &U, &O, head, D.stream));
+  acct_tables(O, sig_len, clamp, U.cbeg, nc, T);
+  return SV_OK;
+}
+
 // sv_ed25519_check_txbodies_accounts_device and, with `res`, sv_ed25519_decide_txbodies_accounts_device.
 int accounts_device(int device, const HintDev& H, const sv_txaccounts* A, CheckPtrs p, const sv_txresults* res,
                     void* d_digests, void* stream) {
@@ -1164,42 +1210,371 @@ int accounts_device(int device, const HintDev& H, const sv_txaccounts* A, CheckP
       },
       // the explicit tables, expanded on the slot's stream from the caller's account table
       [&](Device& D, TxDev* T) {
-        int rc;
-        const size_t na = A->n_accounts, ns = A->n_asigners, ne = A->n_bacct, nc = A->n_checks, k = H.nb;
-        const sv_acct_tab tab{A->acct_key,       A->acct_thresholds, A->asigner_begin,   A->asigner_type,
-                              A->asigner_weight, A->asigner_key,     A->asigner_payload, A->apayload,
-                              A->apayload_len,   na,                 ns,                 A->n_apayloads};
+        const size_t na = A->n_accounts, ns = A->n_asigners;
         const sv_acct_use U{A->bacct_begin, A->bacct, A->check_begin, A->check_acct, A->check_level, A->check_needed,
-                            k,              ne,       nc};
-        // the per-account counts and ranks, the expansion's workspace and its CSR arrays (growing drains the
-        // kernel stream), and the pinned words the totals come back in
-        const size_t tws = al16(sv_acct_tab_ws_bytes(na, ns));
-        const AcctBufs Hd = acct_layout(sv_acct_ws_bytes(k, ne, nc), k, nc, true, 0, 0, 0);
-        if (tws + Hd.head > D.txaws.cap) {
-          SV_HIP(hipStreamSynchronize(D.stream));
-          if ((rc = D.txaws.ensure(tws + Hd.head))) return rc;
-        }
-        if ((rc = D.h_txcnt.ensure(64))) return rc;
-        uint8_t* tab_ws = (uint8_t*)D.txaws.p;
-        uint8_t* head = tab_ws + tws;
-        SV_HIP(hipEventRecord(D.dep_in, (hipStream_t)stream));
-        SV_HIP(hipStreamWaitEvent(D.stream, D.dep_in, 0));
-        sv_acct_out O = acct_out(Hd, head, nullptr, 0, 0, 0);
-        SV_HIP(sv_launch_acct_table(&tab, tab_ws, D.stream));
-        SV_HIP(sv_launch_acct_count(&tab, tab_ws, &U, &O, head, D.stream));
-        SV_HIP(hipMemcpyAsync(D.h_txcnt.p, sv_acct_totals(head, k, ne, nc), 24, hipMemcpyDeviceToHost, D.stream));
-        // the wait this form adds: the expansion's three row counts are only known on the device
+                            H.nb,           A->n_bacct, A->n_checks};
+        // (the per-account counts and ranks ahead of the expansion's workspace)
+        return acct_expand_device(
+            D, stream, U, al16(sv_acct_tab_ws_bytes(na, ns)), false, A->sig_len, A->protocol_version >= 10,
+            [&](uint8_t* own, sv_acct_tab* tab, const void** tab_ws, sv_acct_use*) {
+              *tab = sv_acct_tab{A->acct_key,       A->acct_thresholds, {A->asigner_begin}, A->asigner_type,
+                                 A->asigner_weight, A->asigner_key,     A->asigner_payload, A->apayload,
+                                 A->apayload_len,   na,                 ns,                 A->n_apayloads};
+              *tab_ws = own;
+              SV_HIP(sv_launch_acct_table(tab, own, D.stream));
+              return (int)SV_OK;
+            },
+            T);
+      });
+}
+
+// ---- the account store's replicas (acctstore.h, txstore.h, sv_txstore.hip) ----
+
+// Serialises the store's writers and their replication (exclusive); a host-buffer ledger call holds it shared from
+// its resolve to its last chunk, so the rows it resolved stay what the replicas hold.  Lock order: g_life, g_as_mu,
+// g_mu, a slot's mu; the store's own lock is a leaf.  Every holder takes its LifeGuard FIRST: g_life prefers
+// writers, so a reader that held g_as_mu while it queued for g_life behind a teardown would close a cycle with a
+// store writer waiting for g_as_mu.
+std::shared_mutex g_as_mu;
+
+void as_point(AcctReplica& R, size_t accounts, size_t local, size_t pays, size_t slots, uint64_t seed) {
+  const size_t rows = accounts + local, prows = pays + kAcctStride * local;
+  const sv_store_layout L = sv_store_layout_of(rows, prows, slots);
+  uint8_t* b = (uint8_t*)R.buf.p;
+  R.tab = sv_store_tab{b + L.key,
+                       b + L.thr,
+                       (uint32_t*)(b + L.scnt),
+                       b + L.stype,
+                       (uint32_t*)(b + L.sweight),
+                       b + L.skey,
+                       (uint32_t*)(b + L.spay),
+                       b + L.pay,
+                       b + L.plen,
+                       (uint32_t*)(b + L.acnt),
+                       (uint32_t*)(b + L.rank),
+                       (uint32_t*)(b + L.index),
+                       (uint32_t)accounts,
+                       (uint32_t)rows,
+                       (uint32_t)pays,
+                       (uint32_t)prows,
+                       (uint32_t)slots,
+                       seed};
+}
+
+// The slot's replica at the host store's version (caller holds D.mu, device set, slot ready): nothing to do when
+// it is, else the host's arrays go up whole -- a slot's first use of the store, a new store, or a write that
+// failed half way on this slot.  *on: the store is on.  Waits for D.stream.
+int as_sync_locked(Device& D, bool* on) {
+  AcctStore& S = acct_store();
+  AcctReplica& R = D.as;
+  auto held = S.reader();
+  *on = S.on();
+  if (!*on) {
+    if (R.buf.p) {
+      SV_HIP(hipStreamSynchronize(D.stream));
+      R.release();
+    }
+    return SV_OK;
+  }
+  if (R.version == S.version()) return SV_OK;
+  const size_t acc = S.capacity(), pays = S.payload_capacity(), local = S.local_accounts(), slots = S.index_slots();
+  const sv_store_layout L = sv_store_layout_of(acc + local, pays + kAcctStride * local, slots);
+  SV_HIP(hipStreamSynchronize(D.stream));
+  R.version = 0;
+  int rc;
+  if ((rc = R.buf.ensure(L.bytes))) return rc;
+  as_point(R, acc, local, pays, slots, S.seed());
+  const sv_store_tab& t = R.tab;
+  SV_HIP(hipMemsetAsync(R.buf.p, 0, L.bytes, D.stream));
+  auto up = [&](void* d, const void* h, size_t bytes) {
+    return bytes ? hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, D.stream) : hipSuccess;
+  };
+  SV_HIP(up(t.key, S.key(), 32 * acc));
+  SV_HIP(up(t.thr, S.thr(), 4 * acc));
+  SV_HIP(up(t.scnt, S.scnt(), 4 * acc));
+  SV_HIP(up(t.stype, S.stype(), kAcctStride * acc));
+  SV_HIP(up(t.sweight, S.sweight(), 4 * kAcctStride * acc));
+  SV_HIP(up(t.skey, S.skey(), 32 * kAcctStride * acc));
+  SV_HIP(up(t.spay, S.spay(), 4 * kAcctStride * acc));
+  SV_HIP(up(t.pay, S.pay(), 64 * pays));
+  SV_HIP(up(t.plen, S.plen(), pays));
+  SV_HIP(up(t.acnt, S.acnt(), 8 * acc));
+  SV_HIP(up(t.rank, S.rank(), 4 * kAcctStride * acc));
+  SV_HIP(up(t.index, S.index(), 4 * slots));
+  SV_HIP(hipStreamSynchronize(D.stream));  // (the host's arrays are read under `held`)
+  R.max_probe = S.max_probe();
+  R.version = S.version();
+  return SV_OK;
+}
+
+// A write's staged records into every replica that held the version before it (g_as_mu held; the others catch up
+// by as_sync_locked at their next use).  Returns when each of them holds the write.
+int as_replicate(AcctDirty& dirty, uint64_t v0) {
+  AcctStore& S = acct_store();
+  const uint64_t v1 = S.version();
+  if (v1 == v0) return SV_OK;
+  AcctStore::Staged st;
+  try {
+    if (dirty.whole) throw std::bad_alloc();  // (the lists are incomplete)
+    S.stage(dirty, &st);
+  } catch (const std::bad_alloc&) {
+    st.rec.clear();
+    st.rows = ~(size_t)0;  // (no records: every replica goes stale and is copied whole at its next use)
+  }
+  const uint32_t probe = S.max_probe();
+  int rc = SV_OK;
+  // (the slot list under g_mu, the per-slot copies, kernels and waits outside it: the caller's LifeGuard keeps the
+  // slots alive, and calls that never touch the store do not wait for a write behind g_mu)
+  std::vector<Device*> devs;
+  {
+    std::lock_guard<std::mutex> g0(g_mu);
+    devs = g_devs;
+  }
+  for (Device* Dp : devs) {
+    Device& D = *Dp;
+    std::lock_guard<std::mutex> g(D.mu);
+    AcctReplica& R = D.as;
+    if (!D.ready || R.version != v0) continue;
+    R.version = 0;
+    if (st.rows == ~(size_t)0) continue;
+    auto one = [&]() -> int {
+      SV_HIP(hipSetDevice(D.phys));
+      const size_t bytes = st.rec.size();
+      if (bytes > R.d_stage.cap) {
         SV_HIP(hipStreamSynchronize(D.stream));
-        const uint64_t* tot = (const uint64_t*)D.h_txcnt.p;
+        int rc2;
+        if ((rc2 = R.d_stage.ensure(bytes))) return rc2;
+      }
+      int rc2;
+      if ((rc2 = R.h_stage.ensure(bytes + 16))) return rc2;
+      if (dirty.index_cleared) {  // clear(): the index and, as on the host, every row's counts
+        SV_HIP(hipMemsetAsync(R.tab.index, 0, 4 * (size_t)R.tab.slots, D.stream));
+        SV_HIP(hipMemsetAsync(R.tab.scnt, 0, 4 * (size_t)R.tab.accounts, D.stream));
+        SV_HIP(hipMemsetAsync(R.tab.acnt, 0, 8 * (size_t)R.tab.accounts, D.stream));
+      }
+      if (bytes) {
+        std::memcpy(R.h_stage.p, st.rec.data(), bytes);
+        SV_HIP(hipMemcpyAsync(R.d_stage.p, R.h_stage.p, bytes, hipMemcpyHostToDevice, D.stream));
+        SV_HIP(sv_launch_store_scatter(&R.tab, R.d_stage.p, (uint32_t)st.rows, (uint32_t)st.pays,
+                                       (uint32_t)st.slots, D.stream));
+      }
+      SV_HIP(hipStreamSynchronize(D.stream));
+      return SV_OK;
+    };
+    const int r = one();
+    if (r == SV_OK) {
+      R.max_probe = probe;
+      R.version = v1;
+    } else if (rc == SV_OK) {
+      rc = r;
+    }
+  }
+  return rc;
+}
+
+uint64_t as_seed() {
+  if (getenv("SV_ACCT_STORE_SEED")) return env_size("SV_ACCT_STORE_SEED", 0);
+  std::random_device rd;
+  return ((uint64_t)rd() << 32) ^ rd();
+}
+
+// Drops every replica (g_mu held).
+void as_drop_replicas_locked() {
+  for (Device* D : g_devs) {
+    std::lock_guard<std::mutex> g(D->mu);
+    if (!D->ready || !D->as.buf.p) continue;
+    (void)hipSetDevice(D->phys);
+    (void)hipStreamSynchronize(D->stream);
+    D->as.release();
+  }
+}
+
+// The host-buffer ledger forms' source of check_chunks_locked, beside the explicit one and AcctSrc: in.eacct holds
+// the replica rows the call's resolve found on the host index and in.ecnt their counts, so the planner knows the
+// expanded rows exactly and nothing waits for the device.  begin() brings the slot's replica to the store's
+// version and uploads only the call's local accounts, into the borrowed rows; a chunk carries 4 bytes per entry,
+// as in the by-account form, and the stride instantiations expand the replica in place.
+struct LedgerSrc {
+  const AcctIn& in;
+  const sv_txaccounts& A;  // (its account table: the local accounts)
+  int clamp;
+  sv_acct_tab tab{};
+  const void* tab_ws = nullptr;
+  AcctBufs L{};
+  std::vector<AcctChunk> plan(size_t B0, size_t B1) const {
+    return acct_plan<true>(in, B0, B1, stage_chunk(), stage_chunk(), txbody_chunk_bytes(), stage_chunk(),
+                           8 * stage_chunk());
+  }
+  int begin(Device& D, bool single) {
+    int rc;
+    bool on = false;
+    if ((rc = as_sync_locked(D, &on))) return rc;
+    if (!on) return fail(SV_ERR_INVALID_ARG, "tx checks by ledger: the account store is off");
+    AcctReplica& R = D.as;
+    if (A.n_accounts) {
+      sv_acct_tab local{};
+      const void* local_ws = nullptr;
+      if ((rc = acct_table_upload(D, A, &local, &local_ws))) return rc;
+      SV_HIP(sv_launch_store_local(&R.tab, &local, (uint32_t)A.n_accounts, D.stream));
+    }
+    sv_store_tab_as_acct(&R.tab, &tab);
+    tab_ws = R.tab.acnt;
+    if (!single) {
+      SV_HIP(hipEventRecord(D.dep_in, D.stream));
+      SV_HIP(hipStreamWaitEvent(D.h2d, D.dep_in, 0));
+    }
+    return SV_OK;
+  }
+  int prepare(Stage& s, const AcctChunk& c, size_t* bytes, size_t* nq) {
+    L = acct_layout(sv_acct_ws_bytes(c.p.b1 - c.p.b0, c.e1 - c.e0, c.c1 - c.c0), c.p.b1 - c.p.b0, c.c1 - c.c0, false,
+                    c.nk, c.nq, c.ng);
+    *bytes = c.bytes;
+    *nq = c.nq;
+    return s.d_acct.ensure(L.bytes);
+  }
+  void pack(const AcctChunk& c, uint8_t* hp) const { acct_pack(in, c, hp); }
+  int tables(Device&, Stage& s, const AcctChunk& c, const uint8_t* d, hipStream_t st, TxDev* T) const {
+    uint8_t* da = (uint8_t*)s.d_acct.p;
+    const size_t nc = c.c1 - c.c0;
+    const sv_acct_use U{(const uint64_t*)(d + c.o_eb), (const uint32_t*)(d + c.o_ea), (const uint64_t*)(d + c.o_cb),
+                        (const uint32_t*)(d + c.o_ca), d + c.o_lvl, (const int32_t*)(d + c.o_need), T->h.nb, c.e1 - c.e0,
+                        nc};
+    const sv_acct_out O = acct_out(L, da, da, c.nk, c.nq, c.ng);
+    SV_HIP(sv_launch_acct_count(&tab, tab_ws, &U, &O, da, st));
+    SV_HIP(sv_launch_acct_fill_stride(&tab, tab_ws, &U, &O, da, st));
+    acct_tables(O, in.sig_len ? d + c.o_sl : nullptr, clamp, U.cbeg, nc, T);
+    return SV_OK;
+  }
+};
+
+// sv_ed25519_check_txbodies_ledger and, with `res`, sv_ed25519_decide_txbodies_ledger (slices of whole bodies as in
+// the by-account form; every slot uploads the local accounts and reads its own replica).
+int ledger_host(const HintIn& h, size_t n_sigs, const sv_txledger* L, CheckPtrs p, const sv_txresults* res,
+                uint8_t* digests, const sv_opts* opts) {
+  const sv_txaccounts* A = L && L->struct_size >= sizeof(sv_txledger) ? L->accts : nullptr;
+  LifeGuard life_;  // (first, as the lock order has it: check_call_host's own guard then nests)
+  std::shared_lock<std::shared_mutex> pinned(g_as_mu);  // no write to the store from the resolve to the last chunk
+  std::vector<uint32_t> rows, ecnt;
+  return check_call_host(
+      h, n_sigs, p, res, digests, opts,
+      [&](CheckPtrs seen, size_t* n_checks) {
+        std::vector<uint8_t> found;
+        std::vector<uint32_t> view;
+        std::vector<uint8_t> vkey, vthr;
+        std::vector<uint64_t> vsbeg;
+        int rc = ledger_resolve(L, &rows, &ecnt, &found, &view, &vkey, &vthr, &vsbeg);
+        if (rc == SV_ERR_ALLOC) return fail(rc, "tx checks by ledger: no memory (or no thread) for resolving the entries");
+        if (rc)
+          return fail(rc,
+                      "tx checks by ledger: null struct or a struct_size that is too small, the account store is off, "
+                      "more local accounts than local_accounts, a local account with more than 20 signers or a "
+                      "malformed local table, a bacct entry that is neither SV_BACCT_BY_ID nor a local index, or an "
+                      "entry by ID with bacct_id NULL");
+        // the twin's rules, on the local accounts plus one empty account that stands for every entry by ID
+        sv_txaccounts V = *A;
+        V.acct_key = vkey.data();
+        V.acct_thresholds = vthr.data();
+        V.asigner_begin = vsbeg.data();
+        V.bacct = view.data();
+        V.n_accounts = A->n_accounts + 1;
+        if (sv_txaccounts_check(h.nid, h.bodies, h.off, h.len, h.kind, h.nb, h.sb, h.hint, h.sig, n_sigs, &V, seen.ok,
+                                seen.weight, seen.used, nullptr))
+          return fail(SV_ERR_INVALID_ARG,
+                      "tx checks by ledger: null pointer, body kind > 2, malformed CSR array, check_acct outside its "
+                      "body, level > 3, signer type > 3, payload index >= n_apayloads, apayload_len or sig_len > 64, "
+                      "more than 64 signatures in a body with checks, protocol 7, 2^32 or more rows, or a struct_size "
+                      "that is too small");
+        // (the expansion's totals, with the store accounts' rows counted)
+        uint64_t tot[3] = {0, 0, 0};
+        for (size_t e = 0; e < A->n_bacct; ++e) tot[0] += ecnt[2 * e], tot[1] += ecnt[2 * e + 1];
+        for (size_t t = 0; t < h.nb; ++t)
+          for (uint64_t c = A->check_begin[t]; c < A->check_begin[t + 1]; ++c) {
+            const uint64_t e = A->bacct_begin[t] + A->check_acct[c];
+            tot[2] += ecnt[2 * e] + ecnt[2 * e + 1];
+          }
         if (tot[0] >> 32 || tot[1] >> 32 || tot[2] >> 32)
-          return fail(SV_ERR_INVALID_ARG, "tx checks by account: the expansion has 2^32 or more rows");
-        const size_t nk = (size_t)tot[0], nq = (size_t)tot[1], ng = (size_t)tot[2];
-        const AcctBufs L = acct_layout(sv_acct_ws_bytes(k, ne, nc), k, nc, true, nk, nq, ng);
-        if ((rc = D.txarows.ensure(L.bytes))) return rc;  // (the stream is idle)
-        O = acct_out(L, head, (uint8_t*)D.txarows.p, nk, nq, ng);
-        SV_HIP(sv_launch_acct_fill(&tab, tab_ws, &U, &O, head, D.stream));
-        acct_tables(O, A->sig_len, A->protocol_version >= 10, A->check_begin, nc, T);
+          return fail(SV_ERR_INVALID_ARG, "tx checks by ledger: the expansion has 2^32 or more rows");
+        if (L->bacct_found && A->n_bacct) std::memcpy(L->bacct_found, found.data(), A->n_bacct);
+        *n_checks = A->n_checks;
         return (int)SV_OK;
+      },
+      [&](Device& D, size_t B0, size_t B1, const CheckOut& out, int path) {
+        AcctIn in{h, A->sig_len, A->bacct_begin, rows.data(), A->check_begin, A->check_acct, A->check_level,
+                  A->check_needed, nullptr};
+        in.ecnt = ecnt.data();
+        const int clamp = A->protocol_version >= 10;
+        return with_slot(D, [&] {
+          LedgerSrc src{in, *A, clamp};
+          return check_chunks_locked(D, src, B0, B1, out, path);
+        });
+      });
+}
+
+// sv_ed25519_check_txbodies_ledger_device and, with `res`, sv_ed25519_decide_txbodies_ledger_device: the twin's
+// sequence with the slot's replica as the account table (txacct.h: the stride instantiations read it in place).
+// Ahead of the count: the local accounts into the borrowed rows, and the lookup of every entry's row.
+int ledger_device(int device, const HintDev& H, const sv_txledger* L, CheckPtrs p, const sv_txresults* res,
+                  void* d_digests, void* stream) {
+  const sv_txaccounts* A = L && L->struct_size >= sizeof(sv_txledger) ? L->accts : nullptr;
+  return check_call_device(
+      device, H, p, res, d_digests, stream,
+      [&](CheckPtrs seen, size_t* n_checks) {
+        if (!H.nid || !A || A->struct_size < sizeof(sv_txaccounts))
+          return fail(SV_ERR_INVALID_ARG, "tx checks by ledger: null pointer or a struct_size that is too small");
+        const size_t na = A->n_accounts, ns = A->n_asigners, np = A->n_apayloads, ne = A->n_bacct, nc = A->n_checks;
+        if ((H.nb && (!H.bodies || !H.off || !H.len || !H.kind || !H.sb || !A->bacct_begin || !A->check_begin)) ||
+            (H.m && (!H.hint || !H.sig)) || (na && (!A->acct_key || !A->acct_thresholds || !A->asigner_begin)) ||
+            (ns && (!A->asigner_type || !A->asigner_weight || !A->asigner_key)) ||
+            (np && (!A->apayload || !A->apayload_len)) || (ne && !A->bacct) ||
+            (nc && (H.nb == 0 || !A->check_acct || !A->check_level || !seen.ok || !seen.weight || !seen.used)))
+          return fail(SV_ERR_INVALID_ARG, "tx checks by ledger: null pointer");
+        if (A->protocol_version == 7)
+          return fail(SV_ERR_INVALID_ARG, "tx checks by ledger: protocol 7 needs no engine");
+        if ((uint64_t)H.m >> 32 || (uint64_t)na >> 32 || (uint64_t)ns >> 32 || (uint64_t)np >> 32 ||
+            (uint64_t)ne >> 32 || (uint64_t)nc >> 32)
+          return fail(SV_ERR_INVALID_ARG, "tx checks by ledger: 2^32 or more rows");
+        if (!aligned16(H.sig) || !aligned16(d_digests) || !aligned16(A->acct_key) || !aligned16(A->asigner_key) ||
+            !aligned16(A->apayload) || !aligned16(L->bacct_id) || ((uintptr_t)H.hint & 3u) ||
+            ((uintptr_t)A->asigner_begin & 7u) || ((uintptr_t)A->bacct_begin & 7u) ||
+            ((uintptr_t)A->check_begin & 7u) || ((uintptr_t)A->asigner_weight & 3u) ||
+            ((uintptr_t)A->asigner_payload & 3u) || ((uintptr_t)A->bacct & 3u) || ((uintptr_t)A->check_acct & 3u) ||
+            ((uintptr_t)A->check_needed & 3u) || ((uintptr_t)seen.weight & 3u) || ((uintptr_t)seen.used & 7u))
+          return fail(SV_ERR_ALIGN,
+                      "sig/digests/acct_key/asigner_key/apayload/bacct_id must be 16-byte aligned, the other arrays "
+                      "naturally aligned");
+        *n_checks = nc;
+        return (int)SV_OK;
+      },
+      [&](Device& D, TxDev* T) {
+        int rc;
+        bool on = false;
+        if ((rc = as_sync_locked(D, &on))) return rc;
+        if (!on) return fail(SV_ERR_INVALID_ARG, "tx checks by ledger: the account store is off");
+        AcctReplica& R = D.as;
+        const size_t ne = A->n_bacct;
+        const uint32_t nl = (uint32_t)std::min<size_t>(A->n_accounts, R.tab.rows - R.tab.accounts);
+        const sv_acct_use U{A->bacct_begin, nullptr, A->check_begin, A->check_acct, A->check_level, A->check_needed,
+                            H.nb,           ne,      A->n_checks};
+        // (the entries' rows ahead of the expansion's workspace)
+        return acct_expand_device(
+            D, stream, U, al16(4 * ne) + 16, true, A->sig_len, A->protocol_version >= 10,
+            [&](uint8_t* own, sv_acct_tab* tab, const void** tab_ws, sv_acct_use* Uo) {
+              const sv_acct_tab local{A->acct_key,       A->acct_thresholds, {A->asigner_begin}, A->asigner_type,
+                                      A->asigner_weight, A->asigner_key,     A->asigner_payload, A->apayload,
+                                      A->apayload_len,   A->n_accounts,      A->n_asigners,      A->n_apayloads};
+              SV_HIP(sv_launch_store_local(&R.tab, &local, nl, D.stream));
+              int rc2;
+              if ((rc2 = R.timer.begin(D.stream))) return rc2;
+              SV_HIP(sv_launch_store_lookup(&R.tab, A->bacct, L->bacct_id, ne, nl, R.max_probe, (uint32_t*)own,
+                                            L->bacct_found, D.stream));
+              if ((rc2 = R.timer.end(D.stream, ne))) return rc2;
+              R.lookups += ne;
+              Uo->eacct = (const uint32_t*)own;
+              sv_store_tab_as_acct(&R.tab, tab);
+              *tab_ws = R.tab.acnt;
+              return (int)SV_OK;
+            },
+            T);
       });
 }
 }  // namespace
@@ -1299,6 +1674,250 @@ int sv_ed25519_decide_txbodies_accounts_device(int device, const uint8_t* networ
                                 {network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin,
                                  d_hint, d_sig, n_sigs, nullptr, nullptr, 0},
                                 A, decide_outputs(res), res, d_digests, stream);
+}
+
+int sv_ed25519_check_txbodies_ledger(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                     const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                     const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig, size_t n_sigs,
+                                     const sv_txledger* L, uint8_t* check_ok, uint32_t* check_weight,
+                                     uint64_t* check_used, uint8_t* digests, const sv_opts* opts) {
+  return ledger_host({network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig, nullptr,
+                      nullptr},
+                     n_sigs, L, {check_ok, check_weight, check_used}, nullptr, digests, opts);
+}
+
+int sv_ed25519_decide_txbodies_ledger(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                      const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                      const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig,
+                                      size_t n_sigs, const sv_txledger* L, const sv_txresults* res, uint8_t* digests,
+                                      const sv_opts* opts) {
+  return !res ? no_results()
+              : ledger_host({network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, hint, sig,
+                             nullptr, nullptr},
+                            n_sigs, L, decide_outputs(res), res, digests, opts);
+}
+
+// The CPU forms: the expansion on the host (sv_txledger.cpp), then the twin's CPU path.  bacct_found is written
+// once the call is accepted.
+static int ledger_cpu(const sv_txledger* L, LedgerCombined* c) {
+  const int rc = ledger_combine(L, c);
+  if (rc == SV_ERR_ALLOC) return fail(rc, "tx checks by ledger: no memory for the combined table");
+  if (rc)
+    return fail(rc,
+                "tx checks by ledger: null struct or a struct_size that is too small, the account store is off, more "
+                "local accounts than local_accounts, a local account with more than 20 signers or a malformed local "
+                "table, a bacct entry that is neither SV_BACCT_BY_ID nor a local index, or an entry by ID with "
+                "bacct_id NULL");
+  return SV_OK;
+}
+static int ledger_cpu_done(int rc, const sv_txledger* L, const LedgerCombined& c) {
+  if (rc) return fail(rc, "tx checks by ledger: refused by the by-account form's argument check on the combined table");
+  if (L->bacct_found && !c.found.empty()) std::memcpy(L->bacct_found, c.found.data(), c.found.size());
+  return SV_OK;
+}
+
+int sv_ed25519_check_txbodies_ledger_cpu(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                         const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                         const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig,
+                                         size_t n_sigs, const sv_txledger* L, uint8_t* check_ok,
+                                         uint32_t* check_weight, uint64_t* check_used, uint8_t* digests, int threads) {
+  LedgerCombined c;
+  int rc = ledger_cpu(L, &c);
+  if (rc) return rc;
+  rc = sv_ed25519_check_txbodies_accounts_cpu(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin,
+                                              hint, sig, n_sigs, &c.accts, check_ok, check_weight, check_used, digests,
+                                              threads);
+  return ledger_cpu_done(rc, L, c);
+}
+
+int sv_ed25519_decide_txbodies_ledger_cpu(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                          const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                          const uint64_t* sig_begin, const uint8_t* hint, const uint8_t* sig,
+                                          size_t n_sigs, const sv_txledger* L, const sv_txresults* res,
+                                          uint8_t* digests, int threads) {
+  LedgerCombined c;
+  int rc = ledger_cpu(L, &c);
+  if (rc) return rc;
+  rc = sv_ed25519_decide_txbodies_accounts_cpu(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin,
+                                               hint, sig, n_sigs, &c.accts, res, digests, threads);
+  return ledger_cpu_done(rc, L, c);
+}
+
+int sv_ed25519_check_txbodies_ledger_device(int device, const uint8_t* network_id, const void* d_bodies,
+                                            const uint64_t* d_body_off, const uint32_t* d_body_len,
+                                            const uint8_t* d_body_kind, size_t n_bodies, const uint64_t* d_sig_begin,
+                                            const void* d_hint, const void* d_sig, size_t n_sigs,
+                                            const sv_txledger* L, void* d_check_ok, uint32_t* d_check_weight,
+                                            uint64_t* d_check_used, void* d_digests, void* stream) {
+  return ledger_device(device,
+                       {network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin, d_hint,
+                        d_sig, n_sigs, nullptr, nullptr, 0},
+                       L, {(uint8_t*)d_check_ok, d_check_weight, d_check_used}, nullptr, d_digests, stream);
+}
+
+int sv_ed25519_decide_txbodies_ledger_device(int device, const uint8_t* network_id, const void* d_bodies,
+                                             const uint64_t* d_body_off, const uint32_t* d_body_len,
+                                             const uint8_t* d_body_kind, size_t n_bodies,
+                                             const uint64_t* d_sig_begin, const void* d_hint, const void* d_sig,
+                                             size_t n_sigs, const sv_txledger* L, const sv_txresults* res,
+                                             void* d_digests, void* stream) {
+  return !res ? no_results()
+              : ledger_device(device,
+                              {network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies, d_sig_begin,
+                               d_hint, d_sig, n_sigs, nullptr, nullptr, 0},
+                              L, decide_outputs(res), res, d_digests, stream);
+}
+
+int sv_set_account_store(size_t accounts, size_t payloads, size_t local_accounts) {
+  LifeGuard life_;
+  std::unique_lock<std::shared_mutex> gw(g_as_mu);
+  const int rc = acct_store().configure(accounts, payloads, local_accounts, accounts ? as_seed() : 0);
+  if (rc == SV_ERR_INVALID_ARG) return fail(rc, "account store: a capacity above 2^26");
+  if (rc) return fail(rc, "account store: no memory for the host copy");
+  // (the replicas of the store that was: the next use of a slot builds the new one's)
+  std::lock_guard<std::mutex> g0(g_mu);
+  as_drop_replicas_locked();
+  return SV_OK;
+}
+
+int sv_account_store_upsert(const sv_txaccounts* A) {
+  LifeGuard life_;
+  if (!A || A->struct_size < sizeof(sv_txaccounts)) return fail(SV_ERR_INVALID_ARG, "account store: null table");
+  const AcctRows rows{A->acct_key,       A->acct_thresholds, A->asigner_begin, A->asigner_type, A->asigner_weight,
+                      A->asigner_key,    A->asigner_payload, A->apayload,      A->apayload_len, A->n_accounts,
+                      A->n_asigners,     A->n_apayloads};
+  std::unique_lock<std::shared_mutex> gw(g_as_mu);
+  AcctStore& S = acct_store();
+  const uint64_t v0 = S.version();
+  AcctDirty dirty;
+  const int rc = S.upsert(rows, &dirty);
+  if (rc == SV_ERR_INVALID_ARG)
+    return fail(rc,
+                "account store upsert: the store is off, a null array, a malformed asigner_begin, more than 20 "
+                "signers, a signer type > 3, a payload index >= n_apayloads or an apayload_len > 64");
+  if (rc) return fail(rc, "account store upsert: no room for the new accounts or payload rows");
+  return as_replicate(dirty, v0);
+}
+
+int sv_account_store_erase(const uint8_t* ids, size_t n) {
+  LifeGuard life_;
+  std::unique_lock<std::shared_mutex> gw(g_as_mu);
+  AcctStore& S = acct_store();
+  const uint64_t v0 = S.version();
+  AcctDirty dirty;
+  const int rc = S.erase(ids, n, &dirty);
+  if (rc) return fail(rc, "account store erase: the store is off, or null ids");
+  return as_replicate(dirty, v0);
+}
+
+int sv_account_store_clear(void) {
+  LifeGuard life_;
+  std::unique_lock<std::shared_mutex> gw(g_as_mu);
+  AcctStore& S = acct_store();
+  const uint64_t v0 = S.version();
+  AcctDirty dirty;
+  S.clear(&dirty);
+  return as_replicate(dirty, v0);
+}
+
+int sv_account_store_get_stats(int device, sv_account_store_stats* out) {
+  LifeGuard life_;
+  if (!out || out->struct_size < sizeof(sv_account_store_stats))
+    return fail(SV_ERR_INVALID_ARG, "account store stats: null struct or struct_size too small");
+  AcctStats st;
+  acct_store().stats(&st);
+  out->capacity = st.capacity;
+  out->accounts = st.accounts;
+  out->payload_capacity = st.payload_capacity;
+  out->payloads = st.payloads;
+  out->local_accounts = st.local_accounts;
+  out->index_slots = st.index_slots;
+  out->max_probe = st.max_probe;
+  out->upsert_calls = st.upsert_calls;
+  out->inserted = st.inserted;
+  out->replaced = st.replaced;
+  out->erase_calls = st.erase_calls;
+  out->erased = st.erased;
+  out->erase_absent = st.erase_absent;
+  out->host_bytes = st.host_bytes;
+  out->device_bytes = out->replica_current = out->lookups = 0;
+  out->lookup_ms = 0;
+  if (device == -1) return SV_OK;
+  Device* Dp;
+  int rc = slot_arg(device, Dp);
+  if (rc) return rc;
+  Device& D = *Dp;
+  std::lock_guard<std::mutex> g(D.mu);
+  AcctReplica& R = D.as;
+  if (!D.ready || !R.buf.p) return SV_OK;
+  SV_HIP(hipSetDevice(D.phys));
+  SV_HIP(hipStreamSynchronize(D.stream));
+  if ((rc = R.timer.harvest())) return rc;
+  out->device_bytes = R.bytes();
+  out->replica_current = R.version == st.version ? 1 : 0;
+  out->lookups = R.lookups;
+  out->lookup_ms = R.timer.total_ms;
+  return SV_OK;
+}
+
+int sv_account_store_read(int device, const uint8_t* ids, size_t n, uint8_t* found, uint8_t* thresholds,
+                          uint32_t* n_signers, uint8_t* signer_type, uint32_t* signer_weight, uint8_t* signer_key,
+                          uint8_t* signer_payload, uint8_t* signer_payload_len) {
+  LifeGuard life_;
+  if (n == 0) return SV_OK;
+  if (!ids) return fail(SV_ERR_INVALID_ARG, "account store read: null ids");
+  if ((uint64_t)n >> 24) return fail(SV_ERR_INVALID_ARG, "account store read: 2^24 or more IDs");
+  const AcctReadOut o{found,      thresholds,     n_signers,         signer_type, signer_weight,
+                      signer_key, signer_payload, signer_payload_len};
+  if (device == -1) {
+    acct_store().read(ids, n, o);
+    return SV_OK;
+  }
+  int rc;
+  if ((rc = debug_fail())) return rc;
+  Device* Dp;
+  if ((rc = slot_arg(device, Dp))) return rc;
+  Device& D = *Dp;
+  std::lock_guard<std::mutex> g(D.mu);
+  SV_HIP(hipSetDevice(D.phys));
+  if ((rc = ready_locked(D))) return rc;
+  bool on = false;
+  if ((rc = as_sync_locked(D, &on))) return rc;
+  if (!on) {
+    acct_store().read(ids, n, o);  // (off: nothing is found, here as on the host)
+    return SV_OK;
+  }
+  AcctReplica& R = D.as;
+  // ids | rows | found | the gathered accounts, everything on D.stream in order
+  const size_t o_rows = 32 * n, o_found = o_rows + al16(4 * n), o_out = o_found + al16(n);
+  const size_t bytes = o_out + sv_store_read_bytes(n);
+  if (bytes > R.ws.cap) {
+    SV_HIP(hipStreamSynchronize(D.stream));
+    if ((rc = R.ws.ensure(bytes))) return rc;
+  }
+  uint8_t* w = (uint8_t*)R.ws.p;
+  SV_HIP(hipMemcpyAsync(w, ids, 32 * n, hipMemcpyHostToDevice, D.stream));
+  if ((rc = R.timer.begin(D.stream))) return rc;
+  SV_HIP(sv_launch_store_lookup(&R.tab, nullptr, w, n, 0, R.max_probe, (uint32_t*)(w + o_rows), w + o_found,
+                                D.stream));
+  if ((rc = R.timer.end(D.stream, n))) return rc;
+  R.lookups += n;
+  SV_HIP(sv_launch_store_gather(&R.tab, (const uint32_t*)(w + o_rows), n, w + o_out, D.stream));
+  size_t off[7];
+  sv_store_read_offsets(n, off);
+  auto down = [&](void* h, const uint8_t* d, size_t b) {
+    return h ? hipMemcpyAsync(h, d, b, hipMemcpyDeviceToHost, D.stream) : hipSuccess;
+  };
+  SV_HIP(down(found, w + o_found, n));
+  SV_HIP(down(thresholds, w + o_out + off[0], 4 * n));
+  SV_HIP(down(n_signers, w + o_out + off[1], 4 * n));
+  SV_HIP(down(signer_type, w + o_out + off[2], 20 * n));
+  SV_HIP(down(signer_weight, w + o_out + off[3], 80 * n));
+  SV_HIP(down(signer_key, w + o_out + off[4], 640 * n));
+  SV_HIP(down(signer_payload, w + o_out + off[5], 1280 * n));
+  SV_HIP(down(signer_payload_len, w + o_out + off[6], 20 * n));
+  SV_HIP(hipStreamSynchronize(D.stream));
+  return SV_OK;
 }
 
 int sv_ed25519_verify_device(int device, const void* d_pk, const void* d_sig, const void* d_msg,
@@ -1742,7 +2361,7 @@ int sv_workspace_bytes(int device, size_t* bytes) {
   std::lock_guard<std::mutex> gl(Dp->lat.mu);
   std::lock_guard<std::mutex> g(Dp->mu);
   size_t b = Dp->ws.cap + Dp->txmsg.cap + Dp->txpk.cap + Dp->txsg.cap + Dp->txpair.cap + Dp->txchk.cap + Dp->txpp.cap;
-  b += Dp->txatab.cap + Dp->txaws.cap + Dp->txarows.cap + Dp->txres.cap + Dp->vc.bytes();
+  b += Dp->txatab.cap + Dp->txaws.cap + Dp->txarows.cap + Dp->txres.cap + Dp->vc.bytes() + Dp->as.bytes();
   for (const LatCtx& c : Dp->lat.ctx) b += c.ws.cap + c.d_in.cap + c.d_out.cap + c.d_keys.cap;
   *bytes = b;
   return SV_OK;

@@ -28,6 +28,8 @@
 //            per body would copy a 20-signer account's rows one after another
 //            while its neighbours idle (DESIGN.md 3.11 on body-per-lane)
 //   signers  SV_ACCT_GROUP lanes per check (its body from the count's search), striding over its signers
+// rows and signers exist twice: for the CSR table of a by-account call, and -- the _stride kernels -- for the
+// fixed-stride rows of an account store's replica (sv_txstore.hip), which the ledger forms expand in place.
 //
 // Device-resident tables are not validated by the host: txacct.h clamps every
 // range and index, and no row is written at or past the row counts the caller
@@ -133,41 +135,53 @@ __global__ __launch_bounds__(SV_ACCTBLOCK) void sv_acct_begin_kernel(sv_acctpara
   if (live) p.O.signer_begin[i] = g;
 }
 
-__global__ __launch_bounds__(SV_ACCTBLOCK) void sv_acct_rows_kernel(sv_acctparams p) {
-  const uint64_t t = (uint64_t)blockIdx.x * (SV_ACCTBLOCK / SV_ACCT_GROUP) + threadIdx.x / SV_ACCT_GROUP;
-  const unsigned gl = threadIdx.x % SV_ACCT_GROUP;
-  if (t >= p.U.nb) return;
-  uint64_t e0, e1;
-  sv_acct_entries(p.U, t, &e0, &e1);
-  uint64_t krow = p.O.key_begin[t], qrow = p.O.pkey_begin[t];
-  SV_NOUNROLL for (uint64_t e = e0; e < e1; ++e) {
-    if (gl == 0) {
-      p.erow[2 * e] = (uint32_t)krow;
-      p.erow[2 * e + 1] = (uint32_t)qrow;
-    }
-    const uint64_t a = p.U.eacct[e];
-    if (a >= p.T.na) continue;
-    const uint64_t n = (uint64_t)p.acnt[2 * a] + p.acnt[2 * a + 1];
-    SV_NOUNROLL for (uint64_t j = gl; j < n; j += SV_ACCT_GROUP) sv_acct_fill_row(p.T, p.rank, a, j, krow, qrow, p.O);
-    krow += p.acnt[2 * a];
-    qrow += p.acnt[2 * a + 1];
+// rows and signers: one body each, written as a kernel for a CSR table (kStride false) and for an account store's
+// replica (true: txacct.h sv_acct_tab::scnt; sv_txstore.hip).  The bodies are macros and not inlined functions, so
+// the CSR kernels are the plain kernels they were: through a function their instructions come out in another
+// order (by reference the signers kernel also needs two more SGPRs).
+#define SV_ACCT_ROWS_KERNEL(name, kStride)                                                                         \
+  __global__ __launch_bounds__(SV_ACCTBLOCK) void name(sv_acctparams p) {                                          \
+    const uint64_t t = (uint64_t)blockIdx.x * (SV_ACCTBLOCK / SV_ACCT_GROUP) + threadIdx.x / SV_ACCT_GROUP;        \
+    const unsigned gl = threadIdx.x % SV_ACCT_GROUP;                                                               \
+    if (t >= p.U.nb) return;                                                                                       \
+    uint64_t e0, e1;                                                                                               \
+    sv_acct_entries(p.U, t, &e0, &e1);                                                                             \
+    uint64_t krow = p.O.key_begin[t], qrow = p.O.pkey_begin[t];                                                    \
+    SV_NOUNROLL for (uint64_t e = e0; e < e1; ++e) {                                                               \
+      if (gl == 0) {                                                                                               \
+        p.erow[2 * e] = (uint32_t)krow;                                                                            \
+        p.erow[2 * e + 1] = (uint32_t)qrow;                                                                        \
+      }                                                                                                            \
+      const uint64_t a = p.U.eacct[e];                                                                             \
+      if (a >= p.T.na) continue;                                                                                   \
+      const uint64_t n = (uint64_t)p.acnt[2 * a] + p.acnt[2 * a + 1];                                              \
+      SV_NOUNROLL for (uint64_t j = gl; j < n; j += SV_ACCT_GROUP)                                                 \
+        sv_acct_fill_row<kStride>(p.T, p.rank, a, j, krow, qrow, p.O);                                             \
+      krow += p.acnt[2 * a];                                                                                       \
+      qrow += p.acnt[2 * a + 1];                                                                                   \
+    }                                                                                                              \
   }
-}
 
-__global__ __launch_bounds__(SV_ACCTBLOCK) void sv_acct_signers_kernel(sv_acctparams p) {
-  const uint64_t c = (uint64_t)blockIdx.x * (SV_ACCTBLOCK / SV_ACCT_GROUP) + threadIdx.x / SV_ACCT_GROUP;
-  const unsigned gl = threadIdx.x % SV_ACCT_GROUP;
-  if (c >= p.U.nc) return;
-  const uint64_t t = p.cbody[c];
-  if (t >= p.U.nb) return;
-  uint64_t e;
-  const uint64_t a = sv_acct_check_account(p.T, p.U, t, c, &e);
-  if (a >= p.T.na) return;
-  const uint64_t n = p.cnt_g[c], g0 = p.O.signer_begin[c];
-  const uint64_t krow = p.erow[2 * e], qrow = p.erow[2 * e + 1];
-  SV_NOUNROLL for (uint64_t j = gl; j < n; j += SV_ACCT_GROUP)
-    sv_acct_fill_signer(p.T, p.rank, a, j, krow, qrow, g0 + j, p.O);
-}
+#define SV_ACCT_SIGNERS_KERNEL(name, kStride)                                                                      \
+  __global__ __launch_bounds__(SV_ACCTBLOCK) void name(sv_acctparams p) {                                          \
+    const uint64_t c = (uint64_t)blockIdx.x * (SV_ACCTBLOCK / SV_ACCT_GROUP) + threadIdx.x / SV_ACCT_GROUP;        \
+    const unsigned gl = threadIdx.x % SV_ACCT_GROUP;                                                               \
+    if (c >= p.U.nc) return;                                                                                       \
+    const uint64_t t = p.cbody[c];                                                                                 \
+    if (t >= p.U.nb) return;                                                                                       \
+    uint64_t e;                                                                                                    \
+    const uint64_t a = sv_acct_check_account(p.T, p.U, t, c, &e);                                                  \
+    if (a >= p.T.na) return;                                                                                       \
+    const uint64_t n = p.cnt_g[c], g0 = p.O.signer_begin[c];                                                       \
+    const uint64_t krow = p.erow[2 * e], qrow = p.erow[2 * e + 1];                                                 \
+    SV_NOUNROLL for (uint64_t j = gl; j < n; j += SV_ACCT_GROUP)                                                   \
+      sv_acct_fill_signer<kStride>(p.T, p.rank, a, j, krow, qrow, g0 + j, p.O);                                    \
+  }
+
+SV_ACCT_ROWS_KERNEL(sv_acct_rows_kernel, false)
+SV_ACCT_SIGNERS_KERNEL(sv_acct_signers_kernel, false)
+SV_ACCT_ROWS_KERNEL(sv_acct_rows_stride_kernel, true)
+SV_ACCT_SIGNERS_KERNEL(sv_acct_signers_stride_kernel, true)
 
 namespace {
 
@@ -248,18 +262,30 @@ hipError_t sv_launch_acct_count(const sv_acct_tab* T, const void* tab_ws, const 
   return hipGetLastError();
 }
 
-hipError_t sv_launch_acct_fill(const sv_acct_tab* T, const void* tab_ws, const sv_acct_use* U, const sv_acct_out* O,
-                               void* ws, hipStream_t s) {
+static hipError_t acct_fill(const sv_acct_tab* T, const void* tab_ws, const sv_acct_use* U, const sv_acct_out* O,
+                            void* ws, hipStream_t s, bool stride) {
   const sv_acctparams p = acct_params(*T, tab_ws, *U, *O, ws);
   const uint64_t per = SV_ACCTBLOCK / SV_ACCT_GROUP;
   if (U->nb) {
-    hipLaunchKernelGGL(sv_acct_rows_kernel, dim3((unsigned)((U->nb + per - 1) / per)), dim3(SV_ACCTBLOCK), 0, s, p);
+    hipLaunchKernelGGL(stride ? sv_acct_rows_stride_kernel : sv_acct_rows_kernel,
+                       dim3((unsigned)((U->nb + per - 1) / per)), dim3(SV_ACCTBLOCK), 0, s, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   if (U->nc && O->ng)
-    hipLaunchKernelGGL(sv_acct_signers_kernel, dim3((unsigned)((U->nc + per - 1) / per)), dim3(SV_ACCTBLOCK), 0, s, p);
+    hipLaunchKernelGGL(stride ? sv_acct_signers_stride_kernel : sv_acct_signers_kernel,
+                       dim3((unsigned)((U->nc + per - 1) / per)), dim3(SV_ACCTBLOCK), 0, s, p);
   return hipGetLastError();
+}
+
+hipError_t sv_launch_acct_fill(const sv_acct_tab* T, const void* tab_ws, const sv_acct_use* U, const sv_acct_out* O,
+                               void* ws, hipStream_t s) {
+  return acct_fill(T, tab_ws, U, O, ws, s, false);
+}
+
+hipError_t sv_launch_acct_fill_stride(const sv_acct_tab* T, const void* tab_ws, const sv_acct_use* U,
+                                      const sv_acct_out* O, void* ws, hipStream_t s) {
+  return acct_fill(T, tab_ws, U, O, ws, s, true);
 }
 
 }  // extern "C"

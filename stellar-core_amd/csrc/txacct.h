@@ -47,7 +47,14 @@
 struct sv_acct_tab {       // the account table
   const uint8_t* key;      // na x 32
   const uint8_t* thr;      // na x 4: master weight, low, med, high
-  const uint64_t* sbeg;    // na + 1
+  union {
+    const uint64_t* sbeg;  // na + 1
+    // The kStride instantiations (an account store's replica: acctstore.h, sv_txstore.hip) read this word as scnt:
+    // rows of a fixed stride of SV_ACCT_STRIDE signers, account a's signers at SV_ACCT_STRIDE * a, scnt[a] of
+    // them.  The caller picks the instantiation (sv_launch_acct_fill_stride); the struct, and with it the CSR
+    // kernels' arguments and code, are what they were without the store.
+    const uint32_t* scnt;  // na
+  };
   const uint8_t* stype;    // ns
   const uint32_t* sweight; // ns
   const uint8_t* skey;     // ns x 32
@@ -56,6 +63,7 @@ struct sv_acct_tab {       // the account table
   const uint8_t* plen;     // np
   uint64_t na, ns, np;
 };
+#define SV_ACCT_STRIDE 20  // MAX_SIGNERS of an account entry
 
 struct sv_acct_use {       // who refers to it
   const uint64_t* ebeg;    // nb + 1: body t's account entries (bacct_begin)
@@ -101,18 +109,25 @@ SV_HD void sv_acct_zero(uint8_t* d, int n16) {
 }
 
 // account a's signers [*s0, *s1) and whether its master key is a signer
+template <bool kStride = false>
 SV_HD uint32_t sv_acct_signers(const sv_acct_tab& T, uint64_t a, uint64_t* s0, uint64_t* s1) {
-  *s1 = sv_acct_min(T.sbeg[a + 1], T.ns);
-  *s0 = sv_acct_min(T.sbeg[a], *s1);
+  if (kStride) {
+    *s0 = SV_ACCT_STRIDE * a;
+    *s1 = *s0 + sv_acct_min(T.scnt[a], SV_ACCT_STRIDE);
+  } else {
+    *s1 = sv_acct_min(T.sbeg[a + 1], T.ns);
+    *s0 = sv_acct_min(T.sbeg[a], *s1);
+  }
   return T.thr[4 * a] != 0 ? 1u : 0u;
 }
 
 // Once per account: acnt[2a] the rows it adds to a key list, acnt[2a + 1] to
 // the payload candidates (their sum: the signers of a check on it), and every
 // signer's rank.
+template <bool kStride = false>
 SV_HD void sv_acct_count(const sv_acct_tab& T, uint64_t a, uint32_t* acnt, uint32_t* rank) {
   uint64_t s0, s1;
-  uint32_t nk = sv_acct_signers(T, a, &s0, &s1), nq = 0;
+  uint32_t nk = sv_acct_signers<kStride>(T, a, &s0, &s1), nq = 0;
   SV_NOUNROLL for (uint64_t s = s0; s < s1; ++s) rank[s] = T.stype[s] == 3 ? nq++ : nk++;
   acnt[2 * a] = nk;
   acnt[2 * a + 1] = nq;
@@ -165,10 +180,11 @@ SV_HD uint32_t sv_acct_check_count(const sv_acct_tab& T, const sv_acct_use& U, c
 // Item j of account a (its master key, if a signer, is item 0, then its
 // signers) as a row of a body's key list or payload candidates; krow / qrow:
 // the account's first row in either.
+template <bool kStride = false>
 SV_HD void sv_acct_fill_row(const sv_acct_tab& T, const uint32_t* rank, uint64_t a, uint64_t j, uint64_t krow,
                             uint64_t qrow, const sv_acct_out& O) {
   uint64_t s0, s1;
-  const uint32_t hm = sv_acct_signers(T, a, &s0, &s1);
+  const uint32_t hm = sv_acct_signers<kStride>(T, a, &s0, &s1);
   if (j < hm) {
     if (krow < O.nk) sv_acct_copy(O.key + 32 * krow, T.key + 32 * a, 2);
     return;
@@ -194,11 +210,12 @@ SV_HD void sv_acct_fill_row(const sv_acct_tab& T, const uint32_t* rank, uint64_t
 }
 
 // ... and as signer g of a check on that account.
+template <bool kStride = false>
 SV_HD void sv_acct_fill_signer(const sv_acct_tab& T, const uint32_t* rank, uint64_t a, uint64_t j, uint64_t krow,
                                uint64_t qrow, uint64_t g, const sv_acct_out& O) {
   if (g >= O.ng) return;
   uint64_t s0, s1;
-  const uint32_t hm = sv_acct_signers(T, a, &s0, &s1);
+  const uint32_t hm = sv_acct_signers<kStride>(T, a, &s0, &s1);
   if (j < hm) {
     O.gtype[g] = 0;
     O.gweight[g] = T.thr[4 * a];

@@ -308,17 +308,23 @@ def main():
     ap.add_argument("--root", default=REPO, help="the tree whose stellar-core_amd package is imported")
     ap.add_argument("--out", default="", help="where the JSON line is also written")
     a = ap.parse_args()
-    for d in (os.path.join(REPO, "tests"), os.path.join(REPO, "tools"), os.path.abspath(a.root)):
+    for d in (os.path.join(REPO, "tests"), os.path.join(REPO, "tools")):
         sys.path.insert(0, d)
     import torch
     import txchecks_bench as cb
     import txpairs_bench as tb
+    # --root goes in LAST: the helper modules above put this tree's root at the front of sys.path as they load
+    root = os.path.abspath(a.root)
+    sys.path.insert(0, root)
     sv = importlib.import_module("stellar-core_amd")
+    assert os.path.dirname(os.path.dirname(os.path.abspath(sv.__file__))) == root, (sv.__file__, root)
     dev = torch.device("cuda", 0)
     stream = torch.cuda.current_stream(dev).cuda_stream
     reps = max(5, a.reps)
     res = {"tool": "tools/txaccounts_bench.py", "reps": reps, "explicit_only": bool(a.explicit_only),
-           "kernel_source_digest": sv.kernel_source_digest()}
+           "kernel_source_digest": sv.kernel_source_digest(),
+           "package": os.path.relpath(os.path.abspath(sv.__file__), REPO),
+           "library": os.path.relpath(sv.LIB_PATH, REPO)}
     single = cb.add_checks(tb.build(sv, dev, stream, a.n, np.ones(a.n, np.int64), 20), np.ones(a.n, np.int64),
                            np.random.default_rng(23))
     res["single"] = run(sv, tb, dev, stream, by_account_one_per_body(single), reps, a.explicit_only)
