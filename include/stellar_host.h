@@ -94,6 +94,20 @@ int svh_verify_sig_batch(const uint8_t* pk, const uint8_t* sig /* n x 64 */, con
  * any call did not return 1 (the cases must be valid). */
 int svh_bench_verify_hits(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, size_t msg_len, size_t n,
                           int passes, int threads, double* hits_per_s, double* fill_s);
+/* Batch signing through the mirror (SecretKey::signBatchRaw -> sv_ed25519_sign_batch, on an engine error
+ * sv_ed25519_sign_batch_cpu: a fallback is counted, never a wrong signature): variable-length messages, arguments
+ * as sv_ed25519_sign_batch (key_of NULL: k == n).  svh_sign: SecretKey::fromSeed(seed).sign(msg) on the CPU path,
+ * pk optional.  svh_sign_fallbacks: engine errors re-run on the CPU path since the last call (flushes).  These
+ * return SVH_ERR_INVALID_ARG for a malformed batch and do not set svh_last_error_string. */
+int svh_sign_batch(const uint8_t* seed, size_t k, const uint32_t* key_of, const uint8_t* msg, const uint64_t* msg_off,
+                   const uint32_t* msg_len, size_t n, uint8_t* sig /* n x 64 */, uint8_t* pk /* optional, k x 32 */);
+int svh_sign(const uint8_t seed[32], const uint8_t* msg, size_t msg_len, uint8_t sig[64], uint8_t pk[32]);
+uint64_t svh_sign_fallbacks(void);
+/* Sign benchmark, the sign half of SecretKey::benchmarkOpsPerSecond's shape (SecretKey.cpp:193-212: n_keys cases
+ * of one key and one msg_len-byte message, `iterations` passes): batched == 0 signs one at a time with
+ * SecretKey::sign (the CPU path), batched != 0 signs each pass with one SecretKey::signBatch call (the engine).
+ * *signs_per_s = signatures / wall seconds. */
+int svh_bench_sign(size_t n_keys, size_t msg_len, int iterations, int batched, double* signs_per_s);
 void svh_cache_clear(void);
 void svh_cache_seed(unsigned int seed);
 void svh_cache_counts(uint64_t* hits, uint64_t* misses); /* flushes, like flushVerifySigCacheCounts */

@@ -203,6 +203,78 @@ int sv_ed25519_verify_device(int device, const void* d_pk, const void* d_sig, co
 int sv_ed25519_sign_device(int device, const void* d_seed, const void* d_msg32, size_t n, void* d_pk,
                            void* d_sig, void* stream);
 
+/* ---- Batch signing (src/crypto/SecretKey.cpp:134-146, 286, 309) ----------
+ * sig[i] = crypto_sign_detached(message i, sk(seed[key_of[i]])) and
+ * pk[j] = crypto_sign_seed_keypair(seed[j]).pk, byte for byte (RFC 8032
+ * signing is deterministic), for messages of any length and with keys shared
+ * between messages: every key is expanded once per call, not once per
+ * signature.  key_of == NULL means k == n and key i signs message i.
+ * fixed_msg_len != 0: message i = msg[i*fixed_msg_len ..); 0: msg_off/msg_len
+ * as in sv_ed25519_verify_batch.  n == 0 with k > 0 yields only the public
+ * keys; k == 0 with n == 0 does nothing.  pk is optional (NULL: not written).
+ *
+ * What this signer is for: load generation, test networks, benchmarks and
+ * dataset building -- the bulk signing of src/simulation/TxGenerator.cpp.  It
+ * is NOT constant-time: table addresses follow the secret scalars' digits.
+ * In the host and device forms the seeds cross PCIe and they and the expanded
+ * keys sit in HBM for the length of the call (the engine's copies are cleared
+ * before it returns, on the call's stream in the device form).  A validator's
+ * NODE_SEED signing of single messages stays where it is, in libsodium.
+ *
+ * Host and CPU forms return SV_ERR_INVALID_ARG before any work, with no
+ * output byte written, for: a null required pointer; key_of == NULL with
+ * k != n (n > 0); a key_of[i] >= k; k or n >= 2^32.
+ *
+ * Host form: stages through one slot in pieces of at most SV_STAGE_CHUNK
+ * signatures (and 256 MiB of message bytes); copy and compute do not overlap.  Signing calls are not
+ * sharded: opts->device == -1 is served by one slot (round-robin).
+ *
+ * Device form: stream semantics as sv_ed25519_verify_device.  d_seed, d_sig
+ * and d_pk must be 16-byte aligned (SV_ERR_ALIGN).  The device arrays are not
+ * validated: a d_key_of[i] >= k writes 64 zero bytes for row i, and nothing
+ * is written outside d_sig (n x 64) and d_pk (k x 32).
+ */
+int sv_ed25519_sign_batch(const uint8_t* seed /* k x 32 */, size_t k,
+                          const uint32_t* key_of /* n; NULL: k == n, key i signs message i */, const uint8_t* msg,
+                          const uint64_t* msg_off, const uint32_t* msg_len, uint32_t fixed_msg_len, size_t n,
+                          uint8_t* sig /* n x 64 */, uint8_t* pk /* optional, k x 32 */, const sv_opts* opts);
+int sv_ed25519_sign_batch_device(int device, const void* d_seed, size_t k, const uint32_t* d_key_of,
+                                 const void* d_msg, const uint64_t* d_msg_off, const uint32_t* d_msg_len,
+                                 uint32_t fixed_msg_len, size_t n, void* d_sig, void* d_pk /* optional */,
+                                 void* stream);
+/* The same contract on the engine's CPU path (csrc/sign_core.h compiled for
+ * the host; threads as sv_ed25519_verify_batch_cpu). */
+int sv_ed25519_sign_batch_cpu(const uint8_t* seed, size_t k, const uint32_t* key_of, const uint8_t* msg,
+                              const uint64_t* msg_off, const uint32_t* msg_len, uint32_t fixed_msg_len, size_t n,
+                              uint8_t* sig, uint8_t* pk, int threads);
+
+/*
+ * Signing over transaction bodies: what SignatureUtils::sign
+ * (src/transactions/SignatureUtils.cpp:19-27) produces per (transaction, key).
+ * Bodies, kinds and sig_begin as in sv_ed25519_verify_txbodies; signature s of
+ * body t (sig_begin[t] <= s < sig_begin[t+1], n = sig_begin[n_bodies]) is made
+ * with seed[key_of[s]] over the body's contents hash.  Outputs: hint (n x 4,
+ * bytes 28..31 of the signer's public key) and sig (n x 64), which with
+ * sig_begin are exactly the inputs of sv_ed25519_verify_txbodies_hinted*;
+ * pk (k x 32) and digests (n_bodies x 32) are optional.  key_of is required.
+ * Refusals, staging, alignment (d_hint: 4 bytes) and the notes above apply;
+ * in the device form a d_key_of[s] >= k also writes a zero hint.
+ */
+int sv_ed25519_sign_txbodies(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                             const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                             const uint64_t* sig_begin, const uint8_t* seed, size_t k, const uint32_t* key_of,
+                             size_t n, uint8_t* hint, uint8_t* sig, uint8_t* pk, uint8_t* digests,
+                             const sv_opts* opts);
+int sv_ed25519_sign_txbodies_device(int device, const uint8_t* network_id /* host, 32 B */, const void* d_bodies,
+                                    const uint64_t* d_body_off, const uint32_t* d_body_len,
+                                    const uint8_t* d_body_kind, size_t n_bodies, const uint64_t* d_sig_begin,
+                                    const void* d_seed, size_t k, const uint32_t* d_key_of, size_t n, void* d_hint,
+                                    void* d_sig, void* d_pk, void* d_digests, void* stream);
+int sv_ed25519_sign_txbodies_cpu(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                 const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                 const uint64_t* sig_begin, const uint8_t* seed, size_t k, const uint32_t* key_of,
+                                 size_t n, uint8_t* hint, uint8_t* sig, uint8_t* pk, uint8_t* digests, int threads);
+
 /* ---- Batch hashing on the device ----------------------
  * Verify-cache keys: keys[32*i..] = BLAKE2b-256(pk_i || sig_i || msg_i), the key
  * PubKeyUtils::verifySig computes per call before consulting the cache

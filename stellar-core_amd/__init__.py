@@ -87,6 +87,8 @@ EXPORTED_SYMBOLS = (
     "sv_ed25519_check_txbodies_ledger", "sv_ed25519_decide_txbodies_ledger",
     "sv_ed25519_check_txbodies_ledger_device", "sv_ed25519_check_txbodies_ledger_cpu",
     "sv_ed25519_decide_txbodies_ledger_device", "sv_ed25519_decide_txbodies_ledger_cpu",
+    "sv_ed25519_sign_batch", "sv_ed25519_sign_batch_device", "sv_ed25519_sign_batch_cpu",
+    "sv_ed25519_sign_txbodies", "sv_ed25519_sign_txbodies_device", "sv_ed25519_sign_txbodies_cpu",
 )
 
 # a bacct entry of the ledger forms that names a store account by its ID (include/stellar_sigverify.h)
@@ -224,6 +226,15 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.sv_ed25519_verify_batch_fixed.argtypes = [vp, vp, vp, ctypes.c_uint32, sz, vp, vp]
     lib.sv_ed25519_verify_device.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_uint32, sz, vp, vp, vp]
     lib.sv_ed25519_sign_device.argtypes = [ctypes.c_int, vp, vp, sz, vp, vp, vp]
+    u32 = ctypes.c_uint32
+    lib.sv_ed25519_sign_batch.argtypes = [vp, sz, vp, vp, vp, vp, u32, sz, vp, vp, vp]
+    lib.sv_ed25519_sign_batch_device.argtypes = [ctypes.c_int, vp, sz, vp, vp, vp, vp, u32, sz, vp, vp, vp]
+    lib.sv_ed25519_sign_batch_cpu.argtypes = [vp, sz, vp, vp, vp, vp, u32, sz, vp, vp, ctypes.c_int]
+    lib.sv_ed25519_sign_txbodies.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp]
+    lib.sv_ed25519_sign_txbodies_device.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, vp,
+                                                    vp, vp, vp]
+    lib.sv_ed25519_sign_txbodies_cpu.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp,
+                                                 ctypes.c_int]
     lib.sv_timing_enable.argtypes = [ctypes.c_int]
     lib.sv_kernel_time.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                    ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
@@ -459,6 +470,123 @@ def verify_device(device: int, d_pk: int, d_sig: int, d_msg: int, n: int, d_verd
 def sign_device(device: int, d_seed: int, d_msg32: int, n: int, d_pk: int, d_sig: int, stream: int = 0) -> None:
     lib = load_library()
     _check(lib.sv_ed25519_sign_device(device, d_seed, d_msg32, n, d_pk, d_sig, stream or None))
+
+
+def _sign_args(seed, msg, msg_off, msg_len, key_of, fixed_msg_len):
+    seed = _u8(seed, 32)
+    k = seed.shape[0]
+    if key_of is None:
+        n, ko = k, None
+    else:
+        ko = np.ascontiguousarray(np.asarray(key_of, dtype=np.uint32).reshape(-1))
+        n = ko.shape[0]
+    if fixed_msg_len:
+        msg = np.ascontiguousarray(np.asarray(msg, dtype=np.uint8).reshape(-1))
+        if msg.size != n * fixed_msg_len:
+            raise ValueError("msg must hold n * fixed_msg_len bytes")
+        if msg.size == 0:
+            msg = np.zeros(1, np.uint8)
+        off = ln = None
+    else:
+        msg, off, ln = _var_msgs(msg, msg_off, msg_len, n)
+    return seed, k, ko, msg, off, ln, n
+
+
+def _optr(a):
+    return None if a is None else _ptr(a)
+
+
+def sign_batch(seed, msg, msg_off=None, msg_len=None, key_of=None, fixed_msg_len: int = 0, device: int = -1):
+    """Batch ed25519 signing on the GPU (sv_ed25519_sign_batch): seed is k x 32,
+    message i (msg[msg_off[i]:msg_off[i]+msg_len[i]], or row i of n x fixed_msg_len
+    bytes) is signed with seed[key_of[i]] (key_of None: k == n, key i signs
+    message i).  Returns (sig n x 64, pk k x 32), byte-equal to libsodium's
+    crypto_sign_detached / crypto_sign_seed_keypair.  Not constant-time: for load
+    generation, test networks, benchmarks and datasets."""
+    lib = load_library()
+    seed, k, ko, msg, off, ln, n = _sign_args(seed, msg, msg_off, msg_len, key_of, fixed_msg_len)
+    sig = np.zeros((n, 64), np.uint8)
+    pk = np.zeros((k, 32), np.uint8)
+    _check(lib.sv_ed25519_sign_batch(_ptr(seed), k, _optr(ko), _ptr(msg), _optr(off), _optr(ln), fixed_msg_len, n,
+                                     _ptr(sig), _ptr(pk), _opts(device)))
+    return sig, pk
+
+
+def sign_batch_cpu(seed, msg, msg_off=None, msg_len=None, key_of=None, fixed_msg_len: int = 0, threads: int = 0):
+    """The same on the engine's CPU path (what a caller runs on an engine error)."""
+    lib = load_library()
+    seed, k, ko, msg, off, ln, n = _sign_args(seed, msg, msg_off, msg_len, key_of, fixed_msg_len)
+    sig = np.zeros((n, 64), np.uint8)
+    pk = np.zeros((k, 32), np.uint8)
+    _check(lib.sv_ed25519_sign_batch_cpu(_ptr(seed), k, _optr(ko), _ptr(msg), _optr(off), _optr(ln), fixed_msg_len, n,
+                                         _ptr(sig), _ptr(pk), int(threads)))
+    return sig, pk
+
+
+def sign_batch_device(device: int, d_seed: int, k: int, d_msg: int, n: int, d_sig: int, d_pk: int = 0,
+                      d_key_of: int = 0, fixed_msg_len: int = 32, d_msg_off: int = 0, d_msg_len: int = 0,
+                      stream: int = 0) -> None:
+    """Device-resident form (raw device pointers; seed / sig / pk 16-byte aligned)."""
+    lib = load_library()
+    _check(lib.sv_ed25519_sign_batch_device(device, d_seed or None, k, d_key_of or None, d_msg or None,
+                                            d_msg_off or None, d_msg_len or None, fixed_msg_len, n, d_sig or None,
+                                            d_pk or None, stream or None))
+
+
+def _sign_tx_args(network_id, bodies, body_off, body_len, body_kind, sig_begin, seed, key_of):
+    nid = np.ascontiguousarray(np.frombuffer(bytes(network_id), np.uint8))
+    if nid.size != 32:
+        raise ValueError("network_id must be 32 bytes")
+    kind = np.ascontiguousarray(np.asarray(body_kind, dtype=np.uint8).reshape(-1))
+    nb = kind.shape[0]
+    bodies, off, ln = _var_msgs(bodies, body_off, body_len, nb)
+    sb = _csr(sig_begin, nb, "sig_begin")
+    seed = _u8(seed, 32)
+    ko = np.ascontiguousarray(np.asarray(key_of, dtype=np.uint32).reshape(-1))
+    return nid, bodies, off, ln, kind, nb, sb, seed, seed.shape[0], ko, ko.shape[0]
+
+
+def _sign_tx_host(fn, last, network_id, bodies, body_off, body_len, body_kind, sig_begin, seed, key_of):
+    nid, bodies, off, ln, kind, nb, sb, seed, k, ko, n = _sign_tx_args(network_id, bodies, body_off, body_len,
+                                                                      body_kind, sig_begin, seed, key_of)
+    hint = np.zeros((n, 4), np.uint8)
+    sig = np.zeros((n, 64), np.uint8)
+    pk = np.zeros((k, 32), np.uint8)
+    dig = np.zeros((nb, 32), np.uint8)
+    kp = np.zeros(max(n, 1), np.uint32)
+    kp[:n] = ko
+    _check(fn(_ptr(nid), _ptr(bodies), _ptr(off), _ptr(ln), _ptr(kind), nb, _ptr(sb), _ptr(seed), k, _ptr(kp), n,
+              _ptr(hint), _ptr(sig), _ptr(pk), _ptr(dig), last))
+    return hint, sig, pk, dig
+
+
+def sign_txbodies(network_id, bodies, body_off, body_len, body_kind, sig_begin, seed, key_of, device: int = -1):
+    """What SignatureUtils::sign produces per (transaction, key), on the GPU
+    (sv_ed25519_sign_txbodies): signature s of body t is made with seed[key_of[s]]
+    over the body's contents hash.  Returns (hint n x 4, sig n x 64, pk k x 32,
+    digests n_bodies x 32); sig_begin, hint and sig feed verify_txbodies_hinted."""
+    return _sign_tx_host(load_library().sv_ed25519_sign_txbodies, _opts(device), network_id, bodies, body_off,
+                         body_len, body_kind, sig_begin, seed, key_of)
+
+
+def sign_txbodies_cpu(network_id, bodies, body_off, body_len, body_kind, sig_begin, seed, key_of, threads: int = 0):
+    """The same on the engine's CPU path."""
+    return _sign_tx_host(load_library().sv_ed25519_sign_txbodies_cpu, int(threads), network_id, bodies, body_off,
+                         body_len, body_kind, sig_begin, seed, key_of)
+
+
+def sign_txbodies_device(device: int, network_id, d_bodies: int, d_body_off: int, d_body_len: int, d_body_kind: int,
+                         n_bodies: int, d_sig_begin: int, d_seed: int, k: int, d_key_of: int, n: int, d_hint: int,
+                         d_sig: int, d_pk: int = 0, d_digests: int = 0, stream: int = 0) -> None:
+    """Device-resident form (raw device pointers; network_id is 32 host bytes)."""
+    lib = load_library()
+    nid = np.ascontiguousarray(np.frombuffer(bytes(network_id), np.uint8))
+    if nid.size != 32:
+        raise ValueError("network_id must be 32 bytes")
+    _check(lib.sv_ed25519_sign_txbodies_device(device, _ptr(nid), d_bodies or None, d_body_off or None,
+                                               d_body_len or None, d_body_kind or None, n_bodies, d_sig_begin or None,
+                                               d_seed or None, k, d_key_of or None, n, d_hint or None, d_sig or None,
+                                               d_pk or None, d_digests or None, stream or None))
 
 
 def verify_batch_cpu(pk, sig, msg, msg_off, msg_len, threads: int = 0) -> np.ndarray:

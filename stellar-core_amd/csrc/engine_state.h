@@ -362,6 +362,11 @@ struct Device {
   // ranks), and the device-resident form's expansion -- workspace and CSR arrays, then the rows sized from its totals
   DevBuf txatab, txaws, txarows;
   DevBuf txres;  // device-resident decide calls: the check arrays the caller did not ask for, the result kernels' workspace
+  // signing calls (sv_sign.hip): the slot's own comb tables of B, built at its first signing call (the latency
+  // lane keeps its copy, so the lane's start-up and first batch are what they were); the expanded-key records,
+  // cleared behind every call's last kernel; the host form's seeds, chunk inputs and outputs
+  void* sign_ctab = nullptr;
+  DevBuf sign_rec, sign_seed, sign_in, sign_out;
   KernelTimer timer;  // the bulk launches (launch_locked)
   LatLane lat;
   KeyTabs kt;  // (under mu)
@@ -518,6 +523,9 @@ inline void release_device(Device& D) {
   D.txmsg.release();
   D.txpk.release(); D.txsg.release(); D.txpair.release(); D.h_txcnt.release(); D.txchk.release(); D.txpp.release();
   D.txatab.release(); D.txaws.release(); D.txarows.release(); D.txres.release();
+  D.sign_rec.release(); D.sign_seed.release(); D.sign_in.release(); D.sign_out.release();
+  if (D.sign_ctab) (void)hipFree(D.sign_ctab);
+  D.sign_ctab = nullptr;
   D.ws.release();
   D.kt.index.release(); D.kt.store.release(); D.kt.kslot.release(); D.kt.builders.release();
   D.kt.count.release(); D.kt.h_count.release();

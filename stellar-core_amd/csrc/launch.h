@@ -1,6 +1,6 @@
 // The one declaration of every extern "C" launcher and size query that
 // crosses between the kernel files (sv_kernels.hip, sv_comb.hip, sv_hash.hip,
-// sv_txhash.hip, sv_txpair.hip, sv_txcheck.hip, sv_txacct.hip, sv_txresult.hip, sv_vcache.hip), sv_cpu.cpp and the engine (sv_api.cpp and its modules).
+// sv_txhash.hip, sv_txpair.hip, sv_txcheck.hip, sv_txacct.hip, sv_txresult.hip, sv_vcache.hip, sv_sign.hip), sv_cpu.cpp and the engine (sv_api.cpp and its modules).
 // Included by the callers and by every definer, so a changed parameter list
 // is a compile error instead of arguments corrupted at run time.
 #pragma once
@@ -63,6 +63,16 @@ void sv_txresults_bad_list(const struct sv_txresults* res, size_t n_bodies);
 void sv_txresults_fold(const struct sv_txresults* res, const uint64_t* check_begin, const uint64_t* sig_begin,
                        const uint8_t* check_ok, const uint64_t* check_used, size_t n_bodies, size_t n_checks,
                        size_t n_sigs);
+
+// Argument checks of the signing entry points (sv_cpu.cpp): the host and CPU forms of sv_ed25519_sign_batch
+// (null pointers, key_of == NULL with k != n, a key_of[i] >= k, k or n >= 2^32) and of sv_ed25519_sign_txbodies
+// (the bodies and sig_begin as in sv_txbodies_check, then the keys).
+int sv_sign_check(const uint8_t* seed, size_t k, const uint32_t* key_of, const uint8_t* msg, const uint64_t* msg_off,
+                  const uint32_t* msg_len, uint32_t fixed_len, size_t n, const uint8_t* sig);
+int sv_sign_txbodies_check(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                           const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                           const uint64_t* sig_begin, const uint8_t* seed, size_t k, const uint32_t* key_of, size_t n,
+                           const uint8_t* hint, const uint8_t* sig);
 
 }  // extern "C"
 
@@ -215,6 +225,16 @@ hipError_t sv_launch_vc_bitmap(const void* verdict, uint64_t n, void* bitmap, hi
 struct sv_vc_feed_args;
 hipError_t sv_launch_vc_feed(const struct sv_vc_feed_args* A, hipStream_t s);
 hipError_t sv_launch_vc_lookup(const void* tab, uint64_t sets, const void* keys, uint64_t n, void* out, hipStream_t s);
+// batch signing (sv_sign.hip, sign_core.h): the keys kernel writes k expanded-key records (sv_sign_rec_bytes(k),
+// 16-byte aligned) and, with pk, the public keys; the messages kernel signs n messages, message i with record
+// key_of[i] (nullptr: i), 64 zero bytes where key_of[i] >= k; hint (optional): bytes 28..31 of each signer's key.
+// ctab: the comb tables of B (sv_launch_comb_btab).  seed / pk / sig 16-byte aligned.
+size_t sv_sign_rec_bytes(uint64_t k);
+hipError_t sv_launch_sign_keys(const void* seed, uint32_t k, void* rec, void* pk, const uint32_t* ctab,
+                               hipStream_t s);
+hipError_t sv_launch_sign_msgs(const void* rec, uint32_t k, const uint32_t* key_of, const void* msg,
+                               const uint64_t* off, const uint32_t* len, uint32_t fixed_len, uint32_t n, void* sig,
+                               void* hint, const uint32_t* ctab, hipStream_t s);
 // warm-key latency path (sv_comb.hip)
 size_t sv_comb_btab_bytes(void);
 size_t sv_key_slot_bytes(void);

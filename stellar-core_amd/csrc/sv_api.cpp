@@ -2028,6 +2028,301 @@ int sv_ed25519_sign_device(int device, const void* d_seed, const void* d_msg32, 
       });
 }
 
+}  // extern "C"
+
+// ------------------------------------------------------------------ signing
+namespace {
+
+// Message bytes a host signing chunk stages at most (one message always fits).
+constexpr size_t kSignChunkBytes = (size_t)256 << 20;
+
+// The slot's comb tables of B, built on D.stream at its first signing call (caller holds D.mu, device set).
+int sign_ready(Device& D) {
+  if (D.sign_ctab) return SV_OK;
+  SV_HIP(hipMalloc(&D.sign_ctab, sv_comb_btab_bytes()));
+  const hipError_t e = sv_launch_comb_btab((uint32_t*)D.sign_ctab, D.stream);
+  if (e != hipSuccess) {
+    (void)hipFree(D.sign_ctab);
+    D.sign_ctab = nullptr;
+    return hip_fail(e, "sv_launch_comb_btab");
+  }
+  return SV_OK;
+}
+// A signing buffer of `bytes` (growing frees the old one, so D.stream is drained first).
+int sign_buf(Device& D, DevBuf& b, size_t bytes) {
+  if (bytes <= b.cap) return SV_OK;
+  SV_HIP(hipStreamSynchronize(D.stream));
+  return b.ensure(bytes);
+}
+inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// Keys, messages, then the clear of the records, all on D.stream (device-resident arrays).
+int sign_launch(Device& D, const void* d_seed, size_t k, const uint32_t* d_key_of, const void* d_msg,
+                const uint64_t* d_off, const uint32_t* d_len, uint32_t fixed_len, size_t n, void* d_sig, void* d_pk,
+                void* d_hint) {
+  const uint32_t* ctab = (const uint32_t*)D.sign_ctab;
+  SV_HIP(sv_launch_sign_keys(d_seed, (uint32_t)k, D.sign_rec.p, d_pk, ctab, D.stream));
+  const hipError_t e = sv_launch_sign_msgs(D.sign_rec.p, (uint32_t)k, d_key_of, d_msg, d_off, d_len, fixed_len,
+                                           (uint32_t)n, d_sig, d_hint, ctab, D.stream);
+  if (k) SV_HIP(hipMemsetAsync(D.sign_rec.p, 0, sv_sign_rec_bytes(k), D.stream));
+  if (e != hipSuccess) return hip_fail(e, "sv_launch_sign_msgs");
+  return SV_OK;
+}
+
+// The host form on slot D (caller holds D.mu, device set, slot ready; arguments checked, k > 0): the seeds up, the
+// keys kernel, the seeds cleared; then per piece its key_of / message arrays up, the messages kernel, its
+// signatures down.  pk_out: k x 32 host bytes or nullptr.
+int sign_host_run(Device& D, const uint8_t* seed, size_t k, const uint32_t* key_of, const uint8_t* msg,
+                  const uint64_t* msg_off, const uint32_t* msg_len, uint32_t fixed_len, size_t n, uint8_t* sig,
+                  uint8_t* pk_out) {
+  int rc;
+  const uint32_t* ctab = (const uint32_t*)D.sign_ctab;
+  hipStream_t st = D.stream;
+  SV_HIP(hipMemcpyAsync(D.sign_seed.p, seed, 32 * k, hipMemcpyHostToDevice, st));
+  SV_HIP(sv_launch_sign_keys(D.sign_seed.p, (uint32_t)k, D.sign_rec.p, pk_out ? D.sign_out.p : nullptr, ctab, st));
+  SV_HIP(hipMemsetAsync(D.sign_seed.p, 0, 32 * k, st));
+  if (pk_out) SV_HIP(hipMemcpyAsync(pk_out, D.sign_out.p, 32 * k, hipMemcpyDeviceToHost, st));
+  SV_HIP(hipStreamSynchronize(st));
+  const size_t chunk = stage_chunk();
+  std::vector<uint8_t> pack;
+  std::vector<uint64_t> offs;
+  for (size_t lo = 0; lo < n;) {
+    size_t hi = std::min(n, lo + chunk);
+    size_t bytes = 0;
+    if (fixed_len) {
+      const size_t fit = std::max<size_t>(1, kSignChunkBytes / fixed_len);
+      hi = std::min(hi, lo + fit);
+      bytes = (hi - lo) * (size_t)fixed_len;
+    } else {
+      size_t i = lo;
+      for (; i < hi && (i == lo || bytes + msg_len[i] <= kSignChunkBytes); ++i) bytes += msg_len[i];
+      hi = i;
+    }
+    const size_t m = hi - lo;
+    // the piece's image: key_of | off | len | message bytes
+    const size_t o_key = 0, o_off = up16(4 * m), o_len = o_off + up16(8 * m), o_msg = o_len + up16(4 * m);
+    if ((rc = sign_buf(D, D.sign_in, o_msg + bytes + 16))) return rc;
+    if ((rc = sign_buf(D, D.sign_out, std::max(32 * k, 64 * m)))) return rc;
+    uint8_t* in = (uint8_t*)D.sign_in.p;
+    if (key_of) SV_HIP(hipMemcpyAsync(in + o_key, key_of + lo, 4 * m, hipMemcpyHostToDevice, st));
+    if (fixed_len) {
+      SV_HIP(hipMemcpyAsync(in + o_msg, msg + lo * (size_t)fixed_len, bytes, hipMemcpyHostToDevice, st));
+    } else {
+      pack.resize(bytes);
+      offs.resize(m);
+      size_t at = 0;
+      for (size_t i = 0; i < m; ++i) {
+        offs[i] = at;
+        if (msg_len[lo + i]) std::memcpy(pack.data() + at, msg + msg_off[lo + i], msg_len[lo + i]);
+        at += msg_len[lo + i];
+      }
+      SV_HIP(hipMemcpyAsync(in + o_off, offs.data(), 8 * m, hipMemcpyHostToDevice, st));
+      SV_HIP(hipMemcpyAsync(in + o_len, msg_len + lo, 4 * m, hipMemcpyHostToDevice, st));
+      if (bytes) SV_HIP(hipMemcpyAsync(in + o_msg, pack.data(), bytes, hipMemcpyHostToDevice, st));
+    }
+    // (key_of == NULL: key i signs message i, so the piece's records start at lo)
+    const uint8_t* rec = (const uint8_t*)D.sign_rec.p + (key_of ? 0 : sv_sign_rec_bytes(lo));
+    SV_HIP(sv_launch_sign_msgs(rec, (uint32_t)(key_of ? k : m), key_of ? (const uint32_t*)(in + o_key) : nullptr,
+                               in + o_msg, fixed_len ? nullptr : (const uint64_t*)(in + o_off),
+                               fixed_len ? nullptr : (const uint32_t*)(in + o_len), fixed_len, (uint32_t)m,
+                               D.sign_out.p, nullptr, ctab, st));
+    SV_HIP(hipMemcpyAsync(sig + 64 * lo, D.sign_out.p, 64 * m, hipMemcpyDeviceToHost, st));
+    SV_HIP(hipStreamSynchronize(st));
+    lo = hi;
+  }
+  return SV_OK;
+}
+
+// sign_host_run inside its bracket: buffers first, and whatever happens the device copies of the seeds and of the
+// expanded keys are cleared before the call returns.
+int sign_host(Device& D, const uint8_t* seed, size_t k, const uint32_t* key_of, const uint8_t* msg,
+              const uint64_t* msg_off, const uint32_t* msg_len, uint32_t fixed_len, size_t n, uint8_t* sig,
+              uint8_t* pk_out) {
+  std::lock_guard<std::mutex> g(D.mu);
+  SV_HIP(hipSetDevice(D.phys));
+  int rc;
+  if ((rc = ready_locked(D))) return rc;
+  if ((rc = sign_ready(D))) return rc;
+  if ((rc = sign_buf(D, D.sign_seed, 32 * k))) return rc;
+  if ((rc = sign_buf(D, D.sign_rec, sv_sign_rec_bytes(k)))) return rc;
+  if ((rc = sign_buf(D, D.sign_out, 32 * k))) return rc;
+  rc = sign_host_run(D, seed, k, key_of, msg, msg_off, msg_len, fixed_len, n, sig, pk_out);
+  hipError_t e = hipMemsetAsync(D.sign_seed.p, 0, 32 * k, D.stream);
+  if (e == hipSuccess) e = hipMemsetAsync(D.sign_rec.p, 0, sv_sign_rec_bytes(k), D.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(D.stream);
+  if (rc) return rc;
+  if (e != hipSuccess) return hip_fail(e, "clearing the signing keys");
+  return SV_OK;
+}
+
+// The one slot a host signing call runs on (signing is not sharded).
+int sign_slot(const sv_opts* opts, Device*& D) {
+  int rc;
+  if ((rc = ensure_init())) return rc;
+  std::vector<Device*> devs;
+  if ((rc = select_devices(opts, 0, devs))) return rc;
+  D = devs[0];
+  return SV_OK;
+}
+
+// Contents hashes of host bodies on slot D, in pieces of at most SV_STAGE_CHUNK bodies (sv_txhash.hip).
+int sign_txdigests(Device& D, const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                   const uint32_t* body_len, const uint8_t* body_kind, size_t nb, uint8_t* digests) {
+  std::lock_guard<std::mutex> g(D.mu);
+  SV_HIP(hipSetDevice(D.phys));
+  int rc;
+  if ((rc = ready_locked(D))) return rc;
+  const size_t chunk = stage_chunk();
+  std::vector<uint8_t> pack;
+  std::vector<uint64_t> offs;
+  for (size_t lo = 0; lo < nb;) {
+    size_t hi = lo, bytes = 0;
+    for (; hi < std::min(nb, lo + chunk) && (hi == lo || bytes + up16(body_len[hi]) <= kSignChunkBytes); ++hi)
+      bytes += up16(body_len[hi]);
+    const size_t m = hi - lo;
+    const size_t o_off = 0, o_len = up16(8 * m), o_kind = o_len + up16(4 * m), o_body = o_kind + up16(m);
+    if ((rc = sign_buf(D, D.sign_in, o_body + bytes + 16))) return rc;
+    if ((rc = sign_buf(D, D.sign_out, 32 * m))) return rc;
+    pack.assign(bytes, 0);
+    offs.resize(m);
+    size_t at = 0;
+    for (size_t i = 0; i < m; ++i) {
+      offs[i] = o_body + at;
+      if (body_len[lo + i]) std::memcpy(pack.data() + at, bodies + body_off[lo + i], body_len[lo + i]);
+      at += up16(body_len[lo + i]);
+    }
+    uint8_t* in = (uint8_t*)D.sign_in.p;
+    hipStream_t st = D.stream;
+    SV_HIP(hipMemcpyAsync(in + o_off, offs.data(), 8 * m, hipMemcpyHostToDevice, st));
+    SV_HIP(hipMemcpyAsync(in + o_len, body_len + lo, 4 * m, hipMemcpyHostToDevice, st));
+    SV_HIP(hipMemcpyAsync(in + o_kind, body_kind + lo, m, hipMemcpyHostToDevice, st));
+    if (bytes) SV_HIP(hipMemcpyAsync(in + o_body, pack.data(), bytes, hipMemcpyHostToDevice, st));
+    SV_HIP(sv_launch_txhash(D.grid * 8, network_id, in, (const uint64_t*)(in + o_off), (const uint32_t*)(in + o_len),
+                            in + o_kind, m, nullptr, 0, nullptr, D.sign_out.p, st));
+    SV_HIP(hipMemcpyAsync(digests + 32 * lo, D.sign_out.p, 32 * m, hipMemcpyDeviceToHost, st));
+    SV_HIP(hipStreamSynchronize(st));
+    lo = hi;
+  }
+  return SV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sv_ed25519_sign_batch(const uint8_t* seed, size_t k, const uint32_t* key_of, const uint8_t* msg,
+                          const uint64_t* msg_off, const uint32_t* msg_len, uint32_t fixed_msg_len, size_t n,
+                          uint8_t* sig, uint8_t* pk, const sv_opts* opts) {
+  LifeGuard life_;
+  int rc = check_opts(opts);
+  if (rc) return rc;
+  if (sv_sign_check(seed, k, key_of, msg, msg_off, msg_len, fixed_msg_len, n, sig))
+    return fail(SV_ERR_INVALID_ARG, "sign batch: null pointer, key_of NULL with k != n, key_of[i] >= k, or k / n >= 2^32");
+  if (k == 0) return SV_OK;
+  if ((rc = debug_fail())) return rc;
+  Device* D;
+  if ((rc = sign_slot(opts, D))) return rc;
+  return sign_host(*D, seed, k, key_of, msg, msg_off, msg_len, fixed_msg_len, n, sig, pk);
+}
+
+int sv_ed25519_sign_batch_device(int device, const void* d_seed, size_t k, const uint32_t* d_key_of,
+                                 const void* d_msg, const uint64_t* d_msg_off, const uint32_t* d_msg_len,
+                                 uint32_t fixed_msg_len, size_t n, void* d_sig, void* d_pk, void* stream) {
+  LifeGuard life_;
+  Device* Dp;
+  int rc = slot_arg(device, Dp);
+  if (rc) return rc;
+  if ((uint64_t)k >> 32 || (uint64_t)n >> 32) return fail(SV_ERR_INVALID_ARG, "sign batch: k or n >= 2^32");
+  if (k == 0 && n == 0) return SV_OK;
+  if ((k && !d_seed) || (n && !d_sig)) return fail(SV_ERR_INVALID_ARG, "null device buffer");
+  if (n && (fixed_msg_len ? !d_msg : (!d_msg_off || !d_msg_len)))
+    return fail(SV_ERR_INVALID_ARG, "null msg / msg_off / msg_len");
+  if (!aligned16(d_seed) || !aligned16(d_sig) || !aligned16(d_pk))
+    return fail(SV_ERR_ALIGN, "seed/sig/pk must be 16-byte aligned");
+  if ((rc = debug_fail())) return rc;
+  Device& D = *Dp;
+  return device_call(
+      D, stream,
+      [&]() -> int {
+        int r = sign_ready(D);
+        return r ? r : sign_buf(D, D.sign_rec, sv_sign_rec_bytes(k));
+      },
+      [&] {
+        return sign_launch(D, d_seed, k, d_key_of, d_msg, d_msg_off, d_msg_len, fixed_msg_len, n, d_sig, d_pk,
+                           nullptr);
+      });
+}
+
+int sv_ed25519_sign_txbodies(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                             const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                             const uint64_t* sig_begin, const uint8_t* seed, size_t k, const uint32_t* key_of,
+                             size_t n, uint8_t* hint, uint8_t* sig, uint8_t* pk, uint8_t* digests,
+                             const sv_opts* opts) {
+  LifeGuard life_;
+  int rc = check_opts(opts);
+  if (rc) return rc;
+  if (sv_sign_txbodies_check(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, seed, k, key_of, n,
+                             hint, sig))
+    return fail(SV_ERR_INVALID_ARG,
+                "sign tx bodies: null pointer, body kind > 2, malformed sig_begin, key_of[i] >= k, or k / n >= 2^32");
+  if (n_bodies == 0 && k == 0) return SV_OK;
+  if ((rc = debug_fail())) return rc;
+  Device* D;
+  if ((rc = sign_slot(opts, D))) return rc;
+  std::vector<uint8_t> own_dig, own_pk;
+  if (!digests && n_bodies) {
+    own_dig.resize(32 * n_bodies);
+    digests = own_dig.data();
+  }
+  if (n_bodies && (rc = sign_txdigests(*D, network_id, bodies, body_off, body_len, body_kind, n_bodies, digests)))
+    return rc;
+  if (k == 0) return SV_OK;
+  if (!pk) {
+    own_pk.resize(32 * k);
+    pk = own_pk.data();
+  }
+  // fixed-32 signing over the per-signature digests, then the hints from the public keys
+  std::vector<uint8_t> msg(32 * std::max<size_t>(n, 1));
+  for (size_t t = 0; t < n_bodies; ++t)
+    for (uint64_t s = sig_begin[t]; s < sig_begin[t + 1]; ++s) std::memcpy(&msg[32 * s], digests + 32 * t, 32);
+  if ((rc = sign_host(*D, seed, k, key_of, msg.data(), nullptr, nullptr, 32, n, sig, pk))) return rc;
+  for (size_t s = 0; s < n; ++s) std::memcpy(hint + 4 * s, pk + 32 * (size_t)key_of[s] + 28, 4);
+  return SV_OK;
+}
+
+int sv_ed25519_sign_txbodies_device(int device, const uint8_t* network_id, const void* d_bodies,
+                                    const uint64_t* d_body_off, const uint32_t* d_body_len,
+                                    const uint8_t* d_body_kind, size_t n_bodies, const uint64_t* d_sig_begin,
+                                    const void* d_seed, size_t k, const uint32_t* d_key_of, size_t n, void* d_hint,
+                                    void* d_sig, void* d_pk, void* d_digests, void* stream) {
+  LifeGuard life_;
+  if (!network_id || (n_bodies && (!d_bodies || !d_body_off || !d_body_len || !d_body_kind)) ||
+      (n && (n_bodies == 0 || !d_sig_begin || !d_key_of || !d_hint || !d_sig)) || (k && !d_seed))
+    return fail(SV_ERR_INVALID_ARG, "sign tx bodies: null pointer");
+  if ((uint64_t)k >> 32 || (uint64_t)n >> 32) return fail(SV_ERR_INVALID_ARG, "sign tx bodies: k or n >= 2^32");
+  if (!aligned16(d_seed) || !aligned16(d_sig) || !aligned16(d_pk) || !aligned16(d_digests) ||
+      ((uintptr_t)d_hint & 3u))
+    return fail(SV_ERR_ALIGN, "seed/sig/pk/digests must be 16-byte aligned, hint 4-byte aligned");
+  int rc;
+  if ((rc = debug_fail())) return rc;
+  Device* Dp;
+  if ((rc = slot_arg(device, Dp))) return rc;
+  if (n_bodies == 0 && k == 0) return SV_OK;
+  Device& D = *Dp;
+  return device_call(
+      D, stream,
+      [&]() -> int {
+        int r = sign_ready(D);
+        if (!r) r = sign_buf(D, D.sign_rec, sv_sign_rec_bytes(k));
+        return r ? r : ensure_txmsg(D, n);
+      },
+      [&]() -> int {
+        SV_HIP(sv_launch_txhash(D.grid * 8, network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies,
+                                d_sig_begin, n, D.txmsg.p, d_digests, D.stream));
+        return sign_launch(D, d_seed, k, d_key_of, D.txmsg.p, nullptr, nullptr, 32, n, d_sig, d_pk, d_hint);
+      });
+}
+
 int sv_timing_enable(int enable) {
   LifeGuard life_;
   g_timing.store(enable ? 1 : 0);
@@ -2362,6 +2657,8 @@ int sv_workspace_bytes(int device, size_t* bytes) {
   std::lock_guard<std::mutex> g(Dp->mu);
   size_t b = Dp->ws.cap + Dp->txmsg.cap + Dp->txpk.cap + Dp->txsg.cap + Dp->txpair.cap + Dp->txchk.cap + Dp->txpp.cap;
   b += Dp->txatab.cap + Dp->txaws.cap + Dp->txarows.cap + Dp->txres.cap + Dp->vc.bytes() + Dp->as.bytes();
+  b += Dp->sign_rec.cap + Dp->sign_seed.cap + Dp->sign_in.cap + Dp->sign_out.cap;
+  if (Dp->sign_ctab) b += sv_comb_btab_bytes();
   for (const LatCtx& c : Dp->lat.ctx) b += c.ws.cap + c.d_in.cap + c.d_out.cap + c.d_keys.cap;
   *bytes = b;
   return SV_OK;

@@ -22,6 +22,7 @@
 // the multiplications here
 #define SV_HOST_FE51 1
 #include "verify_core.h"
+#include "sign_core.h"
 // (hash_dev.h's whole-message hashes are device-side helpers, unused here)
 #pragma GCC diagnostic push
 #pragma GCC diagnostic ignored "-Wunused-function"
@@ -81,9 +82,144 @@ bool verify_one(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, uint3
   return ok && sv_is_identity(P);
 }
 
+// ---------------------------------------------------------------- signing
+// The comb tables of B (comb.h) for the host signer (sign_core.h), built at
+// first use: 32 x 129 entries, a few tens of milliseconds on four threads.
+std::vector<sv_u4> g_ctab;
+std::once_flag g_conce;
+
+void build_ctab() {
+  g_ctab.assign((size_t)SV_CB_DW / 4, sv_u4{0, 0, 0, 0});
+  const unsigned T = 4;
+  std::vector<std::thread> th;
+  for (unsigned t = 0; t < T; ++t)
+    th.emplace_back([t] {
+      for (int id = (int)t; id < SV_CB_POS * SV_CB_ENT; id += (int)T)
+        sv_comb_bentry((uint32_t*)g_ctab.data() + (size_t)id * SV_CE_DW, id / SV_CB_ENT, id % SV_CB_ENT);
+    });
+  for (auto& x : th) x.join();
+}
+
+template <class F>
+void sign_threads(size_t n, int threads, size_t grain, F f) {
+  size_t T = threads > 0 ? (size_t)threads : std::min<size_t>(16, std::max(1u, std::thread::hardware_concurrency()));
+  T = std::max<size_t>(1, std::min(T, n / grain));
+  std::vector<std::thread> th;
+  for (size_t t = 1; t < T; ++t) th.emplace_back([&, t] { f(n * t / T, n * (t + 1) / T); });
+  f(0, n / T);
+  for (auto& x : th) x.join();
+}
+
+// Keys once, then the messages (arguments already checked).  hint (optional):
+// n x 4, bytes 28..31 of each signer's public key.
+void sign_cpu(const uint8_t* seed, size_t k, const uint32_t* key_of, const uint8_t* msg, const uint64_t* msg_off,
+              const uint32_t* msg_len, uint32_t fixed_len, size_t n, uint8_t* sig, uint8_t* pk, uint8_t* hint,
+              int threads) {
+  std::call_once(g_conce, build_ctab);
+  const uint32_t* ctab = (const uint32_t*)g_ctab.data();
+  std::vector<uint32_t> rec(k * SV_SIGN_REC_DW);
+  sign_threads(k, threads, 8, [&](size_t a, size_t b) {
+    for (size_t j = a; j < b; ++j) {
+      uint32_t sd[8];
+      words(sd, seed + 32 * j);
+      sv_sign_expand(&rec[j * SV_SIGN_REC_DW], sd, ctab);
+      if (pk) std::memcpy(pk + 32 * j, &rec[j * SV_SIGN_REC_DW + 16], 32);
+    }
+  });
+  sign_threads(n, threads, 8, [&](size_t a, size_t b) {
+    for (size_t i = a; i < b; ++i) {
+      const uint32_t* r = &rec[(size_t)(key_of ? key_of[i] : i) * SV_SIGN_REC_DW];
+      const uint32_t len = fixed_len ? fixed_len : msg_len[i];
+      const uint8_t* m = !msg ? nullptr : fixed_len ? msg + (size_t)fixed_len * i : msg + msg_off[i];
+      uint32_t s[16];
+      sv_sign_msg(s, r, m, len, ctab);
+      std::memcpy(sig + 64 * i, s, 64);
+      if (hint) std::memcpy(hint + 4 * i, &r[23], 4);
+    }
+  });
+  // (the expanded keys leave no copy behind)
+  volatile uint32_t* z = rec.data();
+  for (size_t i = 0; i < rec.size(); ++i) z[i] = 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int sv_sign_check(const uint8_t* seed, size_t k, const uint32_t* key_of, const uint8_t* msg, const uint64_t* msg_off,
+                  const uint32_t* msg_len, uint32_t fixed_len, size_t n, const uint8_t* sig) {
+  if ((uint64_t)k >> 32 || (uint64_t)n >> 32) return SV_ERR_INVALID_ARG;
+  if ((k && !seed) || (n && !sig)) return SV_ERR_INVALID_ARG;
+  if (n == 0) return SV_OK;
+  if (!key_of && k != n) return SV_ERR_INVALID_ARG;
+  if (fixed_len) {
+    if (!msg) return SV_ERR_INVALID_ARG;
+  } else {
+    if (!msg_off || !msg_len) return SV_ERR_INVALID_ARG;
+    if (!msg)
+      for (size_t i = 0; i < n; ++i)
+        if (msg_len[i]) return SV_ERR_INVALID_ARG;
+  }
+  if (key_of)
+    for (size_t i = 0; i < n; ++i)
+      if (key_of[i] >= k) return SV_ERR_INVALID_ARG;
+  return SV_OK;
+}
+
+int sv_sign_txbodies_check(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                           const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                           const uint64_t* sig_begin, const uint8_t* seed, size_t k, const uint32_t* key_of, size_t n,
+                           const uint8_t* hint, const uint8_t* sig) {
+  if (!network_id || !sig_begin) return SV_ERR_INVALID_ARG;
+  if (n_bodies && (!body_off || !body_len || !body_kind)) return SV_ERR_INVALID_ARG;
+  if ((uint64_t)k >> 32 || (uint64_t)n >> 32) return SV_ERR_INVALID_ARG;
+  if ((k && !seed) || (n && (!key_of || !hint || !sig))) return SV_ERR_INVALID_ARG;
+  if (sig_begin[0] != 0 || sig_begin[n_bodies] != n) return SV_ERR_INVALID_ARG;
+  for (size_t t = 0; t < n_bodies; ++t) {
+    if (sig_begin[t + 1] < sig_begin[t] || body_kind[t] > 2) return SV_ERR_INVALID_ARG;
+    if (body_len[t] && !bodies) return SV_ERR_INVALID_ARG;
+  }
+  for (size_t i = 0; i < n; ++i)
+    if (key_of[i] >= k) return SV_ERR_INVALID_ARG;
+  return SV_OK;
+}
+
+int sv_ed25519_sign_batch_cpu(const uint8_t* seed, size_t k, const uint32_t* key_of, const uint8_t* msg,
+                              const uint64_t* msg_off, const uint32_t* msg_len, uint32_t fixed_msg_len, size_t n,
+                              uint8_t* sig, uint8_t* pk, int threads) {
+  int rc = sv_sign_check(seed, k, key_of, msg, msg_off, msg_len, fixed_msg_len, n, sig);
+  if (rc) return rc;
+  if (k == 0) return SV_OK;
+  sign_cpu(seed, k, key_of, msg, msg_off, msg_len, fixed_msg_len, n, sig, pk, nullptr, threads);
+  return SV_OK;
+}
+
+int sv_ed25519_sign_txbodies_cpu(const uint8_t* network_id, const uint8_t* bodies, const uint64_t* body_off,
+                                 const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
+                                 const uint64_t* sig_begin, const uint8_t* seed, size_t k, const uint32_t* key_of,
+                                 size_t n, uint8_t* hint, uint8_t* sig, uint8_t* pk, uint8_t* digests, int threads) {
+  int rc = sv_sign_txbodies_check(network_id, bodies, body_off, body_len, body_kind, n_bodies, sig_begin, seed, k,
+                                  key_of, n, hint, sig);
+  if (rc) return rc;
+  // the digests through the tx-body CPU form (no signatures), then fixed-32 signing over them
+  std::vector<uint8_t> own;
+  if (!digests && n_bodies) {
+    own.resize(32 * n_bodies);
+    digests = own.data();
+  }
+  if (n_bodies) {
+    const std::vector<uint64_t> none(n_bodies + 1, 0);
+    rc = sv_ed25519_verify_txbodies_cpu(network_id, bodies, body_off, body_len, body_kind, n_bodies, none.data(),
+                                        nullptr, nullptr, 0, nullptr, digests, threads);
+    if (rc) return rc;
+  }
+  if (k == 0) return SV_OK;
+  std::vector<uint8_t> msg(32 * std::max<size_t>(n, 1));
+  for (size_t t = 0; t < n_bodies; ++t)
+    for (uint64_t s = sig_begin[t]; s < sig_begin[t + 1]; ++s) std::memcpy(&msg[32 * s], digests + 32 * t, 32);
+  sign_cpu(seed, k, key_of, msg.data(), nullptr, nullptr, 32, n, sig, pk, hint, threads);
+  return SV_OK;
+}
 
 int sv_ed25519_verify_batch_cpu(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, const uint64_t* msg_off,
                                 const uint32_t* msg_len, size_t n, uint8_t* verdict, int threads) {
