@@ -119,6 +119,11 @@ typedef struct svh_engine_stats {
   uint64_t gpu_signatures, gpu_batches, cpu_signatures, fallbacks;
 } svh_engine_stats;
 void svh_engine_counts_ex(svh_engine_stats* out); /* flushes all four */
+/* The verdict audit's `mismatches` of engine slot `device` (sv_audit_get_stats; waits for the slot's kernel
+ * stream): rows where the textbook verifier disagreed with the engine.  With SV_AUDIT_STRICT set such a batch
+ * comes back as SV_ERR_AUDIT and is re-run on the CPU path like any engine error (a fallback is counted, nothing
+ * of the failed call is cached).  0 where the engine cannot be asked (no device). */
+uint64_t svh_audit_mismatches(int device);
 /* Batch-size and latency histograms (PubKeyUtils::flushEngineHistograms):
  * out[0..31] GPU batch sizes, [32..63] GPU latencies (us), [64..95] CPU-path
  * batch sizes, [96..127] CPU-path latencies; bucket b counts values v with

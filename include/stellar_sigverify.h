@@ -1117,6 +1117,118 @@ int sv_ed25519_verify_device_cached(int device, const void* d_pk, const void* d_
                                     void* d_hit /* optional, n bytes */, void* d_keys /* optional, n x 32 */,
                                     void* stream);
 
+/* The verdict audit (csrc/audit.h, csrc/sv_audit.hip).  Behind
+ * a verify launch of the bulk route, a deterministic sample of its rows is
+ * verified again on the same stream by the textbook equation -- libsodium's
+ * steps (1)-(8) with the full-length [h](-A) + [S]B ladder of
+ * csrc/verify_core.h sv_verify_core: no half-size equation, no per-key table,
+ * no verdict cache -- and compared with the verdict bytes the caller will see.
+ * Rows whose verdict came from the verdict cache are sampled like any other.
+ *
+ *   OFF BY DEFAULT (what == 0, or the SV_AUDIT / SV_AUDIT_ONE_IN / SV_AUDIT_SEED
+ *   environment variables, read at first use): then no call allocates,
+ *   launches, waits for or returns anything more than before.
+ *   The pick: row i of the slot's audited launch number seq is audited iff
+ *     (what & SV_AUDIT_REJECTS) and verdict[i] == 0, or
+ *     (what & SV_AUDIT_SAMPLE) and mix(seed, seq, i) % one_in == 0
+ *   (mix: the 64-bit mixer written out in csrc/audit.h; one_in == 1: every
+ *   row).  The picks are taken in ascending row order, only the first `budget`
+ *   of a launch are audited (0: 65,536; at most SV_AUDIT_BUDGET_MAX) and the
+ *   rest count as over_budget.  Nothing waits on the host: the audit kernels
+ *   are queued behind the verify kernels and add to device counters.
+ *   A disagreement never changes a verdict byte.  It is counted (mismatches)
+ *   and recorded in the slot's ring of SV_AUDIT_RING records, oldest first;
+ *   what does not fit counts as records_lost.
+ *   Audited: every caller-visible verdict array of the bulk route -- raw
+ *   batches, the tx-body, hinted, check, decide, accounts and ledger forms,
+ *   the device-resident forms, cached launches with their hits.  NOT audited:
+ *   the latency lane (batches of at most 12,288 signatures on the automatic
+ *   path); its launches count in lane_launches.  Check decisions and tx
+ *   results are not audited, only verify verdicts.
+ *
+ * sv_set_audit is process-wide; what == 0 turns the audit off and frees its
+ * buffers (counters and ring included).  SV_ERR_INVALID_ARG: unknown bits,
+ * SV_AUDIT_SAMPLE with one_in == 0, a budget above SV_AUDIT_BUDGET_MAX.
+ * SV_AUDIT_STRICT: a host-buffer form on the bulk route -- the raw batches and
+ * every tx-body, hinted, check, decide, accounts and ledger form -- returns
+ * SV_ERR_AUDIT if its slot's `mismatches` moved during the call, or during any
+ * slice of a sharded call (one more 8-byte read-back per slice, after the
+ * slice's last wait, and only in strict mode).  The verdicts already copied
+ * out are unspecified then, as on any engine error, and the caller re-runs the
+ * batch on the CPU path.  Device-resident forms never wait and never return
+ * SV_ERR_AUDIT: their mismatches show in the stats, and the slot's next strict
+ * host-buffer slice answers for them (the count is compared with its value
+ * at the last strict read-back, or at the sv_set_audit that set the bit).
+ * sv_audit_get_stats / sv_audit_read wait for the slot's kernel stream.
+ * sv_audit_read hands out the ring's records oldest first, at most cap of
+ * them, and consumes what it hands out.  Before a record leaves, the engine
+ * runs sv_verify_core on the HOST (radix-2^51 field) over the record's bytes
+ * and stores the result in cpu_verdict: the arbitration between engine and
+ * audit.  A message longer than SV_AUDIT_MSG_MAX is recorded truncated
+ * (SV_AUDIT_REC_TRUNCATED) and gets cpu_verdict 0xFF.
+ * sv_audit_device: audits n claimed verdict bytes from anywhere against the
+ * textbook kernel, into the slot's counters and ring; stream semantics and
+ * alignment rules of sv_ed25519_verify_device (d_pk, d_sig 16-byte aligned);
+ * no wait.  It works with the process-wide audit off (o->what says what to
+ * pick; o->seq names the launch).
+ * sv_audit_batch_cpu: the CPU twin -- the same pick, budget and record rules,
+ * sv_verify_core on the host; stats / rec are the caller's (rec holds at most
+ * min(cap, SV_AUDIT_RING) records, the rest counts as records_lost; every
+ * record's cpu_verdict equals its audit_verdict, for a truncated record too:
+ * the twin has the whole message).  Fully determined by its arguments.
+ * The verify kernel holds 256 VGPRs at two waves per SIMD; its fixed-32 form
+ * uses no scratch, the any-length form spills 36 bytes per lane
+ * (profiles/r18/audit/kernel_resources.csv). */
+#define SV_AUDIT_REJECTS 1u
+#define SV_AUDIT_SAMPLE 2u
+#define SV_AUDIT_STRICT 4u
+#define SV_ERR_AUDIT (-9)
+#define SV_AUDIT_BUDGET_MAX ((size_t)1 << 22)
+#define SV_AUDIT_MSG_MAX 512
+#define SV_AUDIT_RING 64
+#define SV_AUDIT_REC_TRUNCATED 1u
+int sv_set_audit(uint32_t what, uint32_t one_in, uint64_t seed, size_t budget);
+typedef struct sv_audit_stats {
+  uint64_t struct_size;     /* in: sizeof(sv_audit_stats) of the caller; fields past it are not written */
+  uint64_t what;            /* the setting in force (0: off) */
+  uint64_t seq;             /* audited launches of the slot so far: the seq of the next one */
+  uint64_t audited;         /* rows verified again */
+  uint64_t audited_rejects; /* ... whose engine verdict was a reject */
+  uint64_t over_budget;     /* picked rows past the launch's budget: not audited */
+  uint64_t mismatches;      /* audited rows where engine and audit disagree */
+  uint64_t records_lost;    /* mismatches the full ring could not take */
+  uint64_t records_held;    /* records waiting in the ring */
+  uint64_t lane_launches;   /* latency-lane launches while the audit was on: not audited */
+  uint64_t bytes;           /* device memory the slot's audit holds now */
+  double kernel_ms;         /* time of the audit's kernels (only while sv_timing_enable is on) */
+} sv_audit_stats;
+typedef struct sv_audit_record {
+  uint64_t seq; /* the audited launch */
+  uint64_t row; /* row of that launch's verdict array */
+  uint32_t msg_len;
+  uint8_t engine_verdict, audit_verdict, cpu_verdict /* 0xFF: not arbitrated */, flags /* SV_AUDIT_REC_* */;
+  uint8_t pk[32];
+  uint8_t sig[64];
+  uint8_t msg[SV_AUDIT_MSG_MAX]; /* the first min(msg_len, SV_AUDIT_MSG_MAX) bytes, then zeros */
+} sv_audit_record;
+typedef struct sv_audit_opts {
+  uint64_t struct_size; /* sizeof(sv_audit_opts) */
+  uint32_t what;        /* SV_AUDIT_REJECTS | SV_AUDIT_SAMPLE */
+  uint32_t one_in;
+  uint64_t seed;
+  uint64_t seq;
+  uint64_t budget; /* 0: 65,536 */
+} sv_audit_opts;
+int sv_audit_get_stats(int device, sv_audit_stats* out);
+int sv_audit_read(int device, sv_audit_record* out, size_t cap, size_t* n);
+int sv_audit_device(int device, const sv_audit_opts* o, const void* d_pk, const void* d_sig, const void* d_msg,
+                    const uint64_t* d_msg_off, const uint32_t* d_msg_len, uint32_t fixed_msg_len, size_t n,
+                    const void* d_claimed /* n verdict bytes */, void* stream);
+int sv_audit_batch_cpu(const sv_audit_opts* o, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg,
+                       const uint64_t* msg_off, const uint32_t* msg_len, uint32_t fixed_msg_len, size_t n,
+                       const uint8_t* claimed, sv_audit_stats* stats, sv_audit_record* rec, size_t cap,
+                       size_t* n_rec, int threads);
+
 /* Host-side stages of the calling thread's last latency-lane batch (a batch of
  * at most one staging chunk on one slot), in microseconds: out[0] plan + pack,
  * [1] the H2D call (0 while the kernels read the image in place), [2] the kernel launch, [3] the D2H / event record calls,
@@ -1166,6 +1278,11 @@ int sv_set_key_tables(int mode, size_t slots);
  * failure word, and the call returns SV_ERR_KERNEL (the error path of a lost
  * hand-over). */
 #define SV_DBG_DROP_HANDOVER 0x80u
+/* AUDIT_DISSENT (needs SV_TEST_KNOBS=1): the audit kernel inverts its OWN
+ * verdict byte for the first picked row of every audited launch.  The engine's
+ * verdicts are untouched: it exists so that the strict path and the
+ * arbitration of sv_audit_read can be tested end to end. */
+#define SV_DBG_AUDIT_DISSENT 0x100u
 int sv_set_debug_flags(uint32_t flags);
 
 /* Host-feed probe (multi-GPU sizing).  Runs the host

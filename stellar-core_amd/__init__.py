@@ -57,8 +57,10 @@ SV_ERRORS = {
     -6: "SV_ERR_ALIGN",
     -7: "SV_ERR_KERNEL",
     -8: "SV_ERR_PAIR_CAP",
+    -9: "SV_ERR_AUDIT",
 }
 SV_ERR_PAIR_CAP = -8
+SV_ERR_AUDIT = -9
 
 EXPORTED_SYMBOLS = (
     "sv_init", "sv_shutdown", "sv_device_count", "sv_last_error_string", "sv_version",
@@ -89,6 +91,7 @@ EXPORTED_SYMBOLS = (
     "sv_ed25519_decide_txbodies_ledger_device", "sv_ed25519_decide_txbodies_ledger_cpu",
     "sv_ed25519_sign_batch", "sv_ed25519_sign_batch_device", "sv_ed25519_sign_batch_cpu",
     "sv_ed25519_sign_txbodies", "sv_ed25519_sign_txbodies_device", "sv_ed25519_sign_txbodies_cpu",
+    "sv_set_audit", "sv_audit_get_stats", "sv_audit_read", "sv_audit_device", "sv_audit_batch_cpu",
 )
 
 # a bacct entry of the ledger forms that names a store account by its ID (include/stellar_sigverify.h)
@@ -113,6 +116,8 @@ DBG_TRIVIAL_PAIR, DBG_MAX_WINDOWS, DBG_FAIL, DBG_PREP_ONLY, DBG_KEY_COLLIDE = 0x
 DBG_QUAD, DBG_NO_QUAD = 0x20, 0x40
 # three-wave cold octet: the tables' hand-over is dropped (its bounded wait runs out: every signature rejects)
 DBG_DROP_HANDOVER = 0x80
+# the audit kernel inverts its own verdict byte for the first picked row of every audited launch
+DBG_AUDIT_DISSENT = 0x100
 
 
 class SigVerifyError(RuntimeError):
@@ -192,6 +197,28 @@ class VerdictCacheStats(ctypes.Structure):
                                                   "fed_dropped")])
 
 
+class AuditStats(ctypes.Structure):
+    _fields_ = ([(f, ctypes.c_uint64) for f in ("struct_size", "what", "seq", "audited", "audited_rejects",
+                                                 "over_budget", "mismatches", "records_lost", "records_held",
+                                                 "lane_launches", "bytes")]
+                + [("kernel_ms", ctypes.c_double)])
+
+
+AUDIT_MSG_MAX, AUDIT_RING, AUDIT_BUDGET_MAX, AUDIT_REC_TRUNCATED = 512, 64, 1 << 22, 1
+
+
+class AuditRecord(ctypes.Structure):
+    _fields_ = [("seq", ctypes.c_uint64), ("row", ctypes.c_uint64), ("msg_len", ctypes.c_uint32),
+                ("engine_verdict", ctypes.c_uint8), ("audit_verdict", ctypes.c_uint8),
+                ("cpu_verdict", ctypes.c_uint8), ("flags", ctypes.c_uint8),
+                ("pk", ctypes.c_uint8 * 32), ("sig", ctypes.c_uint8 * 64), ("msg", ctypes.c_uint8 * AUDIT_MSG_MAX)]
+
+
+class AuditOpts(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint64), ("what", ctypes.c_uint32), ("one_in", ctypes.c_uint32),
+                ("seed", ctypes.c_uint64), ("seq", ctypes.c_uint64), ("budget", ctypes.c_uint64)]
+
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -264,6 +291,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.sv_verdict_cache_sync.argtypes = [ctypes.c_int]
     lib.sv_verdict_cache_lookup.argtypes = [ctypes.c_int, vp, sz, vp]
     lib.sv_verdict_cache_lookup_device.argtypes = [ctypes.c_int, vp, sz, vp, vp]
+    lib.sv_set_audit.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, sz]
+    lib.sv_audit_get_stats.argtypes = [ctypes.c_int, vp]
+    lib.sv_audit_read.argtypes = [ctypes.c_int, vp, sz, ctypes.POINTER(ctypes.c_size_t)]
+    lib.sv_audit_device.argtypes = [ctypes.c_int, ctypes.POINTER(AuditOpts), vp, vp, vp, vp, vp, ctypes.c_uint32, sz,
+                                    vp, vp]
+    lib.sv_audit_batch_cpu.argtypes = [ctypes.POINTER(AuditOpts), vp, vp, vp, vp, vp, ctypes.c_uint32, sz, vp, vp, vp,
+                                       sz, ctypes.POINTER(ctypes.c_size_t), ctypes.c_int]
     lib.sv_lat_last_trace.argtypes = [ctypes.POINTER(ctypes.c_double)]
     lib.sv_host_feed_probe.argtypes = [vp, vp, vp, ctypes.c_uint32, sz, ctypes.c_uint32, ctypes.c_int,
                                        ctypes.POINTER(FeedStats)]
@@ -1617,6 +1651,109 @@ def verify_device_cached(device: int, d_pk: int, d_sig: int, d_msg: int, n: int,
     _check(lib.sv_ed25519_verify_device_cached(device, d_pk, d_sig, d_msg, d_msg_off or None, d_msg_len or None,
                                                fixed_msg_len, n, d_verdict, d_bitmap or None, d_hit or None,
                                                d_keys or None, stream or None))
+
+
+AUDIT_REJECTS, AUDIT_SAMPLE, AUDIT_STRICT = 1, 2, 4
+
+
+def set_audit(what: int, one_in: int = 0, seed: int = 0, budget: int = 0) -> None:
+    """The verdict audit (include/stellar_sigverify.h sv_set_audit), process-wide: behind every bulk-route verify
+    launch the rejects (AUDIT_REJECTS) and / or a seeded 1-in-one_in sample of the rows (AUDIT_SAMPLE) are verified
+    again by the textbook equation; AUDIT_STRICT makes a host-buffer call that saw a disagreement return
+    SV_ERR_AUDIT.  budget: audited rows per launch (0: 65,536).  what == 0 (the default) turns it off and frees
+    its buffers."""
+    what, one_in, seed, budget = int(what), int(one_in), int(seed), int(budget)
+    if min(what, one_in, seed, budget) < 0 or what >> 32 or one_in >> 32 or seed >> 64:
+        raise ValueError("what and one_in must fit 32 bits, seed 64 bits, and none may be negative")
+    _check(load_library().sv_set_audit(what, one_in, seed, budget))
+
+
+def _audit_stats_dict(st) -> dict:
+    out = {f: int(getattr(st, f)) for f, _ in AuditStats._fields_[:-1]}
+    out["kernel_ms"] = float(st.kernel_ms)
+    return out
+
+
+def _audit_records(recs, n) -> list:
+    out = []
+    for r in recs[:n]:
+        keep = min(int(r.msg_len), AUDIT_MSG_MAX)
+        out.append({"seq": int(r.seq), "row": int(r.row), "msg_len": int(r.msg_len), "engine": int(r.engine_verdict),
+                    "audit": int(r.audit_verdict), "cpu": int(r.cpu_verdict), "flags": int(r.flags),
+                    "pk": bytes(r.pk), "sig": bytes(r.sig), "msg": bytes(r.msg)[:keep], "raw": bytes(r)})
+    return out
+
+
+def audit_stats(device: int = 0) -> dict:
+    """The slot's audit counters; waits for the slot's kernel stream."""
+    st = AuditStats()
+    st.struct_size = ctypes.sizeof(AuditStats)
+    _check(load_library().sv_audit_get_stats(device, ctypes.byref(st)))
+    return _audit_stats_dict(st)
+
+
+def audit_read(device: int = 0, cap: int = AUDIT_RING) -> list:
+    """The mismatch records the slot's ring holds, oldest first, at most `cap`; consumes them.  Each record's `cpu`
+    is the host's verdict over the record's bytes (0xFF: the message was truncated)."""
+    cap = int(cap)
+    if cap < 0:
+        raise ValueError("cap must be non-negative")
+    recs = (AuditRecord * max(cap, 1))()
+    n = ctypes.c_size_t(0)
+    _check(load_library().sv_audit_read(device, ctypes.cast(recs, ctypes.c_void_p), cap, ctypes.byref(n)))
+    return _audit_records(recs, n.value)
+
+
+def _audit_opts(what, one_in, seed, seq, budget) -> AuditOpts:
+    return AuditOpts(ctypes.sizeof(AuditOpts), int(what), int(one_in), int(seed), int(seq), int(budget))
+
+
+def audit_device(device: int, d_pk: int, d_sig: int, d_msg: int, n: int, d_claimed: int, what: int,
+                 one_in: int = 0, seed: int = 0, seq: int = 0, budget: int = 0, stream: int = 0,
+                 fixed_msg_len: int = 32, d_msg_off: int = 0, d_msg_len: int = 0) -> None:
+    """Audits n claimed verdict bytes in device memory against the textbook kernel (raw device pointers; d_pk and
+    d_sig 16-byte aligned), into the slot's counters and ring; ordered on `stream`, does not wait."""
+    n, fixed_msg_len = int(n), int(fixed_msg_len)
+    if n < 0 or fixed_msg_len < 0 or fixed_msg_len >> 32:
+        raise ValueError("n and fixed_msg_len must be non-negative (fixed_msg_len below 2^32)")
+    if n and not (d_pk and d_sig and d_msg and d_claimed):
+        raise ValueError("d_pk, d_sig, d_msg and d_claimed must be device pointers")
+    if (d_pk | d_sig) & 15:
+        raise ValueError("d_pk and d_sig must be 16-byte aligned")
+    o = _audit_opts(what, one_in, seed, seq, budget)
+    _check(load_library().sv_audit_device(device, ctypes.byref(o), d_pk or None, d_sig or None, d_msg or None,
+                                          d_msg_off or None, d_msg_len or None, fixed_msg_len, n, d_claimed or None,
+                                          stream or None))
+
+
+def audit_batch_cpu(pk, sig, msg, msg_off, msg_len, claimed, what: int, one_in: int = 0, seed: int = 0,
+                    seq: int = 0, budget: int = 0, fixed_msg_len: int = 0, cap: int = AUDIT_RING, threads: int = 0):
+    """The CPU twin of the audit (sv_audit_batch_cpu): the same pick, budget and records over host arrays, the
+    textbook verifier on the host.  fixed_msg_len != 0: message i = msg[i * fixed_msg_len:][:fixed_msg_len], and
+    msg_off / msg_len are not read.  Returns (stats, records)."""
+    pk, sig = _u8(pk, 32), _u8(sig, 64)
+    n = pk.shape[0]
+    msg = np.ascontiguousarray(np.asarray(msg, dtype=np.uint8)).reshape(-1)
+    claimed = np.ascontiguousarray(np.asarray(claimed, dtype=np.uint8)).reshape(-1)
+    if sig.shape[0] != n or claimed.size != n:
+        raise ValueError("pk / sig / claimed row mismatch")
+    off = ln = None
+    if not fixed_msg_len:
+        off = np.ascontiguousarray(np.asarray(msg_off, dtype=np.uint64)).reshape(-1)
+        ln = np.ascontiguousarray(np.asarray(msg_len, dtype=np.uint32)).reshape(-1)
+        if off.size != n or ln.size != n:
+            raise ValueError("msg_off / msg_len row mismatch")
+    o = _audit_opts(what, one_in, seed, seq, budget)
+    st = AuditStats()
+    st.struct_size = ctypes.sizeof(AuditStats)
+    cap = int(cap)
+    recs = (AuditRecord * max(cap, 1))()
+    nr = ctypes.c_size_t(0)
+    p = lambda a: None if a is None or a.size == 0 else _ptr(a)  # noqa: E731
+    _check(load_library().sv_audit_batch_cpu(ctypes.byref(o), p(pk), p(sig), p(msg), p(off), p(ln), int(fixed_msg_len),
+                                             n, p(claimed), ctypes.byref(st), ctypes.cast(recs, ctypes.c_void_p), cap,
+                                             ctypes.byref(nr), int(threads)))
+    return _audit_stats_dict(st), _audit_records(recs, nr.value)
 
 
 LAT_TRACE_FIELDS = ("plan_pack_us", "h2d_call_us", "launch_us", "d2h_rec_us", "build_us", "sync_us", "total_us", "warm")

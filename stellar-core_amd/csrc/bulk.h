@@ -70,16 +70,20 @@ inline bool share_now(const Device& D) {
   return w > 0 && now_ns() - D.lat_last_ns.load(std::memory_order_relaxed) < w;
 }
 
+inline int audit_strict_locked(Device& D);  // (the verdict audit, below: SV_OK at once unless SV_AUDIT_STRICT is set)
+
 // Runs fn() on the slot: D.mu held, the device set, the slot's resources
 // created.  A failing call leaves the slot reusable: nothing of it may still
-// be in flight.
+// be in flight.  Every host-buffer slice of the bulk route runs here, so this
+// is where a strict audit answers for the slice's verdicts.
 template <class F>
 int with_slot(Device& D, F fn) {
   std::lock_guard<std::mutex> g(D.mu);
   SV_HIP(hipSetDevice(D.phys));
   int rc;
   if ((rc = ready_locked(D))) return rc;
-  if ((rc = fn()) != SV_OK) {
+  if ((rc = fn()) == SV_OK) rc = audit_strict_locked(D);
+  if (rc != SV_OK) {
     (void)hipStreamSynchronize(D.h2d);
     (void)hipStreamSynchronize(D.stream);
     (void)hipStreamSynchronize(D.d2h);
@@ -164,6 +168,8 @@ inline bool kt_prepare(Device& D, uint64_t n, sv_ktparams* kt) {
   return true;
 }
 
+inline size_t audit_ws_need(Device& D, uint64_t n);  // (the verdict audit, below: 0 with the audit off)
+
 // Launch on D.stream (caller holds D.mu and has set the device).  tables:
 // the launch may use the per-key tables (kt_mode / repeated_keys).
 // kp: SV_KP_* launch hints (SV_KP_IN_PLACE: the inputs are mapped host memory)
@@ -177,7 +183,8 @@ inline int launch_locked(Device& D, int mode, int path, const void* pk, const vo
   sv_ktparams ktp{};
   const int geom = launch_geometry(rp, n);
   const bool kt_on = tables && geom == SV_PATH_THROUGHPUT && kt_prepare(D, n, &ktp);
-  if ((rc = ensure_ws(D, sv_verify_ws_bytes(geom, grid, n)))) return rc;
+  // (with the audit on, room for its tables too: the pass behind this launch then never grows the workspace)
+  if ((rc = ensure_ws(D, std::max(sv_verify_ws_bytes(geom, grid, n), audit_ws_need(D, n))))) return rc;
   if ((rc = D.timer.begin(D.stream))) return rc;
   SV_HIP(sv_launch_verify(mode, geom, grid, pk, sig, msg, off, len, fixed_len, n, verdict, bitmap, D.ws.p, D.btab,
                           (g_dbg.load() & kKernelDbgMask) | (kt_on ? 0u : kp), share ? 1 : 0, kt_on ? &ktp : nullptr,
@@ -191,12 +198,124 @@ inline int launch_locked(Device& D, int mode, int path, const void* pk, const vo
   return D.timer.end(D.stream, n);
 }
 
+// ---------------------------------------------------- verdict audit
+// (the setting: engine_state.h audit_what, audit_cfg; the rules: audit.h)
+
+// Workgroups of the audit's verify kernel over a launch of n with `budget`, and the slot workspace they need
+// (one table of -A per lane, in D.ws behind the verify kernels that used it).
+inline unsigned audit_grid(Device& D, uint64_t n, uint64_t budget) {
+  Audit& A = D.audit;
+  if (!A.blocks_per_cu) A.blocks_per_cu = sv_audit_blocks_per_cu();
+  return sv_audit_grid(n, budget, (unsigned)(D.cus * A.blocks_per_cu));
+}
+// What the audit of a launch of n adds to the launch's workspace need: 0 with the audit off.
+inline size_t audit_ws_need(Device& D, uint64_t n) {
+  if (!audit_what() || !n) return 0;
+  return sv_audit_ws_bytes(audit_grid(D, n, sv_audit_budget(audit_cfg().budget)));
+}
+
+// One audit pass over n claimed verdict bytes, on D.stream (caller holds D.mu, device set): select, scan, fill,
+// verify, report (sv_audit.hip).  Nothing is waited for, except where a buffer has to grow: then the kernel stream
+// is drained first, as everywhere (a launch sized by presize_ws / launch_locked never grows D.ws here).
+inline int audit_pass_locked(Device& D, const AuditCfg& cfg, uint64_t seq, const void* pk, const void* sig,
+                             const void* msg, const uint64_t* off, const uint32_t* len, uint32_t fixed_len,
+                             uint64_t n, const void* verdict) {
+  if (n > SV_AUDIT_MAX_ROWS) return fail(SV_ERR_INVALID_ARG, "audit: more than 2^32 - 1 rows");
+  Audit& A = D.audit;
+  int rc;
+  if (!A.state.p) {
+    if ((rc = A.state.ensure(Audit::kStateBytes)) || (rc = A.h_rd.ensure(Audit::kStateBytes))) return rc;
+    SV_HIP(hipMemsetAsync(A.state.p, 0, Audit::kStateBytes, D.stream));
+  }
+  const uint64_t budget = sv_audit_budget(cfg.budget);
+  const uint64_t cap = sv_audit_clip(n, budget);
+  const size_t o_list = sv_audit_psum_bytes(n), o_av = o_list + al16(4 * cap), bytes = o_av + al16(cap);
+  if (bytes > A.buf.cap) {
+    SV_HIP(hipStreamSynchronize(D.stream));  // (a running pass reads the old one)
+    if ((rc = A.buf.ensure(bytes))) return rc;
+  }
+  sv_audit_args a;
+  a.grid = audit_grid(D, n, budget);
+  if ((rc = ensure_ws(D, sv_audit_ws_bytes(a.grid)))) return rc;
+  uint8_t* b = (uint8_t*)A.buf.p;
+  a.pk = pk;
+  a.sig = sig;
+  a.msg = msg;
+  a.off = off;
+  a.len = len;
+  a.fixed_len = fixed_len;
+  a.what = cfg.what;
+  a.one_in = cfg.one_in;
+  a.dissent = (g_dbg.load() & SV_DBG_AUDIT_DISSENT) ? 1u : 0u;
+  a.seed = cfg.seed;
+  a.seq = seq;
+  a.n = n;
+  a.budget = budget;
+  a.verdict = (const uint8_t*)verdict;
+  a.psum = (uint64_t*)b;
+  a.list = (uint32_t*)(b + o_list);
+  a.av = b + o_av;
+  a.counters = (uint64_t*)A.state.p;
+  a.ring = (sv_audit_record*)((uint8_t*)A.state.p + Audit::kRingOff);
+  a.ws = D.ws.p;
+  a.btab = D.btab;
+  if ((rc = A.timer.begin(D.stream))) return rc;
+  SV_HIP(sv_launch_audit(&a, D.stream));
+  return A.timer.end(D.stream, cap);
+}
+
+// The hook behind a bulk-route verify launch: its n verdict bytes, audited under the process-wide setting as the
+// slot's next audited launch.  With the audit off -- the default -- one atomic load and nothing else.  Under
+// SV_DBG_PREP_ONLY there are no verdicts, so there is no audit.
+inline int audit_locked(Device& D, const void* pk, const void* sig, const void* msg, const uint64_t* off,
+                        const uint32_t* len, uint32_t fixed_len, uint64_t n, const void* verdict) {
+  if (!audit_what() || n == 0 || (g_dbg.load() & SV_DBG_PREP_ONLY)) return SV_OK;
+  const AuditCfg cfg = audit_cfg();
+  if (!cfg.what) return SV_OK;
+  return audit_pass_locked(D, cfg, D.audit.seq++, pk, sig, msg, off, len, fixed_len, n, verdict);
+}
+
+// The slot's `mismatches` now (waits for D.stream; caller holds D.mu, device set); 0 before the first pass.
+inline int audit_mismatches_locked(Device& D, uint64_t* out) {
+  Audit& A = D.audit;
+  *out = 0;
+  if (!A.state.p) return SV_OK;
+  SV_HIP(hipMemcpyAsync(A.h_rd.p, (const uint64_t*)A.state.p + SV_AC_MISMATCH, 8, hipMemcpyDeviceToHost, D.stream));
+  SV_HIP(hipStreamSynchronize(D.stream));
+  *out = *(const uint64_t*)A.h_rd.p;
+  return SV_OK;
+}
+// SV_AUDIT_STRICT, at the end of a host-buffer slice that returned SV_OK (its last wait is behind it): SV_ERR_AUDIT
+// if the slot's `mismatches` moved since they were last read -- during this slice, or during a device-resident
+// call before it, whose mismatches no host call has answered for yet.
+inline int audit_strict_locked(Device& D) {
+  if (!(audit_what() & SV_AUDIT_STRICT)) return SV_OK;
+  Audit& A = D.audit;
+  uint64_t now;
+  int rc;
+  if ((rc = audit_mismatches_locked(D, &now))) return rc;
+  const uint64_t before = A.seen;
+  A.seen = now;
+  if (now != before) return fail(SV_ERR_AUDIT, "audit: the textbook verifier disagrees with a verdict of this call");
+  return SV_OK;
+}
+
+// launch_locked with the audit behind it: a caller-visible verdict array of the bulk route.
+inline int launch_audited_locked(Device& D, int mode, int path, const void* pk, const void* sig, const void* msg,
+                                 const uint64_t* off, const uint32_t* len, uint32_t fixed_len, uint64_t n,
+                                 void* verdict, void* bitmap, bool tables = false, uint32_t kp = 0) {
+  int rc;
+  if ((rc = launch_locked(D, mode, path, pk, sig, msg, off, len, fixed_len, n, verdict, bitmap, tables, kp)))
+    return rc;
+  return audit_locked(D, pk, sig, msg, off, len, fixed_len, n, verdict);
+}
+
 // The workspace of the largest launch of a call (m signatures on `path`)
 // before its first launch, so it never grows under a running kernel.
 inline int presize_ws(Device& D, int path, size_t m) {
   const int rp = resolve_path(path, m);
-  return ensure_ws(D, std::max(sv_verify_ws_bytes(rp, grid_for(D, m), m),
-                               sv_verify_ws_bytes(launch_geometry(rp, m), grid_for(D, m), m)));
+  return ensure_ws(D, std::max({sv_verify_ws_bytes(rp, grid_for(D, m), m),
+                                sv_verify_ws_bytes(launch_geometry(rp, m), grid_for(D, m), m), audit_ws_need(D, m)}));
 }
 
 // ---------------------------------------------------- verdict cache
@@ -316,7 +435,7 @@ inline int launch_cached_locked(Device& D, int mode, int path, const void* pk, c
   if (!vc_entries() || (g_dbg.load() & SV_DBG_PREP_ONLY) || n == 0 || n > SV_VC_MAX_ITEMS) {
     if (hit && n) SV_HIP(hipMemsetAsync(hit, 0, n, D.stream));
     if (keys && n && !keys_done) SV_HIP(sv_launch_hash(0, D.grid * 2, pk, sig, msg, off, len, fixed_len, n, keys, D.stream));
-    return launch_locked(D, mode, path, pk, sig, msg, off, len, fixed_len, n, verdict, bitmap, tables, kp);
+    return launch_audited_locked(D, mode, path, pk, sig, msg, off, len, fixed_len, n, verdict, bitmap, tables, kp);
   }
   VerdictCache& C = D.vc;
   if ((rc = vc_prepare(D))) return rc;
@@ -370,11 +489,14 @@ inline int launch_cached_locked(Device& D, int mode, int path, const void* pk, c
   if (nm && (rc = launch_locked(D, f32 ? 0 : 1, path, A.cpk, A.csig, f32 ? (const void*)A.cmsg : msg, A.coff, A.clen,
                                 f32 ? 32 : 0, nm, A.cverdict, nullptr, tables, 0)))
     return rc;
-  if (!nm && !bitmap) return SV_OK;
-  if ((rc = C.timer.begin(D.stream))) return rc;
-  SV_HIP(sv_launch_vc_insert(&A, nm, D.stream));
-  if (bitmap) SV_HIP(sv_launch_vc_bitmap(verdict, n, bitmap, D.stream));
-  return C.timer.end(D.stream, 0);
+  if (nm || bitmap) {
+    if ((rc = C.timer.begin(D.stream))) return rc;
+    SV_HIP(sv_launch_vc_insert(&A, nm, D.stream));
+    if (bitmap) SV_HIP(sv_launch_vc_bitmap(verdict, n, bitmap, D.stream));
+    if ((rc = C.timer.end(D.stream, 0))) return rc;
+  }
+  // all n rows against the caller's inputs, the hits among them (the launch over the misses was not audited)
+  return audit_locked(D, pk, sig, msg, off, len, fixed_len, n, verdict);
 }
 
 // H2D of a whole packed image.  While latency-lane batches are live (shared
@@ -613,8 +735,8 @@ inline int host_slice_locked(Device& D, const HostIn& in, size_t n, uint8_t* ver
       const uint32_t kp = in_place && decode_first() ? SV_KP_IN_PLACE : 0u;
       if ((rc = cached ? launch_cached_locked(D, mode, path, d, d + im.o_sig, d + im.o_msg, d_off, d_len, in.fixed, m,
                                               dv, nullptr, tables != 0, kp, nullptr, s.d_keys.p, true)
-                       : launch_locked(D, mode, path, d, d + im.o_sig, d + im.o_msg, d_off, d_len, in.fixed, m, dv,
-                                       nullptr, tables != 0, kp)))
+                       : launch_audited_locked(D, mode, path, d, d + im.o_sig, d + im.o_msg, d_off, d_len, in.fixed, m,
+                                               dv, nullptr, tables != 0, kp)))
         return rc;
       trace_at("launched");
     }
@@ -814,8 +936,8 @@ inline int tx_slice_locked(Device& D, const TxIn& in, size_t B0, size_t B1, size
     SV_HIP(sv_launch_txhash(D.grid * 8, in.nid, d + c.o_body, (const uint64_t*)(d + c.o_off),
                             (const uint32_t*)(d + c.o_len), d + c.o_kind, k, (const uint64_t*)(d + c.o_sb), m,
                             D.txmsg.p, s.d_keys.p, D.stream));
-    if (m && (rc = launch_locked(D, 0, path, d, d + c.o_sig, D.txmsg.p, nullptr, nullptr, 32, m, s.d_verdict.p,
-                                 nullptr, kt_mode() == 1)))
+    if (m && (rc = launch_audited_locked(D, 0, path, d, d + c.o_sig, D.txmsg.p, nullptr, nullptr, 32, m,
+                                         s.d_verdict.p, nullptr, kt_mode() == 1)))
       return rc;
     if (!single) {
       SV_HIP(hipEventRecord(s.done, D.stream));

@@ -1,5 +1,5 @@
 // State of the engine: error reporting, device and pinned buffers, the
-// staging slots, the latency lane's contexts, the per-key tables, the verdict cache, the Device
+// staging slots, the latency lane's contexts, the per-key tables, the verdict cache, the verdict audit, the Device
 // slot with the creation and release of its resources, the slot table and the
 // process-wide settings.  Included by sv_api.cpp (and by bulk.h and latlane.h,
 // which work on this state).
@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/stellar_sigverify.h"
+#include "audit.h"
 #include "host_env.h"
 #include "keycache.h"
 #include "keytab.h"
@@ -334,6 +335,32 @@ struct AcctReplica {
   }
 };
 
+// The verdict audit of a slot (audit.h, sv_audit.hip; bulk.h audit_locked): the device counters with the ring
+// behind them (`state`: SV_AC_WORDS words, then SV_AUDIT_RING records), the pick list, audit bytes and block sums
+// of the largest audited launch so far (`buf`), and the pinned words the counters (64 bytes) and the ring come
+// back in.  Allocated at the slot's first audited launch; touched only by kernels on D.stream, under D.mu.
+// seq: audited launches of the bulk route so far.  seen: `mismatches` as of the last read-back (the strict check
+// compares against it).  lane_launches: latency-lane launches while the audit was on, which are not audited.
+struct Audit {
+  DevBuf state, buf;
+  HostBuf h_rd;
+  uint64_t seq = 0, seen = 0;
+  int blocks_per_cu = 0;
+  std::atomic<uint64_t> lane_launches{0};
+  KernelTimer timer;  // the audit's kernels
+  static constexpr size_t kRingOff = 8 * SV_AC_WORDS;
+  static constexpr size_t kStateBytes = kRingOff + (size_t)SV_AUDIT_RING * sizeof(sv_audit_record);
+  size_t bytes() const { return state.cap + buf.cap; }
+  // (D.stream is drained)
+  void release() {
+    state.release(); buf.release(); h_rd.release();
+    timer.release();
+    timer.reset();
+    seq = seen = 0;
+    lane_launches.store(0);
+  }
+};
+
 struct Device {
   int slot = -1;
   int phys = -1;
@@ -372,6 +399,7 @@ struct Device {
   KeyTabs kt;  // (under mu)
   VerdictCache vc;  // (under mu)
   AcctReplica as;   // (under mu)
+  Audit audit;      // (under mu; lane_launches: atomic)
   Journal vj;       // keyed latency-lane batches on their way into vc (its own mutex: vjournal.h)
   std::atomic<int64_t> lat_last_ns{INT64_MIN / 2};  // steady clock of the last latency-lane batch
   std::atomic<uint64_t> shared_launches{0};          // bulk launches in shared mode
@@ -427,6 +455,40 @@ inline size_t vc_journal_rows() {
   static const size_t e =
       std::max<size_t>(1, std::min(env_size("SV_VERDICT_CACHE_JOURNAL", kJournalDefaultRows), kJournalMaxRows));
   return e;
+}
+
+// sv_set_audit: the process-wide setting.  what: the SV_AUDIT_* bits, 0 (the default) off; ~0: SV_AUDIT,
+// SV_AUDIT_ONE_IN (default 1024) and SV_AUDIT_SEED, read once at first use.  The other three words are written
+// under g_audit_mu before `what` is published.
+struct AuditCfg {
+  uint32_t what = 0, one_in = 0;
+  uint64_t seed = 0, budget = 0;
+};
+inline std::mutex g_audit_mu;
+inline std::atomic<uint32_t> g_audit_what{~0u};
+inline AuditCfg g_audit_cfg;
+inline uint32_t audit_what() {
+  uint32_t v = g_audit_what.load(std::memory_order_acquire);
+  if (v != ~0u) return v;
+  std::lock_guard<std::mutex> g(g_audit_mu);
+  v = g_audit_what.load(std::memory_order_acquire);
+  if (v != ~0u) return v;
+  AuditCfg c;
+  c.what = (uint32_t)env_size("SV_AUDIT", 0) & SV_AUDIT_WHAT_MASK;
+  c.one_in = (uint32_t)std::min<size_t>(env_size("SV_AUDIT_ONE_IN", 1024), 0xFFFFFFFFu);
+  c.seed = (uint64_t)env_size("SV_AUDIT_SEED", 0);
+  if (!c.one_in) c.what &= ~SV_AUDIT_SAMPLE;  // (what sv_set_audit refuses)
+  if (!(c.what & (SV_AUDIT_REJECTS | SV_AUDIT_SAMPLE))) c.what = 0;
+  g_audit_cfg = c;
+  g_audit_what.store(c.what, std::memory_order_release);
+  return c.what;
+}
+inline AuditCfg audit_cfg() {
+  AuditCfg c;
+  if (!audit_what()) return c;
+  std::lock_guard<std::mutex> g(g_audit_mu);
+  c = g_audit_cfg;
+  return c;
 }
 
 constexpr uint32_t kKernelDbgMask =
@@ -534,6 +596,7 @@ inline void release_device(Device& D) {
   D.kt.slots = 0;
   D.vc.release();
   D.as.release();
+  D.audit.release();
   if (D.btab) (void)hipFree(D.btab);
   if (D.dep_in) (void)hipEventDestroy(D.dep_in);
   if (D.dep_out) (void)hipEventDestroy(D.dep_out);
@@ -543,6 +606,11 @@ inline void release_device(Device& D) {
   D.btab = nullptr;
   D.stream = D.h2d = D.d2h = nullptr;
   D.ready = false;
+}
+
+// A latency-lane launch while the audit is on: counted, not audited.
+inline void audit_lane_count(Device& D) {
+  if (audit_what()) D.audit.lane_launches.fetch_add(1, std::memory_order_relaxed);
 }
 
 // Caller holds D.mu.

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../../include/stellar_host.h"
+#include "../../../include/stellar_sigverify.h"
 #include "HostPool.h"
 #include "PubKeyUtils.h"
 #include "SignatureChecker.h"
@@ -223,6 +224,11 @@ void svh_engine_counts_ex(svh_engine_stats* out) {
     out->cpu_signatures = c.cpuSignatures;
     out->fallbacks = c.fallbacks;
   }
+}
+uint64_t svh_audit_mismatches(int device) {
+  sv_audit_stats st;
+  st.struct_size = sizeof(st);
+  return sv_audit_get_stats(device, &st) == SV_OK ? st.mismatches : 0;
 }
 void svh_engine_histograms(uint64_t out[4 * 32]) {
   const auto h = PubKeyUtils::flushEngineHistograms();

@@ -348,6 +348,7 @@ inline int lat_launch_locked(Device& D, LatCtx& c, const HostIn& in, size_t n, u
   pd.t0 = std::chrono::steady_clock::now();
   pd.n = n;
   D.lat_last_ns.store(now_ns(), std::memory_order_relaxed);
+  audit_lane_count(D);
   lat_cache_ready(L);
   lat_poll(L);
   const uint32_t dbg = g_dbg.load() & kKernelDbgMask;

@@ -1,6 +1,6 @@
 // The one declaration of every extern "C" launcher and size query that
 // crosses between the kernel files (sv_kernels.hip, sv_comb.hip, sv_hash.hip,
-// sv_txhash.hip, sv_txpair.hip, sv_txcheck.hip, sv_txacct.hip, sv_txresult.hip, sv_vcache.hip, sv_sign.hip), sv_cpu.cpp and the engine (sv_api.cpp and its modules).
+// sv_txhash.hip, sv_txpair.hip, sv_txcheck.hip, sv_txacct.hip, sv_txresult.hip, sv_vcache.hip, sv_sign.hip, sv_audit.hip), sv_cpu.cpp and the engine (sv_api.cpp and its modules).
 // Included by the callers and by every definer, so a changed parameter list
 // is a compile error instead of arguments corrupted at run time.
 #pragma once
@@ -73,6 +73,10 @@ int sv_sign_txbodies_check(const uint8_t* network_id, const uint8_t* bodies, con
                            const uint32_t* body_len, const uint8_t* body_kind, size_t n_bodies,
                            const uint64_t* sig_begin, const uint8_t* seed, size_t k, const uint32_t* key_of, size_t n,
                            const uint8_t* hint, const uint8_t* sig);
+
+// The textbook verifier on the host (sv_cpu.cpp: verify_core.h sv_verify_core over the radix-2^51 field): 1 accept,
+// 0 reject.  The CPU form of the audit and the arbitration of sv_audit_read run it.
+int sv_audit_cpu_one(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, uint32_t len);
 
 }  // extern "C"
 
@@ -235,6 +239,16 @@ hipError_t sv_launch_sign_keys(const void* seed, uint32_t k, void* rec, void* pk
 hipError_t sv_launch_sign_msgs(const void* rec, uint32_t k, const uint32_t* key_of, const void* msg,
                                const uint64_t* off, const uint32_t* len, uint32_t fixed_len, uint32_t n, void* sig,
                                void* hint, const uint32_t* ctab, hipStream_t s);
+// the verdict audit (sv_audit.hip, audit.h), every kernel on the caller's one stream and no host wait: select,
+// scan and fill of the picked rows, the textbook verify over the first A->budget of them on A->grid workgroups
+// (sv_audit_grid: sized from min(n, budget), at most max_blocks; A->ws holds sv_audit_ws_bytes(grid)), and the
+// report into A->counters and A->ring.  A->psum holds sv_audit_psum_bytes(n).  The struct is host memory.
+struct sv_audit_args;
+size_t sv_audit_psum_bytes(uint64_t n);
+int sv_audit_blocks_per_cu(void);
+unsigned sv_audit_grid(uint64_t n, uint64_t budget, unsigned max_blocks);
+size_t sv_audit_ws_bytes(unsigned grid);
+hipError_t sv_launch_audit(const struct sv_audit_args* A, hipStream_t s);
 // warm-key latency path (sv_comb.hip)
 size_t sv_comb_btab_bytes(void);
 size_t sv_key_slot_bytes(void);

@@ -712,7 +712,7 @@ int sv_ed25519_verify_txbodies_device(int device, const uint8_t* network_id, con
         SV_HIP(sv_launch_txhash(D.grid * 8, network_id, d_bodies, d_body_off, d_body_len, d_body_kind, n_bodies,
                                 d_sig_begin, n, D.txmsg.p, d_digests, D.stream));
         if (!n) return SV_OK;
-        return launch_locked(D, 0, SV_PATH_AUTO, d_pk, d_sig, D.txmsg.p, nullptr, nullptr, 32, n, d_verdict, d_bitmap,
+        return launch_audited_locked(D, 0, SV_PATH_AUTO, d_pk, d_sig, D.txmsg.p, nullptr, nullptr, 32, n, d_verdict, d_bitmap,
                              kt_mode() == 1);
       });
 }
@@ -1953,6 +1953,7 @@ int sv_ed25519_verify_device(int device, const void* d_pk, const void* d_sig, co
         break;
       }
     D.lat_last_ns.store(now_ns(), std::memory_order_relaxed);
+    audit_lane_count(D);
     SV_HIP(hipEventRecord(L.ev_lat, user));
     SV_HIP(hipStreamWaitEvent(c->stream, L.ev_lat, 0));
     if ((rc = L.timer.begin(c->stream))) return rc;
@@ -1966,8 +1967,8 @@ int sv_ed25519_verify_device(int device, const void* d_pk, const void* d_sig, co
   }
   // (auto mode cannot look at device-resident keys: tables only when on)
   return device_call(D, stream, [&] {
-    return launch_locked(D, mode, SV_PATH_AUTO, d_pk, d_sig, d_msg, d_msg_off, d_msg_len, fixed_msg_len, n, d_verdict,
-                         d_bitmap, kt_mode() == 1);
+    return launch_audited_locked(D, mode, SV_PATH_AUTO, d_pk, d_sig, d_msg, d_msg_off, d_msg_len, fixed_msg_len, n,
+                                 d_verdict, d_bitmap, kt_mode() == 1);
   });
 }
 
@@ -1986,15 +1987,16 @@ int sv_set_kernel_path(int path) {
 int sv_set_debug_flags(uint32_t flags) {
   LifeGuard life_;
   if (flags & ~(SV_DBG_TRIVIAL_PAIR | SV_DBG_MAX_WINDOWS | SV_DBG_FAIL | SV_DBG_PREP_ONLY | SV_DBG_KEY_COLLIDE |
-                SV_DBG_QUAD | SV_DBG_NO_QUAD | SV_DBG_DROP_HANDOVER))
+                SV_DBG_QUAD | SV_DBG_NO_QUAD | SV_DBG_DROP_HANDOVER | SV_DBG_AUDIT_DISSENT))
     return SV_ERR_INVALID_ARG;
   if ((flags & SV_DBG_QUAD) && (flags & SV_DBG_NO_QUAD)) return SV_ERR_INVALID_ARG;
   // the knobs that change what a call returns (FAIL: every call errs;
-  // PREP_ONLY: no verdicts; DROP_HANDOVER: cold three-wave batches reject)
-  // only exist for processes that opt in
-  if ((flags & (SV_DBG_FAIL | SV_DBG_PREP_ONLY | SV_DBG_DROP_HANDOVER)) && !test_knobs_enabled())
+  // PREP_ONLY: no verdicts; DROP_HANDOVER: cold three-wave batches reject;
+  // AUDIT_DISSENT: a strict audited call errs) only exist for processes that opt in
+  if ((flags & (SV_DBG_FAIL | SV_DBG_PREP_ONLY | SV_DBG_DROP_HANDOVER | SV_DBG_AUDIT_DISSENT)) && !test_knobs_enabled())
     return fail(SV_ERR_INVALID_ARG,
-                "SV_DBG_FAIL / SV_DBG_PREP_ONLY / SV_DBG_DROP_HANDOVER need SV_TEST_KNOBS=1 in the environment");
+                "SV_DBG_FAIL / SV_DBG_PREP_ONLY / SV_DBG_DROP_HANDOVER / SV_DBG_AUDIT_DISSENT need SV_TEST_KNOBS=1 in "
+                "the environment");
   return (int)g_dbg.exchange(flags);
 }
 
@@ -2646,6 +2648,150 @@ int sv_ed25519_verify_device_cached(int device, const void* d_pk, const void* d_
   return SV_OK;
 }
 
+int sv_set_audit(uint32_t what, uint32_t one_in, uint64_t seed, size_t budget) {
+  LifeGuard life_;
+  if (what & ~SV_AUDIT_WHAT_MASK) return fail(SV_ERR_INVALID_ARG, "audit: unknown bits");
+  if ((what & SV_AUDIT_SAMPLE) && one_in == 0) return fail(SV_ERR_INVALID_ARG, "audit: SV_AUDIT_SAMPLE with one_in 0");
+  if (budget > SV_AUDIT_BUDGET_MAX) return fail(SV_ERR_INVALID_ARG, "audit: budget above 2^22 rows");
+  if (!(what & (SV_AUDIT_REJECTS | SV_AUDIT_SAMPLE))) what = 0;  // (nothing to pick: off)
+  std::lock_guard<std::mutex> g0(g_mu);
+  {
+    std::lock_guard<std::mutex> ga(g_audit_mu);
+    g_audit_cfg.what = what;
+    g_audit_cfg.one_in = one_in;
+    g_audit_cfg.seed = seed;
+    g_audit_cfg.budget = budget;
+    g_audit_what.store(what, std::memory_order_release);
+  }
+  for (Device* D : g_devs) {
+    std::lock_guard<std::mutex> g(D->mu);
+    if (D->ready) (void)hipSetDevice(D->phys);
+    if (what) {
+      // (a strict call answers for what moves from here on, not for what an earlier setting left)
+      if (D->ready && (what & SV_AUDIT_STRICT)) (void)audit_mismatches_locked(*D, &D->audit.seen);
+      continue;
+    }
+    if (D->ready) (void)hipStreamSynchronize(D->stream);
+    D->audit.release();
+  }
+  return SV_OK;
+}
+
+int sv_audit_get_stats(int device, sv_audit_stats* out) {
+  LifeGuard life_;
+  if (!out || out->struct_size < offsetof(sv_audit_stats, what))
+    return fail(SV_ERR_INVALID_ARG, "audit stats: null struct or struct_size too small");
+  Device* Dp;
+  int rc = slot_arg(device, Dp);
+  if (rc) return rc;
+  Device& D = *Dp;
+  std::lock_guard<std::mutex> g(D.mu);
+  Audit& A = D.audit;
+  sv_audit_stats s{};
+  s.struct_size = out->struct_size;
+  s.what = audit_what();
+  s.seq = A.seq;
+  s.lane_launches = A.lane_launches.load(std::memory_order_relaxed);
+  s.bytes = A.bytes();
+  if (D.ready && A.state.p) {
+    SV_HIP(hipSetDevice(D.phys));
+    SV_HIP(hipMemcpyAsync(A.h_rd.p, A.state.p, 8 * SV_AC_WORDS, hipMemcpyDeviceToHost, D.stream));
+    SV_HIP(hipStreamSynchronize(D.stream));
+    if ((rc = A.timer.harvest())) return rc;
+    const uint64_t* h = (const uint64_t*)A.h_rd.p;
+    s.audited = h[SV_AC_AUDITED];
+    s.audited_rejects = h[SV_AC_REJECTS];
+    s.over_budget = h[SV_AC_OVER];
+    s.mismatches = h[SV_AC_MISMATCH];
+    s.records_lost = h[SV_AC_LOST];
+    s.records_held = h[SV_AC_HELD];
+    s.kernel_ms = A.timer.total_ms;
+  }
+  // (a caller with a shorter struct is written only up to its struct_size)
+  std::memcpy(out, &s, std::min<size_t>((size_t)out->struct_size, sizeof(s)));
+  return SV_OK;
+}
+
+int sv_audit_read(int device, sv_audit_record* out, size_t cap, size_t* n) {
+  LifeGuard life_;
+  if (!n || (cap && !out)) return fail(SV_ERR_INVALID_ARG, "audit read: null pointer");
+  *n = 0;
+  Device* Dp;
+  int rc = slot_arg(device, Dp);
+  if (rc) return rc;
+  Device& D = *Dp;
+  std::lock_guard<std::mutex> g(D.mu);
+  Audit& A = D.audit;
+  if (!D.ready || !A.state.p) return SV_OK;
+  SV_HIP(hipSetDevice(D.phys));
+  SV_HIP(hipMemcpyAsync(A.h_rd.p, A.state.p, Audit::kStateBytes, hipMemcpyDeviceToHost, D.stream));
+  SV_HIP(hipStreamSynchronize(D.stream));
+  uint64_t* h = (uint64_t*)A.h_rd.p;
+  sv_audit_record* ring = (sv_audit_record*)((uint8_t*)A.h_rd.p + Audit::kRingOff);
+  const size_t held = (size_t)std::min<uint64_t>(h[SV_AC_HELD], SV_AUDIT_RING);
+  const size_t take = std::min(held, cap);
+  for (size_t i = 0; i < take; ++i) {
+    out[i] = ring[i];
+    // the arbitration: the textbook equation on the host (radix-2^51 field) over the record's own bytes
+    out[i].cpu_verdict = (out[i].flags & SV_AUDIT_REC_TRUNCATED)
+                             ? (uint8_t)0xFF
+                             : (uint8_t)sv_audit_cpu_one(out[i].pk, out[i].sig, out[i].msg, out[i].msg_len);
+  }
+  *n = take;
+  if (!take) return SV_OK;
+  // what is left moves to the front of the ring (the stream is idle: D.mu is held and it was drained above)
+  std::memmove(ring, ring + take, (held - take) * sizeof(sv_audit_record));
+  const uint64_t left = held - take;
+  SV_HIP(hipMemcpyAsync((uint8_t*)A.state.p + Audit::kRingOff, ring, std::max<size_t>(left, 1) * sizeof(sv_audit_record),
+                        hipMemcpyHostToDevice, D.stream));
+  h[SV_AC_HELD] = left;
+  SV_HIP(hipMemcpyAsync((uint64_t*)A.state.p + SV_AC_HELD, h + SV_AC_HELD, 8, hipMemcpyHostToDevice, D.stream));
+  SV_HIP(hipStreamSynchronize(D.stream));
+  return SV_OK;
+}
+
+int sv_audit_device(int device, const sv_audit_opts* o, const void* d_pk, const void* d_sig, const void* d_msg,
+                    const uint64_t* d_msg_off, const uint32_t* d_msg_len, uint32_t fixed_msg_len, size_t n,
+                    const void* d_claimed, void* stream) {
+  LifeGuard life_;
+  if (!o || o->struct_size < sizeof(sv_audit_opts)) return fail(SV_ERR_INVALID_ARG, "audit: null or short sv_audit_opts");
+  if ((o->what & ~(SV_AUDIT_REJECTS | SV_AUDIT_SAMPLE)) || ((o->what & SV_AUDIT_SAMPLE) && o->one_in == 0) ||
+      o->budget > SV_AUDIT_BUDGET_MAX)
+    return fail(SV_ERR_INVALID_ARG, "audit: bad sv_audit_opts");
+  Device* Dp;
+  int rc = slot_arg(device, Dp);
+  if (rc) return rc;
+  if (n == 0) return SV_OK;
+  if (!d_pk || !d_sig || !d_msg || !d_claimed) return fail(SV_ERR_INVALID_ARG, "null device buffer");
+  if (!aligned16(d_pk) || !aligned16(d_sig)) return fail(SV_ERR_ALIGN, "pk/sig must be 16-byte aligned");
+  if (fixed_msg_len == 0 && (!d_msg_off || !d_msg_len)) return fail(SV_ERR_INVALID_ARG, "null msg_off/msg_len");
+  if (n > SV_AUDIT_MAX_ROWS) return fail(SV_ERR_INVALID_ARG, "audit: more than 2^32 - 1 rows");
+  if ((rc = debug_fail())) return rc;
+  Device& D = *Dp;
+  AuditCfg cfg;
+  cfg.what = o->what;
+  cfg.one_in = o->one_in;
+  cfg.seed = o->seed;
+  cfg.budget = o->budget;
+  // (buffer growth in prep(): where it drains the slot's stream it waits for the slot's own earlier work only)
+  return device_call(
+      D, stream,
+      [&]() -> int {
+        Audit& A = D.audit;
+        const uint64_t budget = sv_audit_budget(cfg.budget), cap = sv_audit_clip(n, budget);
+        const size_t bytes = sv_audit_psum_bytes(n) + al16(4 * cap) + al16(cap);
+        if (bytes > A.buf.cap) {
+          SV_HIP(hipStreamSynchronize(D.stream));
+          int rc2;
+          if ((rc2 = A.buf.ensure(bytes))) return rc2;
+        }
+        return ensure_ws(D, sv_audit_ws_bytes(audit_grid(D, n, budget)));
+      },
+      [&] {
+        return audit_pass_locked(D, cfg, o->seq, d_pk, d_sig, d_msg, d_msg_off, d_msg_len, fixed_msg_len, n, d_claimed);
+      });
+}
+
 int sv_workspace_bytes(int device, size_t* bytes) {
   LifeGuard life_;
   int rc = ensure_init();
@@ -2657,7 +2803,7 @@ int sv_workspace_bytes(int device, size_t* bytes) {
   std::lock_guard<std::mutex> g(Dp->mu);
   size_t b = Dp->ws.cap + Dp->txmsg.cap + Dp->txpk.cap + Dp->txsg.cap + Dp->txpair.cap + Dp->txchk.cap + Dp->txpp.cap;
   b += Dp->txatab.cap + Dp->txaws.cap + Dp->txarows.cap + Dp->txres.cap + Dp->vc.bytes() + Dp->as.bytes();
-  b += Dp->sign_rec.cap + Dp->sign_seed.cap + Dp->sign_in.cap + Dp->sign_out.cap;
+  b += Dp->sign_rec.cap + Dp->sign_seed.cap + Dp->sign_in.cap + Dp->sign_out.cap + Dp->audit.bytes();
   if (Dp->sign_ctab) b += sv_comb_btab_bytes();
   for (const LatCtx& c : Dp->lat.ctx) b += c.ws.cap + c.d_in.cap + c.d_out.cap + c.d_keys.cap;
   *bytes = b;

@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "../../include/stellar_sigverify.h"
+#include "audit.h"
 #include "launch.h"
 
 namespace {
@@ -885,6 +886,105 @@ int sv_ed25519_decide_txbodies_accounts_cpu(const uint8_t* network_id, const uin
     return rc;
   sv_txresults_fold(res, A->check_begin, sig_begin, b.pok, b.pused, n_bodies, nc, n_sigs);
   return SV_OK;
+}
+
+// ---------------------------------------------------------------- the verdict audit
+// The textbook verifier on the host: verify_core.h sv_verify_core over the radix-2^51 field, with the full-length
+// ladder's own table of B (e B for e <= 2^15, as the device's table 0), built at first use on four threads.
+int sv_audit_cpu_one(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, uint32_t len) {
+  static std::vector<sv_u4> btab;
+  static std::once_flag once;
+  std::call_once(once, [] {
+    btab.assign((size_t)SV_BTAB_ENTRIES * SV_BTAB_QUADS, sv_u4{0, 0, 0, 0});
+    const unsigned T = 4;
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < T; ++t)
+      th.emplace_back([t] {
+        for (int e = (int)t; e < SV_BTAB_ENTRIES; e += (int)T)
+          sv_btab_entry((uint32_t*)&btab[(size_t)e * SV_BTAB_QUADS], e);
+      });
+    for (auto& x : th) x.join();
+  });
+  uint32_t A[8], S[8], hram[16];
+  sv_u4 R[2];
+  words(A, pk);
+  std::memcpy(R, sig, 32);
+  words(S, sig + 32);
+  // sha512_ram_var reads whole aligned dwords (sha512_dev.h sv_msg_word), up to three bytes to either side of the
+  // message: a caller's message may begin and end where its allocation does, so it is hashed from an aligned copy
+  static thread_local std::vector<uint32_t> copy;
+  if (copy.size() < (size_t)len / 4 + 1) copy.resize((size_t)len / 4 + 1);
+  if (len) std::memcpy(copy.data(), msg, len);
+  sha512_ram_var(hram, (const uint32_t*)R, A, (const uint8_t*)copy.data(), len);
+  static thread_local std::vector<sv_u4> slot(SV_SLOT_QUADS_W);
+  return sv_verify_core(A, R, S, hram, slot.data(), 1, btab.data()) ? 1 : 0;
+}
+
+int sv_audit_batch_cpu(const sv_audit_opts* o, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg,
+                       const uint64_t* msg_off, const uint32_t* msg_len, uint32_t fixed_msg_len, size_t n,
+                       const uint8_t* claimed, sv_audit_stats* stats, sv_audit_record* rec, size_t cap, size_t* n_rec,
+                       int threads) {
+  if (!o || o->struct_size < sizeof(sv_audit_opts)) return SV_ERR_INVALID_ARG;
+  if ((o->what & ~(SV_AUDIT_REJECTS | SV_AUDIT_SAMPLE)) || ((o->what & SV_AUDIT_SAMPLE) && o->one_in == 0) ||
+      o->budget > SV_AUDIT_BUDGET_MAX)
+    return SV_ERR_INVALID_ARG;
+  if (stats && stats->struct_size < offsetof(sv_audit_stats, what)) return SV_ERR_INVALID_ARG;
+  if (cap && !rec) return SV_ERR_INVALID_ARG;
+  sv_audit_stats s{};
+  s.what = o->what;
+  s.seq = o->seq;
+  auto done = [&] {
+    if (n_rec) *n_rec = (size_t)s.records_held;
+    if (stats) {
+      s.struct_size = stats->struct_size;
+      std::memcpy(stats, &s, std::min<size_t>((size_t)stats->struct_size, sizeof(s)));
+    }
+    return SV_OK;
+  };
+  if (n == 0) return done();
+  if (!pk || !sig || !claimed || n > SV_AUDIT_MAX_ROWS) return SV_ERR_INVALID_ARG;
+  if (fixed_msg_len ? !msg : (!msg_off || !msg_len)) return SV_ERR_INVALID_ARG;
+  if (!fixed_msg_len && !msg)
+    for (size_t i = 0; i < n; ++i)
+      if (msg_len[i]) return SV_ERR_INVALID_ARG;
+  // the pick, in row order, clipped to the budget
+  const uint64_t budget = sv_audit_budget(o->budget);
+  std::vector<uint32_t> list;
+  uint64_t picks = 0;
+  for (size_t i = 0; i < n; ++i)
+    if (sv_audit_pick(o->what, o->one_in, o->seed, o->seq, i, claimed[i])) {
+      if (picks < budget) list.push_back((uint32_t)i);
+      ++picks;
+    }
+  const size_t m = list.size();
+  auto mptr = [&](size_t i) { return !msg ? nullptr : fixed_msg_len ? msg + (size_t)fixed_msg_len * i : msg + msg_off[i]; };
+  auto mlen = [&](size_t i) { return fixed_msg_len ? fixed_msg_len : msg_len[i]; };
+  std::vector<uint8_t> av(m);
+  sign_threads(m, threads, 8, [&](size_t a, size_t b) {
+    for (size_t j = a; j < b; ++j) {
+      const size_t i = list[j];
+      av[j] = (uint8_t)sv_audit_cpu_one(pk + 32 * i, sig + 64 * i, mptr(i), mlen(i));
+    }
+  });
+  // the report, in row order
+  const size_t room = std::min<size_t>(cap, SV_AUDIT_RING);
+  uint64_t mismatches = 0;
+  for (size_t j = 0; j < m; ++j) {
+    const size_t i = list[j];
+    s.audited_rejects += claimed[i] == 0 ? 1 : 0;
+    if (claimed[i] == av[j]) continue;
+    const uint32_t at = sv_audit_ring_slot(SV_AUDIT_RING - room, mismatches);
+    if (at < SV_AUDIT_RING)
+      sv_audit_record_fill(&rec[at - (SV_AUDIT_RING - room)], o->seq, i, claimed[i], av[j], av[j], pk + 32 * i,
+                           sig + 64 * i, mptr(i), mlen(i));
+    ++mismatches;
+  }
+  s.audited = m;
+  s.over_budget = picks - m;
+  s.mismatches = mismatches;
+  s.records_held = std::min<uint64_t>(mismatches, room);
+  s.records_lost = mismatches - s.records_held;
+  return done();
 }
 
 int sv_ed25519_verify_cpu(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, size_t msg_len) {
