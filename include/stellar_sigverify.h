@@ -1018,7 +1018,8 @@ int sv_key_cache_get_stats(int device, sv_key_cache_stats* out);
  *   While it is on, every cached launch WAITS once on the slot's kernel stream
  *   for its miss count; the host-buffer chunk loops wait once more per chunk.
  *   Per slot: a table only knows what its own slot verified, so a repeated
- *   batch hits only where it is sliced over the slots the same way.
+ *   batch hits only where it is sliced over the slots the same way
+ *   (sv_set_verdict_cache_share, below, is the opt-in that lifts this).
  *   The raw host-buffer batch calls and the latency lane look nothing up and,
  *   by default, store nothing.  sv_set_verdict_cache_feed (below) lets keyed
  *   batches FEED the table: what the latency lane verified is journaled and
@@ -1053,6 +1054,16 @@ typedef struct sv_verdict_cache_stats {
   uint64_t fed_present;  /* drained rows whose key the table already held */
   uint64_t fed_inserted; /* drained rows stored */
   uint64_t fed_dropped;  /* drained rows that lost their claim to another row of the drain */
+  /* one view across slots (sv_set_verdict_cache_share); written only where struct_size covers them */
+  /*   shared_out           rows this slot offered to the others, once per row and not once per peer
+   *   shared_in            rows other slots appended to this slot's journal (also counted in fed_rows)
+   *   shared_skipped       rows of this slot's launches not offered: a launch with more misses than a journal
+   *                        holds, every export buffer still pending, or an export that could not be made (it
+   *                        never fails the call)
+   *   shared_pinned_bytes  pinned host memory this slot holds for exports now
+   * (one declaration of four words, in this order: everything above it is the struct as callers built before
+   * sv_set_verdict_cache_share know it) */
+  uint64_t shared_out, shared_in, shared_skipped, shared_pinned_bytes;
 } sv_verdict_cache_stats;
 int sv_verdict_cache_get_stats(int device, sv_verdict_cache_stats* out);
 
@@ -1104,6 +1115,38 @@ int sv_verdict_cache_sync(int device);
 #define SV_VC_MISS 0xFFu
 int sv_verdict_cache_lookup(int device, const uint8_t* keys /* n x 32 */, size_t n, uint8_t* out /* n */);
 int sv_verdict_cache_lookup_device(int device, const void* d_keys, size_t n, void* d_out, void* stream);
+/* One view across slots (csrc/vshare.h).  A table only knows what its own slot verified; with several slots in
+ * one process a keyed lane batch is served by one slot and a tx set is sliced over all of them, and two overlapping
+ * sets slice their common transactions differently.  sv_set_verdict_cache_share lets the slots tell each other.
+ * OFF BY DEFAULT (0, or the SV_VERDICT_CACHE_SHARE environment variable): then no call allocates, launches,
+ * copies, waits or returns anything different.  With one slot both bits do nothing at all.  Verdicts and every
+ * other output are the same for any setting; a table still holds only verdict bytes that a completed verify
+ * launch of this engine wrote, and every row still enters a table through its slot's journal and drain alone.
+ *   SV_VC_SHARE_FEED    (acts only while SV_VC_FEED_LANE is set) a journaled keyed lane batch is appended to every
+ *     slot's journal, not only its own, from the same pinned copies; every journal has its own bound and counts
+ *     its own fed_overflow.  G journal copies on the batch's return path where there was one.
+ *   SV_VC_SHARE_STORES  (needs no feed bit) a cached launch with misses also EXPORTS them: a kernel behind the
+ *     insert gathers the leading min(misses, journal_rows) rows of the miss list -- keys and verdict bytes, in
+ *     item order, whether this slot stored or dropped them; hits and rows learned through a drain are never
+ *     exported, so nothing echoes -- and one copy takes them to pinned host memory, with an event behind it.  Once
+ *     the event has completed the rows are appended to every other slot's journal, in export order per exporter,
+ *     by whichever cache entry point comes by: a cached launch, a lookup, the stats or a sync on any slot (an event
+ *     query that does not block), and the host-buffer forms for their own exports before they return (a wait for
+ *     their own stream).  The peers insert them at their next drain, by the policy of every drained row.  Rows are
+ *     exported under the conditions under which the insert runs: a failing call and a launch without misses
+ *     export nothing.  A cached launch never waits for another slot.  Bounded: a launch offers at most
+ *     journal_rows rows and a slot has at most 4 exports pending; what is beyond either counts as
+ *     shared_skipped and is simply not shared.  Pinned memory per slot: at most 4 * (33 * journal_rows rounded
+ *     up to 4096) bytes, allocated as exports need it (shared_pinned_bytes).
+ * sv_verdict_cache_sync(B) with the bit set first waits for the exports pending on any slot at the time of the
+ * call and passes them on, then drains B: a cached launch on slot A whose stream work has completed (a
+ * host-buffer form: that has returned) is in B's table when it returns, within B's journal bound and the claim
+ * policy.  Unknown bits: SV_ERR_INVALID_ARG.  With the cache off the setting is remembered and nothing else
+ * happens.  The setter drops pending shared rows (the exports on their way, and what the journals hold); so do
+ * sv_set_verdict_cache, sv_verdict_cache_clear, sv_set_verdict_cache_feed, sv_set_device_map and sv_shutdown. */
+#define SV_VC_SHARE_FEED 1u   /* a journaled keyed lane batch goes to every slot's journal, not only its own */
+#define SV_VC_SHARE_STORES 2u /* what a cached launch verified is handed to the other slots' journals */
+int sv_set_verdict_cache_share(uint32_t what);
 /* sv_ed25519_verify_device behind the slot's verdict cache: the same inputs
  * (d_pk, d_sig 16-byte aligned), the same d_verdict bytes and d_bitmap.
  * d_hit (optional, n bytes): 1 where the verdict came from the table, all 0

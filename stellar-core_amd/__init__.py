@@ -84,6 +84,7 @@ EXPORTED_SYMBOLS = (
     "sv_set_verdict_cache", "sv_verdict_cache_clear", "sv_verdict_cache_get_stats",
     "sv_ed25519_verify_device_cached",
     "sv_set_verdict_cache_feed", "sv_verdict_cache_sync", "sv_verdict_cache_lookup", "sv_verdict_cache_lookup_device",
+    "sv_set_verdict_cache_share",
     "sv_set_account_store", "sv_account_store_upsert", "sv_account_store_erase", "sv_account_store_clear",
     "sv_account_store_get_stats", "sv_account_store_read",
     "sv_ed25519_check_txbodies_ledger", "sv_ed25519_decide_txbodies_ledger",
@@ -197,6 +198,15 @@ class VerdictCacheStats(ctypes.Structure):
                                                   "fed_dropped")])
 
 
+SHARED = ("shared_out", "shared_in", "shared_skipped", "shared_pinned_bytes")
+
+
+class VerdictCacheShareStats(VerdictCacheStats):
+    """sv_verdict_cache_stats as it stands now: VerdictCacheStats (the layout before sv_set_verdict_cache_share,
+    which the engine still fills for a caller passing its size) with the shared_* fields behind it."""
+    _fields_ = [(f, ctypes.c_uint64) for f in SHARED]
+
+
 class AuditStats(ctypes.Structure):
     _fields_ = ([(f, ctypes.c_uint64) for f in ("struct_size", "what", "seq", "audited", "audited_rejects",
                                                  "over_budget", "mismatches", "records_lost", "records_held",
@@ -288,6 +298,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.sv_ed25519_verify_device_cached.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_uint32, sz, vp, vp,
                                                     vp, vp, vp]
     lib.sv_set_verdict_cache_feed.argtypes = [ctypes.c_uint32, sz]
+    lib.sv_set_verdict_cache_share.argtypes = [ctypes.c_uint32]
     lib.sv_verdict_cache_sync.argtypes = [ctypes.c_int]
     lib.sv_verdict_cache_lookup.argtypes = [ctypes.c_int, vp, sz, vp]
     lib.sv_verdict_cache_lookup_device.argtypes = [ctypes.c_int, vp, sz, vp, vp]
@@ -1577,17 +1588,30 @@ def verdict_cache_clear() -> None:
 
 def verdict_cache_stats(device: int = 0) -> dict:
     """The slot's verdict-cache counters since the capacity was last set; waits for the slot's kernel stream."""
-    st = VerdictCacheStats()
-    st.struct_size = ctypes.sizeof(VerdictCacheStats)
+    st = VerdictCacheShareStats()
+    st.struct_size = ctypes.sizeof(VerdictCacheShareStats)
     _check(load_library().sv_verdict_cache_get_stats(device, ctypes.byref(st)))
     out = {f: int(getattr(st, f)) for f, _ in VerdictCacheStats._fields_[:7]}
     out["kernel_ms"], out["wait_ms"] = float(st.kernel_ms), float(st.wait_ms)
     out.update({f: int(getattr(st, f)) for f, _ in VerdictCacheStats._fields_[9:]})
+    out.update({f: int(getattr(st, f)) for f in SHARED})
     return out
 
 
 VC_FEED_LANE, VC_FEED_BULK = 1, 2
 VC_MISS = 0xFF
+VC_SHARE_FEED, VC_SHARE_STORES = 1, 2
+
+
+def set_verdict_cache_share(what: int) -> None:
+    """What the slots tell each other about verified verdicts (include/stellar_sigverify.h
+    sv_set_verdict_cache_share): VC_SHARE_FEED appends a journaled keyed lane batch to every slot's journal,
+    VC_SHARE_STORES hands the misses a cached launch verified to the other slots' journals; 0 (the default)
+    neither.  Process-wide; drops pending shared rows."""
+    what = int(what)
+    if what < 0 or what >> 32:
+        raise ValueError("what must fit 32 bits")
+    _check(load_library().sv_set_verdict_cache_share(what))
 
 
 def set_verdict_cache_feed(sources: int, journal_rows: int = 0) -> None:

@@ -14,6 +14,11 @@
 // sv_set_verdict_cache_feed (off by default): what the slot's latency lane journaled (vjournal.h) is drained into
 // the table ahead of every cached launch's probe (vc_drain_locked), and with SV_VC_FEED_BULK the keyed chunks of
 // host_slice_locked go behind the cache too.
+//
+// sv_set_verdict_cache_share (off by default; vshare.h): with SV_VC_SHARE_STORES and more than one slot a cached
+// launch exports its misses behind its insert (vc_export_locked) and passes on, ahead of its drain, whatever any
+// slot's exports have completed (engine_state.h share_pass_all); a host-buffer slice passes its own on before it
+// returns (with_slot).
 #pragma once
 
 #include <chrono>
@@ -89,6 +94,9 @@ int with_slot(Device& D, F fn) {
     (void)hipStreamSynchronize(D.d2h);
     D.st[0].busy = D.st[1].busy = false;
   }
+  // (sv_set_verdict_cache_share: a host-buffer slice passes its own exports on before it returns -- a wait for
+  // its own stream's events, which the slice's results have as a rule waited out already)
+  if (share_stores()) share_pass(D, true);
   return rc;
 }
 
@@ -358,9 +366,11 @@ inline int vc_prepare(Device& D) {
 // lengths (4 n), every section 16-byte aligned.
 struct VcBufs {
   size_t o_keys, o_miss, o_slot, o_psum, o_missed, o_cv, o_pk, o_sig, o_msg, o_len, bytes;
+  size_t o_exp;  // the export image (33 rows; vshare.h), only while the slots share what they verified
 };
-inline VcBufs vc_layout(size_t n, bool own_keys, bool fixed32) {
+inline VcBufs vc_layout(size_t n, bool own_keys, bool fixed32, size_t exp_rows = 0) {
   VcBufs b;
+  b.o_exp = 0;
   b.o_keys = 0;
   b.o_miss = own_keys ? 32 * n : 0;
   b.o_slot = b.o_miss + al16(4 * n);
@@ -372,6 +382,10 @@ inline VcBufs vc_layout(size_t n, bool own_keys, bool fixed32) {
   b.o_msg = b.o_sig + 64 * n;
   b.o_len = b.o_msg + (fixed32 ? 32 * n : al16(8 * n));
   b.bytes = b.o_len + (fixed32 ? 0 : al16(4 * n)) + 16;
+  if (exp_rows) {  // (behind everything else: with no export the layout is what it always was)
+    b.o_exp = al16(b.bytes);
+    b.bytes = b.o_exp + al16(share_image_bytes(exp_rows));
+  }
   return b;
 }
 
@@ -416,6 +430,40 @@ inline int vc_drain_locked(Device& D) {
   return C.timer.end(D.stream, 0);
 }
 
+// The export of a cached launch behind its insert (vshare.h; caller holds D.mu, device set): the leading
+// min(nm, cap) rows of the pass's miss list -- stored or dropped here alike, the peer applies its own policy --
+// gathered into d_image (33 rows bytes of C.ws), copied to a pinned buffer of the slot's queue and queued with
+// an event behind the copy, all on D.stream.  Nothing is waited for: with every buffer pending the launch skips
+// its export and counts the rows (shared_skipped), as it counts the rows beyond `cap`.  Whoever finds the event
+// complete passes the rows on (share_pass).  An export that fails leaves nothing queued, counts its rows as skipped
+// and does not fail the call.
+inline int vc_export_locked(Device& D, const sv_vc_args& A, uint64_t nm, size_t cap, uint8_t* d_image) {
+  const size_t rows = share_offer(nm, cap);
+  const int b = D.shq.reserve(nm, rows);
+  if (b < 0) return SV_OK;
+  VerdictCache& C = D.vc;
+  int rc = share_buf_ensure(D, b, rows, cap);
+  hipError_t e = hipSuccess;
+  bool queued = false;
+  if (rc == SV_OK && (rc = C.timer.begin(D.stream)) == SV_OK) {
+    e = sv_launch_vc_export(&A, nm, rows, d_image, D.stream);
+    queued = true;
+    if (e == hipSuccess) rc = C.timer.end(D.stream, 0);
+    if (e == hipSuccess && rc == SV_OK)
+      e = hipMemcpyAsync(D.shb[b].p, d_image, share_image_bytes(rows), hipMemcpyDeviceToHost, D.stream);
+    if (e == hipSuccess && rc == SV_OK) e = hipEventRecord(D.shb[b].ev, D.stream);
+  }
+  if (e != hipSuccess || rc != SV_OK) {
+    // An export that cannot be made -- no pinned memory, say -- is no failure of the call: its verdicts, insert and
+    // bitmap are queued and valid, and only the amount of work may depend on the setting.  The rows are skipped.
+    if (queued) (void)hipStreamSynchronize(D.stream);  // (a copy that did start no longer writes the buffer)
+    D.shq.cancel(b, rows);
+    return SV_OK;
+  }
+  D.shq.commit(b, (const uint8_t*)D.shb[b].p, rows);
+  return SV_OK;
+}
+
 // launch_locked behind the slot's verdict cache (vcache.h): the same arguments, the same verdict bytes and
 // bitmap.  With the cache off -- the default -- or under SV_DBG_PREP_ONLY (no verdicts exist, so nothing may be
 // inserted) it IS launch_locked: no allocation, no kernel and no wait of its own.  With it on, all on D.stream:
@@ -439,9 +487,14 @@ inline int launch_cached_locked(Device& D, int mode, int path, const void* pk, c
   }
   VerdictCache& C = D.vc;
   if ((rc = vc_prepare(D))) return rc;
+  // (sv_set_verdict_cache_share: what the other slots' launches exported and is complete goes into the journals
+  // first -- this slot's among them -- without a wait; then the drain)
+  const bool share = share_stores();
+  if (share) share_pass_all(false);
   if ((rc = vc_drain_locked(D))) return rc;
   const bool f32 = fixed_len == 32;
-  const VcBufs L = vc_layout(n, !keys, f32);
+  const size_t share_cap = share ? vc_journal_rows() : 0;
+  const VcBufs L = vc_layout(n, !keys, f32, share_offer(n, share_cap));
   if (L.bytes > C.ws.cap) {
     SV_HIP(hipStreamSynchronize(D.stream));  // (a running pass reads the old one)
     if ((rc = C.ws.ensure(L.bytes))) return rc;
@@ -495,6 +548,7 @@ inline int launch_cached_locked(Device& D, int mode, int path, const void* pk, c
     if (bitmap) SV_HIP(sv_launch_vc_bitmap(verdict, n, bitmap, D.stream));
     if ((rc = C.timer.end(D.stream, 0))) return rc;
   }
+  if (nm && share && (rc = vc_export_locked(D, A, nm, share_cap, w + L.o_exp))) return rc;
   // all n rows against the caller's inputs, the hits among them (the launch over the misses was not audited)
   return audit_locked(D, pk, sig, msg, off, len, fixed_len, n, verdict);
 }

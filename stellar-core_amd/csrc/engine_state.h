@@ -25,6 +25,7 @@
 #include "txstore.h"
 #include "vcache.h"
 #include "vjournal.h"
+#include "vshare.h"
 
 namespace sv {
 namespace {
@@ -401,6 +402,18 @@ struct Device {
   AcctReplica as;   // (under mu)
   Audit audit;      // (under mu; lane_launches: atomic)
   Journal vj;       // keyed latency-lane batches on their way into vc (its own mutex: vjournal.h)
+  // What this slot's cached launches export to the other slots' journals (vshare.h; sv_set_verdict_cache_share):
+  // the queue of pending exports and, per buffer of it, the pinned image with the event behind its copy.  A
+  // buffer is allocated or grown under mu while the exporter has it reserved, and read by whoever passes the
+  // export on; released with D.stream drained (share_release).  shared_in: rows the others appended to vj.
+  ShareQueue shq;
+  struct ShareBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    hipEvent_t ev = nullptr;
+  } shb[kSharePending];
+  std::atomic<size_t> share_pinned{0};
+  std::atomic<uint64_t> shared_in{0};
   std::atomic<int64_t> lat_last_ns{INT64_MIN / 2};  // steady clock of the last latency-lane batch
   std::atomic<uint64_t> shared_launches{0};          // bulk launches in shared mode
   // The slot's own staging workers for multi-slot calls (shard): its slice is
@@ -455,6 +468,82 @@ inline size_t vc_journal_rows() {
   static const size_t e =
       std::max<size_t>(1, std::min(env_size("SV_VERDICT_CACHE_JOURNAL", kJournalDefaultRows), kJournalMaxRows));
   return e;
+}
+
+// sv_set_verdict_cache_share: the SV_VC_SHARE_* bits (~0: SV_VERDICT_CACHE_SHARE, resolved at the first read).
+inline std::atomic<uint32_t> g_vc_share{~0u};
+inline uint32_t vc_share() {
+  uint32_t v = g_vc_share.load(std::memory_order_relaxed);
+  if (v != ~0u) return v;
+  const uint32_t e = (uint32_t)env_size("SV_VERDICT_CACHE_SHARE", 0) & (SV_VC_SHARE_FEED | SV_VC_SHARE_STORES);
+  g_vc_share.compare_exchange_strong(v, e);
+  return g_vc_share.load(std::memory_order_relaxed);
+}
+// Whether cached launches export what they verified: the bit, the cache on and more than one slot.
+inline bool share_stores() { return (vc_share() & SV_VC_SHARE_STORES) && g_devs.size() > 1 && vc_entries(); }
+
+// The pinned image and the event of export buffer b of D at `rows` rows (caller holds D.mu, device set, and has
+// the buffer reserved: nothing of an earlier export is in flight in it).  A buffer that has to grow at least
+// doubles, up to the size of an export of `cap` rows -- the most a launch offers -- so a run of growing launches
+// frees and allocates pinned memory (which synchronises the device) a few times, not once per launch.
+inline int share_buf_ensure(Device& D, int b, size_t rows, size_t cap) {
+  Device::ShareBuf& B = D.shb[b];
+  if (!B.ev) SV_HIP(hipEventCreateWithFlags(&B.ev, hipEventDisableTiming));
+  size_t want = share_buf_bytes(rows);
+  if (want <= B.cap) return SV_OK;
+  want = std::max(want, std::min(2 * B.cap, share_buf_bytes(std::max(rows, cap))));
+  if (B.p) (void)hipHostFree(B.p);
+  D.share_pinned.fetch_sub(B.cap);
+  B.p = nullptr;
+  B.cap = 0;
+  hipError_t e = hipHostMalloc(&B.p, want, hipHostMallocDefault);
+  if (e != hipSuccess) {
+    B.p = nullptr;
+    return fail(SV_ERR_ALLOC, std::string("hipHostMalloc: ") + hipGetErrorString(e));
+  }
+  B.cap = want;
+  D.share_pinned.fetch_add(want);
+  return SV_OK;
+}
+// Forgets D's pending exports and frees their memory, counters included (caller holds D.mu; D.stream is drained,
+// or the slot never was ready).
+inline void share_release(Device& D) {
+  D.shq.reset();
+  for (Device::ShareBuf& B : D.shb) {
+    if (B.p) (void)hipHostFree(B.p);
+    if (B.ev) (void)hipEventDestroy(B.ev);
+    B = Device::ShareBuf();
+  }
+  D.share_pinned.store(0);
+  D.shared_in.store(0);
+}
+// Passes D's complete exports on to every other slot's journal, in export order (vshare.h pass()).  Holds no
+// Device::mu of another slot and waits for none; wait: for the events of the exports pending now (D's own
+// stream), else nothing is waited for at all.  An event that fails loses its export.
+inline void share_pass(Device& D, bool wait) {
+  if (!D.shq.pending()) return;
+  (void)D.shq.pass(
+      wait,
+      [&](int b, bool w) -> int {
+        const hipError_t e = w ? hipEventSynchronize(D.shb[b].ev) : hipEventQuery(D.shb[b].ev);
+        return e == hipSuccess ? 1 : e == hipErrorNotReady ? 0 : -1;
+      },
+      [&](const uint8_t* image, size_t rows) {
+        const size_t cap = vc_journal_rows();
+        for (Device* P : g_devs)
+          if (P != &D)
+            P->shared_in.fetch_add(P->vj.append(image, image + share_image_verdicts(rows), rows, cap),
+                                   std::memory_order_relaxed);
+      });
+}
+// ... of every slot: what a cache entry point does on its way (with one slot, or nothing pending, nothing).
+inline void share_pass_all(bool wait) {
+  if (g_devs.size() < 2) return;
+  for (Device* D : g_devs) share_pass(*D, wait);
+}
+// Marks every slot's pending exports as forgotten (whatever drops the journals drops them first).
+inline void share_drop_all() {
+  for (Device* D : g_devs) D->shq.drop();
 }
 
 // sv_set_audit: the process-wide setting.  what: the SV_AUDIT_* bits, 0 (the default) off; ~0: SV_AUDIT,
@@ -595,6 +684,7 @@ inline void release_device(Device& D) {
   D.kt.copied = nullptr;
   D.kt.slots = 0;
   D.vc.release();
+  share_release(D);
   D.as.release();
   D.audit.release();
   if (D.btab) (void)hipFree(D.btab);

@@ -533,8 +533,18 @@ inline int lat_slice(Device& D, const HostIn& in, size_t n, uint8_t* verdict, ui
   // keys-ready callback has already handed to the caller -- so the context stays busy for the copy.  The lane
   // itself still never touches the table.  An error appended nothing.
   if (rc == SV_OK && (vc_feed() & SV_VC_FEED_LANE) && keys && verdict && vc_entries() &&
-      !(g_dbg.load() & SV_DBG_PREP_ONLY))
-    D.vj.append(pd.kho, pd.vho, n, vc_journal_rows());
+      !(g_dbg.load() & SV_DBG_PREP_ONLY)) {
+    const size_t cap = vc_journal_rows();
+    D.vj.append(pd.kho, pd.vho, n, cap);
+    // SV_VC_SHARE_FEED (sv_set_verdict_cache_share; one more relaxed load): the same rows from the same pinned
+    // copies into every other slot's journal, each with its own bound and its own fed_overflow -- G copies on
+    // this return path where there was one
+    if ((vc_share() & SV_VC_SHARE_FEED) && g_devs.size() > 1) {
+      for (Device* P : g_devs)
+        if (P != &D) P->shared_in.fetch_add(P->vj.append(pd.kho, pd.vho, n, cap), std::memory_order_relaxed);
+      D.shq.count_out(n);
+    }
+  }
   return rc;
 }
 

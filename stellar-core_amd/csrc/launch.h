@@ -224,6 +224,9 @@ size_t sv_vc_psum_bytes(uint64_t n);
 hipError_t sv_launch_vc_probe(const struct sv_vc_args* A, hipStream_t s);
 hipError_t sv_launch_vc_insert(const struct sv_vc_args* A, uint64_t n_miss, hipStream_t s);
 hipError_t sv_launch_vc_bitmap(const void* verdict, uint64_t n, void* bitmap, hipStream_t s);
+// The export of a pass behind its insert (vshare.h): the leading rows <= n_miss rows of the miss list -- keys
+// (32 rows bytes), then verdict bytes (rows) -- into image (device memory, 33 rows bytes, 16-byte aligned).
+hipError_t sv_launch_vc_export(const struct sv_vc_args* A, uint64_t n_miss, uint64_t rows, void* image, hipStream_t s);
 // The drain of a slot's journal (vcache.h Feed): the claim and the store kernel over A->n rows with their
 // verdicts.  lookup: out[i] = the verdict the table holds for key i (keys n x 32, 16-byte aligned), or 0xFF.
 struct sv_vc_feed_args;

@@ -2457,13 +2457,16 @@ int sv_set_verdict_cache(size_t entries) {
   static_assert(SV_VERDICT_CACHE_MAX == SV_VC_MAX_ENTRIES, "the header's limit is the table's");
   std::lock_guard<std::mutex> g0(g_mu);
   g_vc_entries.store(vc_round(entries));
+  share_drop_all();  // (pending exports reach no journal from here on; their memory goes below)
   for (Device* D : g_devs) {
     std::lock_guard<std::mutex> g(D->mu);
     D->vj.reset();  // (journaled rows and the feed's counters go with the table)
-    if (!D->ready) continue;
-    (void)hipSetDevice(D->phys);
-    (void)hipStreamSynchronize(D->stream);
-    D->vc.release();  // (the next cached launch allocates an empty table of the new size)
+    if (D->ready) {
+      (void)hipSetDevice(D->phys);
+      (void)hipStreamSynchronize(D->stream);
+      D->vc.release();  // (the next cached launch allocates an empty table of the new size)
+    }
+    share_release(*D);  // (the stream is drained: every export's copy is done)
   }
   return SV_OK;
 }
@@ -2478,6 +2481,19 @@ int sv_set_verdict_cache_feed(uint32_t sources, size_t journal_rows) {
   g_vc_journal.store(journal_rows);
   // (a batch finishing on the lane right now may still append under the old setting: its rows are verdicts of
   // this engine all the same)
+  share_drop_all();
+  for (Device* D : g_devs) D->vj.drop();
+  return SV_OK;
+}
+
+int sv_set_verdict_cache_share(uint32_t what) {
+  LifeGuard life_;
+  if (what & ~(SV_VC_SHARE_FEED | SV_VC_SHARE_STORES))
+    return fail(SV_ERR_INVALID_ARG, "verdict cache share: unknown bits");
+  std::lock_guard<std::mutex> g0(g_mu);
+  g_vc_share.store(what);
+  // pending shared rows are dropped, the exports still on their way and, with the journals, those that arrived
+  share_drop_all();
   for (Device* D : g_devs) D->vj.drop();
   return SV_OK;
 }
@@ -2488,6 +2504,9 @@ int sv_verdict_cache_sync(int device) {
   int rc = slot_arg(device, Dp);
   if (rc) return rc;
   Device& D = *Dp;
+  // (sv_set_verdict_cache_share: first the exports every slot has pending now -- a wait for their events, with
+  // no Device::mu held -- so that the drain below finds their rows in this slot's journal)
+  if (share_stores()) share_pass_all(true);
   std::lock_guard<std::mutex> g(D.mu);
   if (!vc_entries()) return SV_OK;
   SV_HIP(hipSetDevice(D.phys));
@@ -2508,6 +2527,7 @@ int sv_verdict_cache_lookup(int device, const uint8_t* keys, size_t n, uint8_t* 
   Device* Dp;
   if ((rc = slot_arg(device, Dp))) return rc;
   Device& D = *Dp;
+  if (share_stores()) share_pass_all(false);
   std::lock_guard<std::mutex> g(D.mu);
   if (!vc_entries()) {
     std::memset(out, (int)SV_VC_MISS, n);
@@ -2541,6 +2561,7 @@ int sv_verdict_cache_lookup_device(int device, const void* d_keys, size_t n, voi
   if (!aligned16(d_keys)) return fail(SV_ERR_ALIGN, "keys must be 16-byte aligned");
   if ((rc = debug_fail())) return rc;
   Device& D = *Dp;
+  if (share_stores()) share_pass_all(false);
   // The drain goes in prep(), ahead of the bracket's wait for the caller's stream: where it has to wait on the host
   // (its workspace grows, or the previous drain's upload still holds the staging) it waits for the slot's own
   // earlier work only, never for what the caller's stream holds.  The rows need nothing of the caller's.
@@ -2564,14 +2585,20 @@ int sv_verdict_cache_lookup_device(int device, const void* d_keys, size_t n, voi
 int sv_verdict_cache_clear(void) {
   LifeGuard life_;
   std::lock_guard<std::mutex> g0(g_mu);
+  share_drop_all();  // (nor do rows on their way from one slot to the others: dropped before any journal is)
   for (Device* D : g_devs) {
     std::lock_guard<std::mutex> g(D->mu);
+    // (under the slot's mu: an export that a launch in flight on this slot committed after the drop above is
+    // forgotten with the table it was verified into)
+    D->shq.drop();
     D->vj.drop();  // (rows journaled before the clear do not come back after it)
     if (!D->ready) continue;
     SV_HIP(hipSetDevice(D->phys));
     int rc;
     if ((rc = vc_clear_locked(*D))) return rc;
   }
+  // (... nor what such an export handed to a journal dropped earlier in the loop)
+  for (Device* D : g_devs) D->vj.drop();
   return SV_OK;
 }
 
@@ -2580,11 +2607,13 @@ int sv_verdict_cache_get_stats(int device, sv_verdict_cache_stats* out) {
   if (!out || out->struct_size < offsetof(sv_verdict_cache_stats, kernel_ms))
     return fail(SV_ERR_INVALID_ARG, "verdict cache stats: null struct or struct_size too small");
   const bool timed = out->struct_size >= offsetof(sv_verdict_cache_stats, fed_rows);
-  const bool fed = out->struct_size >= sizeof(sv_verdict_cache_stats);
+  const bool fed = out->struct_size >= offsetof(sv_verdict_cache_stats, shared_out);
+  const bool shared = out->struct_size >= sizeof(sv_verdict_cache_stats);
   Device* Dp;
   int rc = slot_arg(device, Dp);
   if (rc) return rc;
   Device& D = *Dp;
+  if (share_stores()) share_pass_all(false);
   std::lock_guard<std::mutex> g(D.mu);
   VerdictCache& C = D.vc;
   out->entries = vc_entries();
@@ -2593,6 +2622,11 @@ int sv_verdict_cache_get_stats(int device, sv_verdict_cache_stats* out) {
   if (fed) {
     out->fed_present = out->fed_inserted = out->fed_dropped = 0;
     D.vj.counters(&out->fed_rows, &out->fed_overflow);
+  }
+  if (shared) {
+    D.shq.counters(&out->shared_out, &out->shared_skipped);
+    out->shared_in = D.shared_in.load(std::memory_order_relaxed);
+    out->shared_pinned_bytes = D.share_pinned.load();
   }
   if (!D.ready || !C.entries) return SV_OK;
   SV_HIP(hipSetDevice(D.phys));

@@ -27,6 +27,10 @@
 //            to slot[j] and atomicMin(claim[slot], miss[j])
 //   store    the row whose item stands in its claim word writes the whole entry
 //            and resets the claim word; every other row is dropped this pass
+//   export   behind the store, only while the slots share what they verified
+//            (vshare.h): one lane per 16-byte quad of the leading miss rows'
+//            keys, gathered with their verdict bytes into the image a journal
+//            drain uploads; loads and stores only
 //   bitmap   a ballot per wave over the final verdict bytes
 //   feed     the drain of the slot's journal (vjournal.h), one lane per row that
 //            arrives with its verdict: feed claim (present rows name no slot,
@@ -174,6 +178,19 @@ __global__ __launch_bounds__(SV_VCBLOCK) void sv_vc_store_kernel(sv_vc_args a, u
   }
 }
 
+// The export of a pass (vshare.h): the leading r rows of the miss list as the image a journal drain uploads -- keys
+// (32 r bytes), then verdict bytes (r).  One lane per 16-byte quad of a key, two to a row; the row's lane 0 also
+// stores its verdict byte.  r <= the pass's miss count, so j < r names a filled miss row; the image holds 33 r bytes.
+__global__ __launch_bounds__(SV_VCBLOCK) void sv_vc_export_kernel(sv_vc_args a, uint64_t r, uint8_t* image) {
+  const uint64_t t = (uint64_t)blockIdx.x * SV_VCBLOCK + threadIdx.x;
+  const uint64_t j = t >> 1;
+  const unsigned q = (unsigned)(t & 1);
+  if (j >= r) return;
+  const uint64_t i = a.miss[j];
+  ((uint4*)image)[2 * j + q] = ((const uint4*)a.keys)[2 * i + q];
+  if (q == 0) image[32 * r + j] = a.cverdict[j];
+}
+
 __global__ __launch_bounds__(SV_VCBLOCK) void sv_vc_bitmap_kernel(const uint8_t* verdict, uint64_t n, uint64_t* bitmap) {
   const uint64_t i = (uint64_t)blockIdx.x * SV_VCBLOCK + threadIdx.x;
   const bool ok = i < n && verdict[i] == 1;
@@ -259,6 +276,15 @@ hipError_t sv_launch_vc_insert(const sv_vc_args* A, uint64_t n_miss, hipStream_t
   const unsigned blocks = (unsigned)sv_vc_blocks(n_miss);
   hipLaunchKernelGGL(sv_vc_claim_kernel, dim3(blocks), dim3(SV_VCBLOCK), 0, s, *A, n_miss);
   hipLaunchKernelGGL(sv_vc_store_kernel, dim3(blocks), dim3(SV_VCBLOCK), 0, s, *A, n_miss);
+  return hipGetLastError();
+}
+
+// behind sv_launch_vc_insert of the same pass: rows <= n_miss of that pass; image: 33 rows bytes, 16-byte aligned
+hipError_t sv_launch_vc_export(const sv_vc_args* A, uint64_t n_miss, uint64_t rows, void* image, hipStream_t s) {
+  if (!rows) return hipSuccess;
+  if (rows > n_miss || n_miss > A->n || !image || ((uintptr_t)image & 15u)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(sv_vc_export_kernel, dim3((unsigned)sv_vc_blocks(2 * rows)), dim3(SV_VCBLOCK), 0, s, *A, rows,
+                     (uint8_t*)image);
   return hipGetLastError();
 }
 
